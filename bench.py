@@ -2,15 +2,19 @@
 """Headline benchmark: PanguModel forward steps/sec on synthetic 721x1440x(13*5+4) fields, fp32, one sample per GPU.
 
   python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run, one rank per GPU)
+  python bench.py ... --full                           (+ every secondary measurement and checker leg, below)
+  python bench.py ... --dump-outputs DIR               (+ the last timed step's outputs as DIR/*.npy)
 
 A step = one `PanguModel.forward` (BASELINE.json configs[1]: single-GPU fp32 forward through the HIP path) on one
 sample resident in HBM.  With N ranks every rank runs its own sample (pure data parallel, no data-path
 collective in inference): value = N*K / max-over-ranks time, "scaling": "weak".
 
-Rank 0 prints ONE JSON line with the contract keys plus
-  roofline      live HIP-event timing of the dominant kernel (the f32 MFMA projection GEMM) over the timed region
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the contract keys (metric, value,
+unit, higher_is_better, dtype, ms_per_step, ...).  With --full the same line also carries
+  roofline      live HIP-event timing of the dominant kernel (the f32 MFMA projection GEMM) in a second pass over K steps
+  bf16_forward, ddp_train*, ddp_samples_per_s, ddp_model, forward_grad_enabled_eval_ms, reference_loop_step_ms
   cpu_baseline  the CPU oracle (oracle/pangu_oracle.py, a port of the reference's algorithm) timed on this host on a
-                bounded sample (rank 0, N=1 only)
+                bounded sample (rank 0, N=1 only), and rollout_7x24h_vs_reference beside it
 """
 import argparse
 import json
@@ -44,6 +48,11 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement (per-kernel roofline pass, bf16, training, reference call conventions, "
+                         "CPU baseline, rollout vs reference); the options below apply to --full runs only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's outputs (rank 0) to DIR as float32 .npy files")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline", choices=("auto", "sample", "full", "none"), default="auto",
                     help="sample: oracle block pairs on a half-longitude slice, extrapolated (~15 s); full: also the oracle's whole "
@@ -63,7 +72,10 @@ def parse_args():
                          "on a side stream confined to 32 / 64 workgroups)")
     ap.add_argument("--grad-sync", choices=("all_reduce", "reduce_scatter"), default="all_reduce",
                     help="the collective of dist.FlatGradSync (N > 1): bucketed all_reduce(AVG), or reduce_scatter + all_gather per bucket")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def launch_ranks(args):
@@ -385,6 +397,24 @@ def synthetic_inputs(dev, seed):
     return inp, inp_s, stats, u((1, 3, 724, 1440)), u((1, 1, 1, 13, 721, 1440))
 
 
+DUMP_SAMPLE = 1 << 22      # upper-air values --dump-outputs writes (of 67.5 M: the whole tensor is 270 MB in float32)
+
+
+def dump_outputs(out, path):
+    """--dump-outputs: what a caller of the timed forward receives, `(output, output_surface)` of its last timed step, as float32
+    .npy files (33 MB in all): output_surface.npy whole (1,4,721,1440); output_sample.npy = DUMP_SAMPLE values of output
+    (1,5,13,721,1440) at sorted flat indices drawn with a fixed seed, the same on every run, so that two builds compare element
+    for element."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    up, sfc = out
+    idx = np.sort(np.random.default_rng(0).choice(up.numel(), size=DUMP_SAMPLE, replace=False))
+    sample = up.reshape(-1)[torch.from_numpy(idx).to(up.device)]
+    np.save(os.path.join(path, "output_sample.npy"), sample.float().cpu().numpy())
+    np.save(os.path.join(path, "output_surface.npy"), sfc.float().cpu().numpy())
+
+
 def main():
     args = parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -432,6 +462,34 @@ def main():
         out = step()
     barrier()
     elapsed = time.perf_counter() - t0
+    assert torch.isfinite(out[0]).all()
+
+    if dist is not None:
+        t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = t.item()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(out, args.dump_outputs)
+
+    ms = elapsed / args.steps * 1e3
+    res = {
+        "metric": "forward steps/sec (721x1440x13pl) per MI355X", "value": world * args.steps / elapsed,
+        "unit": "forward steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "PanguModel fp32 forward, 1 sample/GPU, input (1,5,13,721,1440)+(1,4,721,1440), "
+                               "depths 2-6-6-2, dims 192/384, random-init weights (BASELINE configs[1])",
+                   "parallelism": f"dp{world}"},
+        "model_tflops": FWD_GFLOP_EXEC / ms,
+        "model_flop_note": f"executed dense-contraction GFLOP per step {FWD_GFLOP_EXEC} (the reference's padded-shape ledger: {FWD_GFLOP})",
+    }
+    if not args.full:          # a plain run ends here: the headline line only
+        if rank == 0:
+            print(json.dumps(res))
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
+    # ---- --full: everything below is reported beside the headline, which is final by now
     # second pass over the same K steps with HIP-event pairs around every GEMM / attention launch (~170 event records per
     # step on the launch stream): the per-kernel roofline numbers come from here, its step time is reported beside the headline
     ops.timing_start()
@@ -443,12 +501,6 @@ def main():
     gemm_ms, gemm_flop, gemm_launches, other = ops.timing_stop("linear", also=("linear_ln", "attn"))
     fused_ms, fused_flop, fused_launches = other["linear_ln"]      # GEMMs with the fused LayerNorm+residual epilogue
     attn_ms, attn_flop, attn_launches = other["attn"]              # fused window attention (QK^T + bias + mask + softmax + PV)
-    assert torch.isfinite(out[0]).all()
-
-    if dist is not None:
-        t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = t.item()
 
     lsync = torch.cuda.synchronize      # no collectives inside the try blocks: a rank that fails must not desynchronise the others
     # ---- secondary metric: bf16 inference forward (BASELINE configs[2]/[4] precision), same inputs
@@ -804,7 +856,6 @@ def main():
         model.eval()
 
     if rank == 0:
-        ms = elapsed / args.steps * 1e3
         ms_i = elapsed_instr / args.steps * 1e3          # step time of the instrumented pass (this rank)
         achieved = gemm_flop / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
         # HBM bytes per launch of the same kernel family from the committed rocprofv3 PMC run (separate --pmc passes,
@@ -812,15 +863,7 @@ def main():
         traffic, mfma_busy, stale, pmc_commit = pmc_traffic("f32", "gemm")
         a_traffic, a_busy, a_stale, _ = pmc_traffic("f32", "attn")
         a_achieved = attn_flop / (attn_ms * 1e-3) / 1e12 if attn_ms > 0 else 0.0
-        res = {
-            "metric": "forward steps/sec (721x1440x13pl) per MI355X", "value": world * args.steps / elapsed,
-            "unit": "forward steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "PanguModel fp32 forward, 1 sample/GPU, input (1,5,13,721,1440)+(1,4,721,1440), "
-                                   "depths 2-6-6-2, dims 192/384, random-init weights (BASELINE configs[1])",
-                       "parallelism": f"dp{world}"},
-            "model_tflops": FWD_GFLOP_EXEC / ms,
-            "model_flop_note": f"executed dense-contraction GFLOP per step {FWD_GFLOP_EXEC} (the reference's padded-shape ledger: {FWD_GFLOP})",
+        res.update({
             "roofline": {"bound": "mfma", "kernel": "gemm_tn_f32_dma_kernel (plain projection GEMMs)", "achieved": achieved,
                          "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": achieved / PEAK_F32_MFMA_TFLOPS,
                          "traffic": traffic, "traffic_stale": stale, "traffic_commit": pmc_commit,
@@ -844,7 +887,7 @@ def main():
                                        "algorithmic_flop_per_launch": attn_flop / max(attn_launches, 1),
                                        "traffic": a_traffic, "traffic_stale": a_stale, "mfma_busy_frac_pmc": a_busy,
                                        "share_of_step": attn_ms / (ms_i * args.steps)}},
-        }
+        })
         if bf16_res is not None:
             res["bf16_forward"] = bf16_res
         res.update(train_res)

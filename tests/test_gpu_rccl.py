@@ -24,7 +24,7 @@ def test_bench_under_torchrun_one_rank_rccl():
     env = dict(os.environ, PANGU_DIST_FORCE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--train-steps", "1",
+           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--train-steps", "1",
            "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -61,7 +61,7 @@ def test_reduce_scatter_mode_on_a_one_rank_rccl_communicator():
         env = dict(os.environ, PANGU_DIST_FORCE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-               os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--train-steps", "2",
+               os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--full", "--train-steps", "2",
                "--no-cpu-baseline", "--no-bf16", "--no-extras", "--no-fed", "--grad-sync", mode]
         r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stderr[-3000:]

@@ -2,11 +2,11 @@
 # Everything the round commits under profiles/, regenerated on the GPU box in ONE gpurun call (every rocprofv3 pass under `timeout`,
 # counters in their own passes):   bash tools/profile_all.sh r04
 #   tools/profile_round.sh  -> forward kernel stats + PMC traffic JSONs, training kernel stats, training PMC table + pmc_train.json,
-#                              kernel micro-benchmarks, training A/B, the default bench line
+#                              kernel micro-benchmarks, training A/B, the full bench line
 #   tools/pmc_per_shape.py  -> per-shape clock / MFMA-busy of the forward kernels
 #   tools/pmc_issue_table.sh (forward bf16, training bf16, training f32) -> issuing / stalled / parked, LDS busy + conflicts, MFMA busy
 #   tools/per_step_kernels.sh (bf16, f32) -> exact per-step kernel lists of the training step
-#   1-rank RCCL run of the bench's training section (PANGU_DIST_FORCE=1)
+#   1-rank RCCL run of the bench's training section (PANGU_DIST_FORCE=1, bench.py --full -> profiles/<tag>_rccl_1rank.json)
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
@@ -21,5 +21,5 @@ bash tools/pmc_issue_table.sh train bf16 > gpurun_out/${TAG}_train_bf16_issue_ta
 bash tools/pmc_issue_table.sh train f32 > gpurun_out/${TAG}_train_f32_issue_table.md 2>> gpurun_out/${TAG}_round.log
 bash tools/per_step_kernels.sh bf16 > gpurun_out/${TAG}_train_bf16_per_step.md 2>> gpurun_out/${TAG}_round.log
 bash tools/per_step_kernels.sh f32 > gpurun_out/${TAG}_train_f32_per_step.md 2>> gpurun_out/${TAG}_round.log
-RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29531 PANGU_DIST_FORCE=1 timeout 600 python3 bench.py --no-bf16 --cpu-baseline none --steps 3 --warmup 1 > gpurun_out/${TAG}_rccl_1rank.json 2> gpurun_out/${TAG}_rccl_1rank.err
+RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29531 PANGU_DIST_FORCE=1 timeout 600 python3 bench.py --full --no-bf16 --cpu-baseline none --steps 3 --warmup 1 > profiles/${TAG}_rccl_1rank.json
 ls -la gpurun_out/${TAG}_* | head -40

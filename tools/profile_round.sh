@@ -3,7 +3,7 @@
 #   bash tools/profile_round.sh r02
 # -> gpurun_out/<tag>_*: forward kernel stats + PMC traffic JSONs (tools/pmc_traffic.sh), training-step kernel stats per dtype,
 #    the training PMC table (FETCH_SIZE | WRITE_SIZE | MFMA busy, three separate passes), the kernel micro-benchmarks and the
-#    default bench line.  Copy what is to be judged into profiles/.
+#    full bench line (bench.py --full, written to profiles/<tag>_bench.json).  Copy what else is to be judged into profiles/.
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
@@ -44,5 +44,5 @@ python3 tools/pmc_train_table.py --json gpurun_out/pmc_train.json /tmp/trpmc_f32
     for m in 0 1; do echo "PANGU_BF16_TRAIN_MLP=$m: $(PANGU_BF16_TRAIN_MLP=$m timeout 300 python3 tools/profile_train.py bf16 6 2 2>&1 | grep train)"; done
   done
 } > gpurun_out/${TAG}_train_ab.txt 2>&1
-timeout 900 python3 bench.py > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err
-tail -c 600 gpurun_out/${TAG}_bench.json
+timeout 900 python3 bench.py --full > profiles/${TAG}_bench.json
+tail -c 600 profiles/${TAG}_bench.json
