@@ -9,8 +9,8 @@ import os
 import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# PANGU_HIP_LIB: development override (tools/ A/B builds of one kernel file linked into a second library); the product loads
-# the in-tree library next to this file
+# PANGU_HIP_LIB: load another build of the library, e.g. one from another commit (an A/B is two builds from two commits); by
+# default the in-tree library next to this file
 LIB_PATH = os.environ.get("PANGU_HIP_LIB") or os.path.join(_HERE, "libpangu_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "pangu_hip.h")
 

@@ -2,26 +2,19 @@
 bf16 weight shadows / activations / activation gradients, fp32 LayerNorm + softmax + accumulation.
 
 Same kernel sequence as autograd.py on the bf16 entry points; saved activations are bf16 (32 GB instead of 64 GB)."""
-import os
-
 import torch
 
 from . import ops
 from . import ops_bf16 as ob
 
-# MLP branch of the training forward (A/B knob PANGU_BF16_TRAIN_MLP): 1 (default) = ONE launch that keeps the hidden activation on
+
+# MLP branch of the training forward (mode 1, C = 192 / 384 with contiguous rows): ONE launch that keeps the hidden activation on
 # chip and writes only what the backward needs (pre, m); the backward's data-gradient GEMM re-creates h = GELU(pre) for the W2
-# weight gradient.  0 = three launches (MLP-up + GELU writing pre AND h, MLP-down, LayerNorm + residual): what widths other than
-# 192 / 384 and row-strided inputs take anyway.  (Recomputing the MLP-up GEMM in the backward instead of saving `pre` -- the
-# reference's answer to activation memory, layers.py:115-119 -- measured +2.7 ms per step and was removed in round 4; so were the
-# QKV-inside-attention training forward, +0.3 ms, and weight gradients on a second stream, +0.5 ms.  DESIGN.md keeps the numbers.)
-_TRAIN_MLP = int(os.environ.get("PANGU_BF16_TRAIN_MLP", "1"))
-
-
-def _mlp_mode(C):
-    return 1 if (C in (192, 384) and _TRAIN_MLP != 0) else 0
-
-
+# weight gradient.  Mode 0, what other widths and row-strided inputs take: three launches (MLP-up + GELU writing pre AND h,
+# MLP-down, LayerNorm + residual), +2.3-3.1 ms per step where mode 1 applies.  (Recomputing the MLP-up GEMM in the backward
+# instead of saving `pre` -- the reference's answer to activation memory, layers.py:115-119 -- measured +2.7 ms per step and was
+# removed in round 4; so were the QKV-inside-attention training forward, +0.3 ms, and weight gradients on a second stream,
+# +0.5 ms.  DESIGN.md keeps the numbers.)
 class EarthBlockFnBF16(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, n1w, n1b, n2w, n2b, m1w, m1b, m2w, m2b, esb, a1w, a1b, a2w, a2b, geom, s1, s2, sh, dst=None):
@@ -40,7 +33,7 @@ class EarthBlockFnBF16(torch.autograd.Function):
             # (a dropped MLP branch -- s2 == 0 -- makes x1 the block's result: written straight into `out`, no copy afterwards)
             x1 = ob.ln_residual(y, x, n1w, n1b, branch_scale=s1, out=out if s2 == 0.0 else None)
             saved += [qkv, o, lse, y]
-        ctx.mlp_mode = mode = _mlp_mode(x.shape[1]) if x1.is_contiguous() else 0
+        ctx.mlp_mode = mode = 1 if (x.shape[1] in (192, 384) and x1.is_contiguous()) else 0
         if s2 != 0.0 and mode:
             x2, pre, m = ob.mlp_ln_residual_train(x1, sh.get_mlp(m1w, m2w), m1b, m2b, n2w, n2b, branch_scale=s2, out=out)
             saved += [x1, pre, m]

@@ -12,7 +12,6 @@
 // (s = acc*scale + bias).  All prologue loads are issued up front (closed-form tokens), there is one barrier, the bias row of
 // tile i+1 is prefetched under tile i, and the two heads sharing a token's 128-B line run back to back on one XCD.
 #include "common.h"
-#include <stdlib.h>
 
 #include "attn_bf16_tile.h"
 
@@ -138,20 +137,6 @@ __device__ inline int kswz64(int row, int chunk) {      // 64-byte rows, 4 chunk
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
-#ifdef PANGU_ATTN_STAMP
-// Diagnostic build only (tools/ablate_attn.py): s_memtime sums over all waves: [0] K-loop, [1] q/K/V staging + barrier,
-// [2] the three attention tiles, [3] whole kernel, [4] waves, [5] prologue up to the first K-step.
-constexpr int STAMP_WAVES = 80000;
-__device__ unsigned long long g_attn_stamp[STAMP_WAVES * 8];      // per wave: no atomics (they would dominate the timing)
-__device__ __forceinline__ unsigned long long attn_stamp() {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-#endif
-
 // win_src_token (common.h) with the window type already split into (zwin, hwin): the split is a runtime division of a
 // workgroup-uniform value that the compiler would redo on the vector ALU for each of the kernel's eight token lookups.
 __device__ inline void split_type(const WinGeom& g, int t, int& zwin, int& hwin) {
@@ -172,24 +157,17 @@ __device__ inline int win_src_token_zh(const WinGeom& g, int l, int zwin, int hw
   return h >= g.H ? -1 : (z * g.H + h) * g.W + w;
 }
 
-// Waves per SIMD the register allocator must leave room for (the second __launch_bounds__ argument).  2 = the compiler's free
-// choice (138-156 VGPRs -> three waves per SIMD, four 3-wave workgroups per CU); 4 = capped at 128 VGPRs (five workgroups per CU):
-// the round-6 A/B build (tools/ab_lib.sh, profiles/r06_attn_qkv_occ4_ab.md).
-#ifndef PANGU_ATTN_QKV_MIN_WAVES
-#define PANGU_ATTN_QKV_MIN_WAVES 2
-#endif
-
+// The second __launch_bounds__ argument (2 waves per SIMD) leaves the register count to the compiler: 138-156 VGPRs -> three waves
+// per SIMD, four 3-wave workgroups per CU.  A 128-VGPR cap (five workgroups per CU) measured level or slower
+// (profiles/r06_attn_qkv_occ4_ab.md).
 template <bool SHIFTED, int C>
-__global__ __launch_bounds__(192, PANGU_ATTN_QKV_MIN_WAVES) void window_attn_qkv_bf16_kernel(const u16* __restrict__ x, int ldx,
+__global__ __launch_bounds__(192, 2) void window_attn_qkv_bf16_kernel(const u16* __restrict__ x, int ldx,
                                                                       const u16* __restrict__ wqkv,
                                                                       const float* __restrict__ bqkv,
                                                                       const u16* __restrict__ esb, u16* __restrict__ out,
                                                                       float* __restrict__ lse, WinGeom g, int n_tok,
                                                                       int heads, int n_pairs) {
   constexpr int QK_RING = 2, BK = 32;        // ring of two 32-channel K-steps (the measured winner; see launch_attn_qkv)
-#ifdef PANGU_ATTN_STAMP
-  const unsigned long long st0 = attn_stamp();
-#endif
   constexpr int KS = C / BK;
   constexpr int CH = BK / 8;                 // 16-B chunks per slot row
   constexpr int ROWB = BK * 2;               // bytes per slot row
@@ -280,9 +258,6 @@ __global__ __launch_bounds__(192, PANGU_ATTN_QKV_MIN_WAVES) void window_attn_qkv
     for (int i = 0; i < 3; ++i) acc[rt][i] = f32x4{bv, bv, bv, bv};
   }
 
-#ifdef PANGU_ATTN_STAMP
-  const unsigned long long st1 = attn_stamp();
-#endif
   for (int ks = 0; ks < KS; ++ks) {
     wait_vmcnt<0>();                                               // step ks landed
     // every fragment read of the previous step must have RETURNED before this wave releases the barrier: behind it the
@@ -302,26 +277,6 @@ __global__ __launch_bounds__(192, PANGU_ATTN_QKV_MIN_WAVES) void window_attn_qkv
         const int row = (tile0 + i) * 16 + lq;
         fx[i] = *reinterpret_cast<const bf16x8*>(slot + row * ROWB + (((kk * 4 + lg) ^ fsw(row)) << 4));
       }
-#if PANGU_ATTN_QKV_MIN_WAVES >= 4
-      // register diet of the 128-VGPR build: the six weight fragments in three pairs instead of all at once (24 -> 8 registers)
-#pragma unroll
-      for (int rp = 0; rp < 3; ++rp) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const int row = PANGU_WTOK + (2 * rp + h) * 16 + lq;
-          fw[h] = *reinterpret_cast<const bf16x8*>(slot + row * ROWB + (((kk * 4 + lg) ^ fsw(row)) << 4));
-        }
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            const int rt = 2 * rp + h;
-            if (rt < 4) acc[rt][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[h], fx[i], acc[rt][i], 0, 0, 0);
-            else acc[rt][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fx[i], fw[h], acc[rt][i], 0, 0, 0);
-          }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#else
 #pragma unroll
       for (int rt = 0; rt < 6; ++rt) {
         const int row = PANGU_WTOK + rt * 16 + lq;
@@ -334,13 +289,9 @@ __global__ __launch_bounds__(192, PANGU_ATTN_QKV_MIN_WAVES) void window_attn_qkv
 #pragma unroll
         for (int rt = 4; rt < 6; ++rt) acc[rt][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fx[i], fw[rt], acc[rt][i], 0, 0, 0);
       }
-#endif
     }
   }
 
-#ifdef PANGU_ATTN_STAMP
-  const unsigned long long st2 = attn_stamp();
-#endif
   // ---- q fragments (registers), K image and V^T image (LDS, over the ring: every wave must be done reading it)
   BiasRow b0 = load_bias_row(bias_tile, tile0 * 16 + lq, lg);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -375,31 +326,11 @@ __global__ __launch_bounds__(192, PANGU_ATTN_QKV_MIN_WAVES) void window_attn_qkv
       }
   }
   __syncthreads();
-#ifdef PANGU_ATTN_STAMP
-  const unsigned long long st3 = attn_stamp();
-#endif
-#if PANGU_ATTN_QKV_MIN_WAVES >= 4
-  // the 128-VGPR build: two key halves per tile, ONE bias row live (the next tile's row refills it half by half)
-  attn_tile_halves<SHIFTED, true>(Ks, Vt, qf[0], b0, bias_tile + (size_t)((tile0 + 1) * 16 + lq) * PANGU_WTOK, tile0 * 16 + lq, qtok[0],
-                                  lq, lg, zcut, hcut, kz_bits, kh_bits, out, lse, C, heads, hd);
-  attn_tile_halves<SHIFTED, true>(Ks, Vt, qf[1], b0, bias_tile + (size_t)((tile0 + 2) * 16 + lq) * PANGU_WTOK, (tile0 + 1) * 16 + lq,
-                                  qtok[1], lq, lg, zcut, hcut, kz_bits, kh_bits, out, lse, C, heads, hd);
-  attn_tile_halves<SHIFTED, true>(Ks, Vt, qf[2], b0, nullptr, (tile0 + 2) * 16 + lq, qtok[2], lq, lg, zcut, hcut, kz_bits, kh_bits, out,
-                                  lse, C, heads, hd);
-#else
   const BiasRow b1 = load_bias_row(bias_tile, (tile0 + 1) * 16 + lq, lg);
   attn_tile<SHIFTED, true>(Ks, Vt, qf[0], b0, tile0 * 16 + lq, qtok[0], lq, lg, zcut, hcut, kz_bits, kh_bits, out, lse, C, heads, hd);
   b0 = load_bias_row(bias_tile, (tile0 + 2) * 16 + lq, lg);
   attn_tile<SHIFTED, true>(Ks, Vt, qf[1], b1, (tile0 + 1) * 16 + lq, qtok[1], lq, lg, zcut, hcut, kz_bits, kh_bits, out, lse, C, heads, hd);
   attn_tile<SHIFTED, true>(Ks, Vt, qf[2], b0, (tile0 + 2) * 16 + lq, qtok[2], lq, lg, zcut, hcut, kz_bits, kh_bits, out, lse, C, heads, hd);
-#endif
-#ifdef PANGU_ATTN_STAMP
-  const unsigned long long st4 = attn_stamp();
-  if (lane == 0 && (int)(blockIdx.x * 3 + wave) < STAMP_WAVES) {
-    unsigned long long* d = g_attn_stamp + (size_t)(blockIdx.x * 3 + wave) * 8;
-    d[0] = st2 - st1; d[1] = st3 - st2; d[2] = st4 - st3; d[3] = st4 - st0; d[4] = 1ull; d[5] = st1 - st0;
-  }
-#endif
 }
 
 
@@ -461,17 +392,3 @@ extern "C" int pangu_window_attn_qkv_fwd_bf16(pangu_stream_t stream, const void*
                                               int C, int heads, int shifted) {
   return launch_attn_qkv(stream, x, ldx, w_qkv, b_qkv, esb, out, lse, Z, H, W, C, heads, shifted);
 }
-
-#ifdef PANGU_ATTN_STAMP
-extern "C" int pangu_attn_stamp_read(unsigned long long* out8) {
-  (void)hipDeviceSynchronize();
-  static unsigned long long host[STAMP_WAVES * 8];
-  (void)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_attn_stamp), sizeof(host));
-  for (int k = 0; k < 8; ++k) out8[k] = 0;
-  for (int w = 0; w < STAMP_WAVES; ++w)
-    for (int k = 0; k < 8; ++k) out8[k] += host[(size_t)w * 8 + k];
-  for (size_t i = 0; i < (size_t)STAMP_WAVES * 8; ++i) host[i] = 0;
-  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_attn_stamp), host, sizeof(host));
-  return 0;
-}
-#endif

@@ -5,7 +5,6 @@
 // kernel below computes the scores in ONE orientation (see its header comment); the round-1 kernel (both orientations, transposed
 // token-major LDS copies, 66 instead of 48 MFMAs per wave and window: 0.86 vs 0.60 ms at C = 192) was removed in round 4.
 #include "common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -19,9 +18,6 @@ constexpr int ROWIMG = PANGU_WTOK * 64;        // bytes of a row-major [144][32]
 __device__ inline u16 f2bf(float f) { return __builtin_bit_cast(u16, (__bf16)f); }
 __device__ inline unsigned pack2(float a, float b) { return pack_bf16x2(a, b); }
 
-#ifndef PANGU_ATTN_BWD_WIDE
-#define PANGU_ATTN_BWD_WIDE 1      // 16-B gradient stores after a v_permlane16_swap exchange (0: two 8-B stores per row and lane)
-#endif
 // x0 / x1: this lane's four values of d = 4lg.. / 16 + 4lg.. of one token -> the 16-B piece d = {0, 16, 8, 24}[lg] .. +7 of that token
 // (all 64 lanes must be active: the swap exchanges whole 16-lane rows)
 __device__ inline u32x4 wide16(const f32x4 x0, const f32x4 x1) {
@@ -78,32 +74,11 @@ __device__ inline unsigned opaque(unsigned v) {
   return v;
 }
 
-#ifdef PANGU_ATTN_BWD_STAMP
-// Diagnostic build only (tools/ablate_attn_bwd.py): per-wave s_memtime sums: [0] staging (loop top .. second barrier),
-// [1] phase 1, [2] wait at the dS barrier, [3] phase 2, [4] whole kernel, [5] waves, [6] prologue
-constexpr int STAMP_WAVES = 9 * 1024;
-__device__ unsigned long long g_bwd_stamp[STAMP_WAVES * 8];
-__device__ __forceinline__ unsigned long long bwd_stamp() {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-#define BWD_STAMP(v) const unsigned long long v = bwd_stamp()
-#else
-#define BWD_STAMP(v)
-#endif
-
 template <bool SHIFTED>
 __global__ __launch_bounds__(NT) void window_attn_bwd2_bf16_kernel(
     const u16* __restrict__ qkv, const u16* __restrict__ qkv_bias, const u16* __restrict__ esb,
     const u16* __restrict__ out, const float* __restrict__ lse, const u16* __restrict__ dout, u16* __restrict__ dqkv,
     float* __restrict__ dqkv_bias, float* __restrict__ d_esb, WinGeom g, int C, int heads) {
-  BWD_STAMP(st_begin);
-#ifdef PANGU_ATTN_BWD_STAMP
-  unsigned long long acc_st[4] = {0ull, 0ull, 0ull, 0ull};
-#endif
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const unsigned L0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;
 
@@ -230,14 +205,11 @@ __global__ __launch_bounds__(NT) void window_attn_bwd2_bf16_kernel(
     }
   };
   request(0);
-  BWD_STAMP(st_loop);
   stage();
 
   for (int l = 0; l < g.nLon; ++l) {
-    BWD_STAMP(s0);
     __syncthreads();                              // window l is staged
     request(l + 1 < g.nLon ? l + 1 : l);          // in flight during the two compute phases (the last one is redundant)
-    BWD_STAMP(s1);
 
     // =========================== phase 1: key tile `wave`; S[query][key], key on the lane ===========================
     {
@@ -294,7 +266,6 @@ __global__ __launch_bounds__(NT) void window_attn_bwd2_bf16_kernel(
       // lane: dK^T / dV^T [d = 16dt + 4lg + r][key kn]
       const int ktok = *ldsp<int>(L0 + L_ROW + 1152 + kn * 4);
       dk0 *= scale; dk1 *= scale;
-#if PANGU_ATTN_BWD_WIDE
       {
         // the token's 64-B head row sits in the wave as 8-B pieces over the four 16-lane rows (x0: d = 4lg.., x1: d = 16 + 4lg..):
         // v_permlane16_swap (odd rows of x0 <-> even rows of x1) leaves EIGHT consecutive d per lane -- rows 0..3: d = 0, 16, 8, 24
@@ -305,15 +276,6 @@ __global__ __launch_bounds__(NT) void window_attn_bwd2_bf16_kernel(
         __builtin_amdgcn_raw_buffer_store_b128(wide16(dv0, dv1), dq_rsrc, (int)dst, 4 * C, 0);
         asm volatile("s_nop 1" ::: "memory");
       }
-#else
-      {
-        const unsigned dst = ktok >= 0 ? ((unsigned)ktok * (unsigned)C3 + (unsigned)(hd * 32 + lg * 4)) * 2u : OOB;
-        __builtin_amdgcn_raw_buffer_store_b64(u32x2{pack2(dk0[0], dk0[1]), pack2(dk0[2], dk0[3])}, dq_rsrc, (int)dst, 2 * C, 0);
-        __builtin_amdgcn_raw_buffer_store_b64(u32x2{pack2(dk1[0], dk1[1]), pack2(dk1[2], dk1[3])}, dq_rsrc, (int)dst, 2 * C + 32, 0);
-        __builtin_amdgcn_raw_buffer_store_b64(u32x2{pack2(dv0[0], dv0[1]), pack2(dv0[2], dv0[3])}, dq_rsrc, (int)dst, 4 * C, 0);
-        __builtin_amdgcn_raw_buffer_store_b64(u32x2{pack2(dv1[0], dv1[1]), pack2(dv1[2], dv1[3])}, dq_rsrc, (int)dst, 4 * C + 32, 0);
-      }
-#endif
       // zero-pad keys all carry linear1.bias: their gradients are summed (lanes of a pad key, then LDS, then ONE
       // global atomic per value at the end) instead of 64 same-address global atomics per pad key and window
       if (__any(ktok < 0)) {
@@ -336,9 +298,7 @@ __global__ __launch_bounds__(NT) void window_attn_bwd2_bf16_kernel(
         }
       }
     }
-    BWD_STAMP(s2);
     __syncthreads();                              // the dS image is complete
-    BWD_STAMP(s3);
 
     // =========================== phase 2: query tile `wave`: dQ^T[d][query] += K^T[d][keys] . dS^T[keys][query] ======
     {
@@ -354,39 +314,15 @@ __global__ __launch_bounds__(NT) void window_attn_bwd2_bf16_kernel(
         dq1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k_hi, dsf, dq1, 0, 0, 0);
       }
       const int qtok = *ldsp<int>(L0 + L_ROW + 1152 + kn * 4);
-#if PANGU_ATTN_BWD_WIDE
       {                       // lane: dQ^T[d = 16dt + 4lg + r][query 16 wave + lq] -> eight consecutive d per lane, one 16-B store
         const unsigned dst = qtok >= 0 ? ((unsigned)qtok * (unsigned)C3 + (unsigned)(hd * 32 + wide_doff)) * 2u : OOB;
         dq0 *= scale; dq1 *= scale;
         __builtin_amdgcn_raw_buffer_store_b128(wide16(dq0, dq1), dq_rsrc, (int)dst, 0, 0);
       }
-#else
-      {                       // lane: dQ^T[d = 16dt + 4lg + r][query 16 wave + lq]
-        const unsigned dst = qtok >= 0 ? ((unsigned)qtok * (unsigned)C3 + (unsigned)(hd * 32 + lg * 4)) * 2u : OOB;
-        __builtin_amdgcn_raw_buffer_store_b64(u32x2{pack2(dq0[0] * scale, dq0[1] * scale), pack2(dq0[2] * scale, dq0[3] * scale)},
-                                              dq_rsrc, (int)dst, 0, 0);
-        __builtin_amdgcn_raw_buffer_store_b64(u32x2{pack2(dq1[0] * scale, dq1[1] * scale), pack2(dq1[2] * scale, dq1[3] * scale)},
-                                              dq_rsrc, (int)dst, 32, 0);
-      }
-#endif
     }
-    BWD_STAMP(s4);
     __syncthreads();                              // every wave is done with the images and dS of window l
     stage();                                      // window l + 1 (its loads were requested before phase 1)
-#ifdef PANGU_ATTN_BWD_STAMP
-    {
-      const unsigned long long s5 = bwd_stamp();
-      acc_st[0] += (s1 - s0) + (s5 - s4); acc_st[1] += s2 - s1; acc_st[2] += s3 - s2; acc_st[3] += s4 - s3;
-    }
-#endif
   }
-#ifdef PANGU_ATTN_BWD_STAMP
-  if (lane == 0 && blockIdx.x < 1024) {
-    unsigned long long* d = g_bwd_stamp + (size_t)(blockIdx.x * 9 + wave) * 8;
-    d[0] = acc_st[0]; d[1] = acc_st[1]; d[2] = acc_st[2]; d[3] = acc_st[3];
-    d[4] = bwd_stamp() - st_begin; d[5] = 1ull; d[6] = st_loop - st_begin;
-  }
-#endif
   {
     const float pv = tid < 64 ? *ldsp<float>(L0 + L_ROW + 1728 + tid * 4) : 0.f;
     if (tid < 64 && pv != 0.f) atomicAdd(dqkv_bias + (tid < 32 ? C : 2 * C) + hd * 32 + (tid & 31), pv);
@@ -402,20 +338,6 @@ __global__ __launch_bounds__(NT) void window_attn_bwd2_bf16_kernel(
 }
 
 }  // namespace
-
-#ifdef PANGU_ATTN_BWD_STAMP
-extern "C" int pangu_attn_bwd_stamp_read(unsigned long long* out8) {
-  (void)hipDeviceSynchronize();
-  static unsigned long long host[STAMP_WAVES * 8];
-  (void)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_bwd_stamp), sizeof(host));
-  for (int k = 0; k < 8; ++k) out8[k] = 0;
-  for (int w = 0; w < STAMP_WAVES; ++w)
-    for (int k = 0; k < 8; ++k) out8[k] += host[(size_t)w * 8 + k];
-  for (size_t i = 0; i < (size_t)STAMP_WAVES * 8; ++i) host[i] = 0;
-  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_bwd_stamp), host, sizeof(host));
-  return 0;
-}
-#endif
 
 extern "C" int pangu_window_attn_bwd_bf16(pangu_stream_t stream, const void* qkv, const void* qkv_bias, const void* esb,
                                           const void* out, const float* lse, const void* dout, void* dqkv,

@@ -8,7 +8,6 @@
 // row of dqkv is written exactly once.  (The round-1 kernel, which computed the scores in both orientations -- 56 instead of 40
 // MFMAs per 16x16 tile pair, 2.36 vs 1.93 ms per launch at C = 192 -- was removed in round 4; DESIGN.md keeps its measurements.)
 #include "common.h"
-#include <stdlib.h>
 #include <type_traits>
 
 namespace {
@@ -52,24 +51,6 @@ namespace v2 {
 
 constexpr int DS_LD = PANGU_WTOK;          // floats per row of the dS image (2-way conflicts on its 9 + 36 accesses per wave and window: noise)
 constexpr int A_SPLIT = 7;                 // owner: query tiles [0, 7); helper: [7, 9) of three key tiles (phase 1: 224 / 192 MFMAs; then the owners' 72 of phase 2)
-
-#ifdef PANGU_ATTN_BWD_STAMP
-// Diagnostic build only (tools/ablate_attn_bwd.py f32): per-wave s_memtime sums of the OWNER waves: [0] staging pass,
-// [1] phase 1, [2] barriers A + B, [3] dK/dV hand-over + stores, [4] request + phase 2, [5] waves, [6] wait at the top
-// barrier, [7] LDS writes of the staging pass + its closing barrier
-constexpr int STAMP_WAVES = 12 * 1024;
-__device__ unsigned long long g_bwdf_stamp[STAMP_WAVES * 8];
-__device__ __forceinline__ unsigned long long bwdf_stamp() {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-#define BWDF_STAMP(v) const unsigned long long v = bwdf_stamp()
-#else
-#define BWDF_STAMP(v)
-#endif
 
 template <bool SHIFTED, bool NTH>
 __global__ __launch_bounds__(NT) void window_attn_bwd2_f32_kernel(
@@ -130,9 +111,6 @@ __global__ __launch_bounds__(NT) void window_attn_bwd2_f32_kernel(
   }
 
   const float* bias_l = bias_tile;
-#ifdef PANGU_ATTN_BWD_STAMP
-  unsigned long long sub_st[2] = {0ull, 0ull};
-#endif
   // ---- staging pass of window l (all 768 threads): Qs (scaled), K, dO images, delta = rowsum(dO o O), lse; the V
   // fragments of this wave's NK key tiles come straight from global memory (in flight during the pass)
   // ---- staging of window l in two halves.  request(): ALL its global loads (1 152 16-B chunk slots = 144 tokens x 8
@@ -177,9 +155,7 @@ __global__ __launch_bounds__(NT) void window_attn_bwd2_f32_kernel(
   };
   auto stage = [&](int l, auto nk_tag) {
     constexpr int NK = decltype(nk_tag)::value;
-    BWDF_STAMP(u0);
     __syncthreads();                               // previous window's LDS reads (images, dS, partial sums) are done
-    BWDF_STAMP(u1);
     // the bias tile is the same for every window: stop the compiler from hoisting its loads out of the window loop
     long lz = 0;
     asm volatile("" : "+s"(lz));
@@ -210,9 +186,6 @@ __global__ __launch_bounds__(NT) void window_attn_bwd2_f32_kernel(
       }
     }
     __syncthreads();
-#ifdef PANGU_ATTN_BWD_STAMP
-    { const unsigned long long u2 = bwdf_stamp(); sub_st[0] += u1 - u0; sub_st[1] += u2 - u1; }
-#endif
   };
   // ---- one 16x16 score tile: query tile i against key tile kt (fragments k0, k1, v0, v1); lane: [query 16i + 4lg + r][key kn]
   int& lq_w = lq;
@@ -274,18 +247,13 @@ __global__ __launch_bounds__(NT) void window_attn_bwd2_f32_kernel(
     f32x4 bv;                                               // bias values of the next tile to run (window-invariant)
 #pragma unroll
     for (int r = 0; r < 4; ++r) bv[r] = bias_tile[(size_t)(lg * 4 + r) * PANGU_WTOK + wave * 16 + lq];
-#ifdef PANGU_ATTN_BWD_STAMP
-    unsigned long long acc_st[5] = {0ull, 0ull, 0ull, 0ull, 0ull};
-#endif
     const __amdgpu_buffer_rsrc_t dq_rsrc =
         __builtin_amdgcn_make_buffer_rsrc(dqkv, 0, (int)((size_t)g.Z * g.H * g.W * C3 * sizeof(float)), 0x00020000);
     f32x4 vfn[1][2];                                        // V fragment of the NEXT window (requested before phase 2)
     request(0, vfn, std::integral_constant<int, 1>{});
     for (int l = 0; l < g.nLon; ++l) {
-      BWDF_STAMP(t0);
       stage(l, std::integral_constant<int, 1>{});
       const f32x4 vfr[1][2] = {{vfn[0][0], vfn[0][1]}};
-      BWDF_STAMP(t1);
       const int kn = wave * 16 + lq;                        // this lane's key column (phase 1) / query row (phase 2)
       // =========================== phase 1: key tile `wave`, query tiles 0..6 ===========================
       const f32x4 k0 = *reinterpret_cast<const f32x4*>(&Ks[kn * KV_LD + lg * 8]);
@@ -297,10 +265,8 @@ __global__ __launch_bounds__(NT) void window_attn_bwd2_f32_kernel(
         score_tile(wave, i, wave, (i + 1) % A_SPLIT, k0, k1, vfr[0][0], vfr[0][1], SHIFTED && ((mbits >> i) & 1u), bv, db[i],
                    dv0, dv1, dk0, dk1);
       }
-      BWDF_STAMP(t2);
       __syncthreads();                             // A: the dS image is complete; the Qs / dO images are dead
       __syncthreads();                             // B: the helpers' partial sums are in LDS (they write them between A and B)
-      BWDF_STAMP(t3);
       {
         const int h = wave / 3, kk = wave - 3 * h;
         const f32x4* src = kk == 0 ? part0_s + h * 4 * 64 + lane : part12_s + ((h * 2 + kk - 1) * 4) * 64 + lane;
@@ -337,7 +303,6 @@ __global__ __launch_bounds__(NT) void window_attn_bwd2_f32_kernel(
           }
         }
       }
-          BWDF_STAMP(t4);
       request(l + 1 < g.nLon ? l + 1 : l, vfn, std::integral_constant<int, 1>{});     // the last one is redundant
       // =========================== phase 2: query tile `wave`: dQ^T[d][query] += K^T[d][key] dS^T[key][query] =========
       {
@@ -363,20 +328,7 @@ __global__ __launch_bounds__(NT) void window_attn_bwd2_f32_kernel(
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, dq0 * scale), dq_rsrc, (int)off, 0, NTH ? 2 : 0);
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, dq1 * scale), dq_rsrc, (int)off, 64, NTH ? 2 : 0);
       }
-#ifdef PANGU_ATTN_BWD_STAMP
-      {
-        const unsigned long long t5 = bwdf_stamp();
-        acc_st[0] += t1 - t0; acc_st[1] += t2 - t1; acc_st[2] += t3 - t2; acc_st[3] += t4 - t3; acc_st[4] += t5 - t4;
-      }
-#endif
     }
-#ifdef PANGU_ATTN_BWD_STAMP
-    if (lane == 0 && blockIdx.x < 1024) {
-      unsigned long long* d = g_bwdf_stamp + (size_t)(blockIdx.x * 12 + wave) * 8;
-      for (int k = 0; k < 5; ++k) d[k] = acc_st[k];
-      d[5] = 1ull; d[6] = sub_st[0]; d[7] = sub_st[1];
-    }
-#endif
     // bias gradient: lane holds sum_l dS[query = 16i + 4lg + r][key = 16 wave + lq]
 #pragma unroll
     for (int i = 0; i < A_SPLIT; ++i)
@@ -427,12 +379,6 @@ __global__ __launch_bounds__(NT) void window_attn_bwd2_f32_kernel(
       __syncthreads();                             // B
       request(l + 1 < g.nLon ? l + 1 : l, vfr, std::integral_constant<int, 3>{});     // the helpers are idle from here on
     }
-#ifdef PANGU_ATTN_BWD_STAMP
-    if (lane == 0 && blockIdx.x < 1024) {
-      unsigned long long* d = g_bwdf_stamp + (size_t)(blockIdx.x * 12 + wave) * 8;
-      for (int k = 0; k < 8; ++k) d[k] = 0ull;
-    }
-#endif
 #pragma unroll
     for (int kk = 0; kk < 3; ++kk)
 #pragma unroll
@@ -448,20 +394,6 @@ __global__ __launch_bounds__(NT) void window_attn_bwd2_f32_kernel(
 }  // namespace v2
 
 }  // namespace
-
-#ifdef PANGU_ATTN_BWD_STAMP
-extern "C" int pangu_attn_bwdf_stamp_read(unsigned long long* out8) {
-  (void)hipDeviceSynchronize();
-  static unsigned long long host[v2::STAMP_WAVES * 8];
-  (void)hipMemcpyFromSymbol(host, HIP_SYMBOL(v2::g_bwdf_stamp), sizeof(host));
-  for (int k = 0; k < 8; ++k) out8[k] = 0;
-  for (int w = 0; w < v2::STAMP_WAVES; ++w)
-    for (int k = 0; k < 8; ++k) out8[k] += host[(size_t)w * 8 + k];
-  for (size_t i = 0; i < (size_t)v2::STAMP_WAVES * 8; ++i) host[i] = 0;
-  (void)hipMemcpyToSymbol(HIP_SYMBOL(v2::g_bwdf_stamp), host, sizeof(host));
-  return 0;
-}
-#endif
 
 extern "C" int pangu_window_attn_bwd(pangu_stream_t stream, const float* qkv, const float* qkv_bias, const float* esb,
                                      const float* out, const float* lse, const float* dout, float* dqkv,

@@ -15,7 +15,6 @@
 // Workgroup order is XCD-aware: the nLon windows sharing one (type, head) bias tile (83 KB) are consecutive
 // on one XCD, so the 62 MB bias tensor streams from HBM once per block and is re-read from L2.
 #include "common.h"
-#include <stdlib.h>
 
 namespace {
 

@@ -11,7 +11,6 @@
 //   ds_read_b128 lane groups (each group holds 16 distinct rows with chunks c / c^1) and for the staging writes.
 //   Staging: global_load_dwordx4 -> registers -> ds_write_b128 one K-step ahead (double-buffered LDS).
 #include "common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -19,12 +18,6 @@ typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned short u16;
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
-#ifndef PANGU_GELU_BWD_H_PATCH
-#define PANGU_GELU_BWD_H_PATCH 1      // the GELU-backward epilogue's h output leaves through the LDS patch as whole 16-B row segments (0: 8-B
-                                      // pieces straight from the MFMA layout; measured 0.57 vs 0.67 ms at C = 192, 0.36 vs 0.41 at C = 384)
-#endif
-// GEMM_ABLATE (tools/ablate_gemm.py, timing only, LDS-DMA kernel): 1 no in-loop requests, 2 and no barrier, 3 and no fragment reads,
-// 4 everything but the epilogue, 5 = 1 without the epilogue
 constexpr int BBM = 128;
 constexpr int BBK = 64;
 
@@ -101,7 +94,7 @@ __device__ __forceinline__ void bf16_epilogue(f32x4 (&acc)[4][2 * TN], unsigned 
   }
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    [[maybe_unused]] u32x2 hp[2 * TN];                                      // PANGU_GELU_BWD_H_PATCH: h of this row group, until the patch rows are free
+    [[maybe_unused]] u32x2 hp[2 * TN];                                      // GELU_BWD_H: h of this row group, until the patch rows are free
 #pragma unroll
     for (int j = 0; j < 2 * TN; ++j) {
       const int col = wave_n0 + j * 16 + lg * 4;
@@ -115,8 +108,7 @@ __device__ __forceinline__ void bf16_epilogue(f32x4 (&acc)[4][2 * TN], unsigned 
         v[3] *= gelu_erf_grad_lp(__builtin_bit_cast(float, xp[1] & 0xFFFF0000u));
       }
       if (ACT == PANGU_ACT_GELU_BWD_H) {
-        // gelu'(x) = Phi(x) + x phi(x) and h = gelu(x) = x Phi(x) share Phi: h leaves as an 8-B piece per lane (the 4 lanes
-        // of a row make one 32-B segment), like the pre-activation of the forward epilogue
+        // gelu'(x) = Phi(x) + x phi(x) and h = gelu(x) = x Phi(x) share Phi
         const u32x2 xp = *reinterpret_cast<const u32x2*>(slot);
         const f32x4 x = {__builtin_bit_cast(float, xp[0] << 16), __builtin_bit_cast(float, xp[0] & 0xFFFF0000u),
                          __builtin_bit_cast(float, xp[1] << 16), __builtin_bit_cast(float, xp[1] & 0xFFFF0000u)};
@@ -127,12 +119,7 @@ __device__ __forceinline__ void bf16_epilogue(f32x4 (&acc)[4][2 * TN], unsigned 
           hh[c] = x[c] * phi_c;
           v[c] *= phi_c + x[c] * 0.3989422804014327f * __expf(-0.5f * x[c] * x[c]);
         }
-#if PANGU_GELU_BWD_H_PATCH
         hp[j] = u32x2{pack2(hh[0], hh[1]), pack2(hh[2], hh[3])};
-#else
-        const unsigned ho = col < N ? ((unsigned)(wave_m0 + i * 16 + lc) * (unsigned)N + (unsigned)col) * 2u : 0xFFFFFFFFu;
-        __builtin_amdgcn_raw_buffer_store_b64(u32x2{pack2(hh[0], hh[1]), pack2(hh[2], hh[3])}, h_rsrc, (int)ho, 0, 0);
-#endif
       }
       if (ACT == PANGU_ACT_ADD) {
         const u32x2 xp = *reinterpret_cast<const u32x2*>(slot);
@@ -162,8 +149,9 @@ __device__ __forceinline__ void bf16_epilogue(f32x4 (&acc)[4][2 * TN], unsigned 
         __builtin_amdgcn_raw_buffer_store_b128(v, c_rsrc, (int)off, 0, 2);
       }
     }
-#if PANGU_GELU_BWD_H_PATCH
-    if (ACT == PANGU_ACT_GELU_BWD_H) {                     // h through the same patch rows: whole 16-B row segments instead of 8-B pieces
+    // h through the same patch rows: whole 16-B row segments instead of 8-B pieces straight from the MFMA layout (measured
+    // 0.57 vs 0.67 ms at C = 192, 0.36 vs 0.41 at C = 384)
+    if (ACT == PANGU_ACT_GELU_BWD_H) {
 #pragma unroll
       for (int j = 0; j < 2 * TN; ++j)
         *reinterpret_cast<u32x2*>(ep + (i * 16 + lc) * EP_LD + (j * 16 + lg * 4) * 2) = hp[j];
@@ -179,7 +167,6 @@ __device__ __forceinline__ void bf16_epilogue(f32x4 (&acc)[4][2 * TN], unsigned 
         }
       }
     }
-#endif
   }
 }
 
@@ -352,33 +339,16 @@ __global__ __launch_bounds__(256, RING == 2 ? 3 : 2) void gemm_tn_bf16_glds_kern
     if (RING >= 4 && rem >= 2) wait_vmcnt<2 * LPS>();
     else if (RING >= 3 && rem >= 1) wait_vmcnt<LPS>();
     else wait_vmcnt<0>();
-#ifdef GEMM_ABLATE
-    if (GEMM_ABLATE < 2 || GEMM_ABLATE == 4)
-#endif
     __builtin_amdgcn_s_barrier();                          // step kt landed for every wave; slot (kt-1)%4 is free
     asm volatile("" ::: "memory");
-#ifdef GEMM_ABLATE
-    if (GEMM_ABLATE == 4)
-#endif
     if (kt + RING - 1 < KT) issue(kt + RING - 1);
     const unsigned char* As = smem + (kt % RING) * STAGE;
     const unsigned char* Ws = As + BBM * 64;
     bf16x8 fa[4], fw[2 * TN];
-#ifdef GEMM_ABLATE
-    if (GEMM_ABLATE == 3) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) asm volatile("v_mov_b32 %0, %1" : "=v"(fa[i][0]) : "v"(kt));
-#pragma unroll
-      for (int j = 0; j < 2 * TN; ++j) asm volatile("v_mov_b32 %0, %1" : "=v"(fw[j][0]) : "v"(kt));
-    } else {
-#endif
 #pragma unroll
     for (int i = 0; i < 4; ++i) fa[i] = *reinterpret_cast<const bf16x8*>(As + kswz64(wm * 64 + i * 16 + lc, lg));
 #pragma unroll
     for (int j = 0; j < 2 * TN; ++j) fw[j] = *reinterpret_cast<const bf16x8*>(Ws + kswz64(wn * 32 * TN + j * 16 + lc, lg));
-#ifdef GEMM_ABLATE
-    }
-#endif
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -386,15 +356,6 @@ __global__ __launch_bounds__(256, RING == 2 ? 3 : 2) void gemm_tn_bf16_glds_kern
         acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[j], fa[i], acc[i][j], 0, 0, 0);
   }
   __syncthreads();                                         // every wave is done with the ring before the epilogue reuses it
-#ifdef GEMM_ABLATE
-  if (GEMM_ABLATE == 4 || GEMM_ABLATE == 5) {              // timing only: no epilogue (one store keeps the accumulators alive)
-    float t = 0.f;
-    for (int i = 0; i < 4; ++i)
-      for (int j = 0; j < 2 * TN; ++j) t += acc[i][j][0] + acc[i][j][1] + acc[i][j][2] + acc[i][j][3];
-    if (t == 123.456f) reinterpret_cast<u16*>(Cv)[0] = 1;
-    return;
-  }
-#endif
   bf16_epilogue<TN, ACT, HAS_BIAS, OUT_F32>(acc, smem, bias, Cv, ldc, M, N, aux, m0, n0, wave, lane, aux2);
 }
 
@@ -407,7 +368,7 @@ int launch_bf16(hipStream_t s, const u16* A, int lda, const u16* W, const float*
   // Staging pipelines, A/B-measured on MI355X at this model's shapes (tools/bench_kernels.py gemm_bf16): the LDS-DMA ring of 2
   // runs THREE workgroups per CU (no staging registers, 53 KB of LDS) and wins 7-13 % on the K = 384 / 768 shapes; for
   // K >= 1024 the register-staged BK = 64 kernel (two workgroups per CU, half the barriers) is 4 % ahead; the ring of 4
-  // equals the register-staged kernel everywhere.  PANGU_BF16_GLDS = 0 / 1 / 2 forces register staging / ring of 4 / ring of 2.
+  // equals the register-staged kernel everywhere.
   const bool glds = K < 1024 && (K % GBK == 0);      // (a ring of 4 measured equal to register staging: removed)
   const size_t epi = OUT_F32 ? 0 : (size_t)4 * 64 * (32 * TN * 2 + 16);
   const size_t ring = (size_t)2 * (BBM + BN) * 64;
@@ -456,14 +417,13 @@ extern "C" int pangu_linear_gelu_bwd_bf16(pangu_stream_t stream, const void* A, 
   const int act = h ? PANGU_ACT_GELU_BWD_H : PANGU_ACT_GELU_BWD;
   // K <= 192: the weights-stationary kernel re-reads dm once per 192-column slice (4x at N = 768) next to the pre-activation
   // read and the dpre / h writes; measured (tools/bench_kernels.py mlp_train, MI355X) the tiled LDS-DMA kernel is 7-13 % ahead
-  // on this epilogue (0.677 vs 0.729 ms with h, 0.479 vs 0.553 without), so it is the default; PANGU_BF16_WS_GELU_BWD=1 = the
-  // weights-stationary kernel
+  // on this epilogue (0.677 vs 0.729 ms with h, 0.479 vs 0.553 without), so it is the one used here
   const u16* a = (const u16*)A;
   const u16* w = (const u16*)W;
   u16* x = (u16*)const_cast<void*>(pre);
   // with h the epilogue moves three (tokens x N) tensors per tile: 128 x 128 tiles (116 VGPRs, 37 KB of patches: four workgroups
   // per CU cover its load -> gelu' -> store chain) beat 128 x 192 (three per CU): 0.53 vs 0.57 ms at C = 192, 0.34 vs 0.36 at
-  // C = 384 (tools/bench_kernels.py mlp_train); without h the two are level.  PANGU_GELU_BWD_TN=3 / 2 forces one.
+  // C = 384 (tools/bench_kernels.py mlp_train); without h the two are level.
   const bool tn2 = h != nullptr;
   if (tn2 && N % 128 == 0) return launch_bf16<2, false>(s, a, lda, w, nullptr, dpre, ldc, M, N, K, act, x, (u16*)h);
   if ((N % 192 == 0) || (N > 128 && N < 192)) return launch_bf16<3, false>(s, a, lda, w, nullptr, dpre, ldc, M, N, K, act, x, (u16*)h);

@@ -12,19 +12,15 @@
 // Block -> tile map is XCD-aware: workgroups that share an A row-panel (the n-tiles of one m-tile) are
 // consecutive on ONE XCD, so the panel is fetched from HBM once and re-read from that XCD's L2.
 #include "common.h"
-#include <stdlib.h>
 
 namespace {
 
 constexpr int BM = 128;
 constexpr int BK = 16;
 constexpr int LDS_LD = 20;   // padded row (floats)
-#ifndef GEMM_WAVES_PER_SIMD
-#define GEMM_WAVES_PER_SIMD 3
-#endif
 
 template <int TN, int ACT, bool HAS_BIAS>
-__global__ __launch_bounds__(256, TN <= 2 ? 4 : GEMM_WAVES_PER_SIMD) void gemm_tn_f32_kernel(const float* __restrict__ A, int lda,
+__global__ __launch_bounds__(256, TN <= 2 ? 4 : 3) void gemm_tn_f32_kernel(const float* __restrict__ A, int lda,
                                                              const float* __restrict__ W,
                                                              const float* __restrict__ bias,
                                                              float* __restrict__ C, int ldc, int M, int N, int K,

@@ -7,7 +7,6 @@
 // SOURCE side (conflict-free ds_read_b128 lane groups), the fragments of the two k-halves share registers, and a ring of
 // two 20-KB stages leaves 40 KB per workgroup: FOUR workgroups per CU at <= 128 VGPRs.
 #include "common.h"
-#include <stdlib.h>
 
 namespace {
 

@@ -17,18 +17,6 @@ typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned short u16;
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
-// Which widths take the persistent LDS-DMA kernel below (bit 0: N = 384 and N = 192 with K >= 384, bit 1: N = 192 always); 0 = the
-// register-staged kernel for everything (tools/ab_lib.sh builds the A/B libraries).
-#ifndef PANGU_GEMM_LN_DMA
-#define PANGU_GEMM_LN_DMA 1
-#endif
-#ifndef PANGU_GEMM_LN_RING
-// N = 384: ring of the persistent kernel.  2 (default since the second A/B of round 6): TWO slots of 64-channel K-steps (128 KB) --
-// half the barriers and the second half-step's fragment reads overlap the first's MFMAs: -6...-9 % against 3 / 4 = three / four slots
-// of 32-channel K-steps (96 / 128 KB; level with each other).  profiles/r06_gemm_ln_bf16_ab.md
-#define PANGU_GEMM_LN_RING 2
-#endif
-
 constexpr int LBM = 128;
 constexpr int LBK = 64;
 constexpr float LN_EPS = 1e-5f;
@@ -230,7 +218,7 @@ __global__ __launch_bounds__(64 * WM * WNW, 2) void gemm_ln_residual_bf16_dma_ke
     const u16* __restrict__ A, int lda, const u16* __restrict__ W, const float* __restrict__ bias,
     const u16* __restrict__ shortcut, const float* __restrict__ gamma, const float* __restrict__ beta, u16* __restrict__ out,
     int ldo, int M, int K, int m_tiles) {
-  static_assert((DBK == 32 && (RING == 3 || RING == 4)) || (DBK == 64 && RING == 2), "ring of three or four K-steps of 32, or two of 64");
+  static_assert((DBK == 32 && RING == 3) || (DBK == 64 && RING == 2), "ring of three K-steps of 32, or two of 64");
   constexpr int ROWB = DBK * 2;                            // bytes per ring row
   constexpr int RPI = 1024 / ROWB;                         // ring rows per LDS-DMA instruction (1 KB)
   constexpr int CH = DBK / 8;                              // 16-B chunks per ring row
@@ -496,10 +484,9 @@ extern "C" int pangu_linear_ln_residual_fwd_bf16(pangu_stream_t stream, const vo
   if (N != 192 && N != 384) return PANGU_E_SHAPE;          // the tile must span the whole row
   hipStream_t s = (hipStream_t)stream;
   // the persistent LDS-DMA kernel: K a multiple of 32 and at least three K-steps, dense A rows addressable through the scalar offset
-  // N = 384: always (bit 0).  N = 192: the 256-row-tile form where the K-loop is long enough to pay (K >= 384: -7 % at K = 768; at
-  // K = 192 -- the forward's launch -- it measured level with the register-staged kernel, which then stays); bit 1 forces it.
-  const bool dma = PANGU_GEMM_LN_DMA && K % 32 == 0 && K >= 96 && pangu_fits_u32(M, lda, 2) &&
-                   (N == 384 ? (PANGU_GEMM_LN_DMA & 1) : ((PANGU_GEMM_LN_DMA & 2) || K >= 384));
+  // N = 384: always.  N = 192: the 256-row-tile form where the K-loop is long enough to pay (K >= 384: -7 % at K = 768; at
+  // K = 192 -- the forward's launch -- it measured level with the register-staged kernel, which then stays).
+  const bool dma = K % 32 == 0 && K >= 96 && pangu_fits_u32(M, lda, 2) && (N == 384 || K >= 384);
   if (N == 192) {
     if (dma && K % 64 == 0 && K >= 192)      // 256 x 192 tiles, one 8-wave workgroup per CU, K-steps of 64, ring of two
       return launch_ln_dma<2, 2, 64, 4>(s, (const u16*)A, lda, (const u16*)W, bias, (const u16*)shortcut, gamma, beta, (u16*)out, ldo, M, K);
@@ -507,11 +494,11 @@ extern "C" int pangu_linear_ln_residual_fwd_bf16(pangu_stream_t stream, const vo
     return launch_ln<2>(s, (const u16*)A, lda, (const u16*)W, bias, (const u16*)shortcut, gamma, beta, (u16*)out, ldo, M, K);
   }
   if (dma) {
-    // ring of four (three K-steps in flight: 96 KB per CU) where the K-loop is long enough for its wait pattern, three otherwise
-    if (PANGU_GEMM_LN_RING == 2 && K % 64 == 0 && K >= 192)      // K-steps of 64, ring of two (A/B build)
+    // TWO ring slots of 64-channel K-steps (128 KB): half the barriers, and the second half-step's fragment reads overlap the first's
+    // MFMAs -- -6..-9 % against three or four slots of 32-channel K-steps (96 / 128 KB; level with each other),
+    // profiles/r06_gemm_ln_bf16_ab.md.  Three slots of 32 channels where K is not a multiple of 64.
+    if (K % 64 == 0 && K >= 192)
       return launch_ln_dma<4, 2, 64>(s, (const u16*)A, lda, (const u16*)W, bias, (const u16*)shortcut, gamma, beta, (u16*)out, ldo, M, K);
-    if (PANGU_GEMM_LN_RING == 4 && K >= 160)
-      return launch_ln_dma<4, 4>(s, (const u16*)A, lda, (const u16*)W, bias, (const u16*)shortcut, gamma, beta, (u16*)out, ldo, M, K);
     return launch_ln_dma<4, 3>(s, (const u16*)A, lda, (const u16*)W, bias, (const u16*)shortcut, gamma, beta, (u16*)out, ldo, M, K);
   }
   return launch_ln<4>(s, (const u16*)A, lda, (const u16*)W, bias, (const u16*)shortcut, gamma, beta, (u16*)out, ldo, M, K);

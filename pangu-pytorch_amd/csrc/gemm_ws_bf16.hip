@@ -13,7 +13,6 @@
 //   * v_mfma_f32_16x16x32_bf16 with swapped operands, so a lane owns 4 consecutive output columns: float4 bias / GELU,
 //     8-byte packed bf16, then a 16-row LDS patch turns them into whole 16-B row segments for the stores.
 #include "common.h"
-#include <stdlib.h>
 
 namespace {
 

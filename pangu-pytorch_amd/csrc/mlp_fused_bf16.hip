@@ -39,7 +39,6 @@
 //             8q..8q+7 of that row with q = p ^ f(hr), f = hr & 15 (C = 384) / (hr >> 1) & 7 (C = 192)   (bank swizzle)
 //   W2 chunk: [s = 0,1][h = 0,1][row c = 0..C-1][8 elements j]: W2[c][32ch + 16s + 8(j>>2) + 4h + (j&3)]
 #include "common.h"
-#include <stdlib.h>
 #include <type_traits>
 
 namespace {
@@ -50,36 +49,9 @@ typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr float LN_EPS = 1e-5f;
 
-// Development knobs (tools/ablate_mlp.py builds timing variants with -D...; the product uses the defaults).
-#ifndef PANGU_MLP_ABLATE
-#define PANGU_MLP_ABLATE 0      // timing only: 1 no in-loop weight requests, 2 no GELU, 4 / 8 no first / second product
-#endif
-#ifndef PANGU_MLP_PD1
-#define PANGU_MLP_PD1 3         // fragment-read distance (k-steps ahead of the MFMAs), first product
-#endif
-#ifndef PANGU_MLP_PD2
-#define PANGU_MLP_PD2 4         // the same (row tiles ahead), second product
-#endif
-#ifndef PANGU_MLP_IGLP
-#define PANGU_MLP_IGLP 4        // VALU instructions placed behind each MFMA of a step (0 = leave it to the scheduler)
-#endif
-#ifndef PANGU_MLP_NT_X
-#define PANGU_MLP_NT_X 0        // cache-policy bits of the once-read activation loads (2 = nt: keep the weight image in L2): A/B in profiles/r03 notes
-#endif
-#ifndef PANGU_MLP_NT_OUT
-#define PANGU_MLP_NT_OUT 0      // ... of the result / side-output stores
-#endif
-#ifndef PANGU_MLP_NT_SIDE
-#define PANGU_MLP_NT_SIDE 0     // ... of the training side outputs (pre, m)
-#endif
-#ifndef PANGU_MLP_PRE_VARIANT
-#define PANGU_MLP_PRE_VARIANT 0 // training variant, how the pre-activation leaves: 0 = 16-B pieces via v_permlane32_swap, 1 = the same with s_nop padding (hazard probe), 2 = 8-B pieces, no exchange
-#endif
-#ifndef PANGU_MLP_PRE_AT_TOP
-#define PANGU_MLP_PRE_AT_TOP 0  // training variant: pre-activation stores at the very top of an iteration instead of under the first fragment reads
-#endif
-constexpr int ABL = PANGU_MLP_ABLATE;
-constexpr int PD1 = PANGU_MLP_PD1, PD2 = PANGU_MLP_PD2, IGLP = PANGU_MLP_IGLP;
+constexpr int PD1 = 3;          // fragment-read distance (k-steps ahead of the MFMAs), first product
+constexpr int PD2 = 4;          // the same (row tiles ahead), second product
+constexpr int IGLP = 4;         // VALU instructions placed behind each MFMA of a step (0 = leave it to the scheduler)
 
 __device__ inline float bflo(unsigned u) { return __builtin_bit_cast(float, u << 16); }
 __device__ inline float bfhi(unsigned u) { return __builtin_bit_cast(float, u & 0xFFFF0000u); }
@@ -97,20 +69,6 @@ __device__ __forceinline__ float gelu1(float x) {
   const float e = __builtin_amdgcn_exp2f(x * w);                    // exp(-x (c0 + c1 x^2)); +inf for x << 0 -> result 0
   return x * __builtin_amdgcn_rcpf(1.0f + e);
 }
-
-#ifdef PANGU_MLP_STAMP
-// Diagnostic build only (tools/ablate_mlp.py): where a steady-state iteration spends its cycles.  Sums over all waves of
-// s_memtime differences: [0] sync (wait + barrier), [1] second product phase, [2] first product phase, [3] iterations,
-// [4] whole kernel per wave, [5] waves.
-__device__ unsigned long long g_stamp[8];
-__device__ __forceinline__ unsigned long long stamp() {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-#endif
 
 template <bool B>
 using Flag = std::integral_constant<bool, B>;
@@ -159,6 +117,8 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void mlp_ln_residual_bf16_kernel(
       const_cast<u16*>(Wimg), 0, 2 * NCH * WB, 0x00020000);
 
   // ---- activations of this wave: fragment (ks, tt) = x[m0 + 32tt + lr][16ks + 8lh .. +7]  (rows >= M read as zeros)
+  // (every load and store here uses cache policy 0: nt hints on the activations, results or side outputs measured level or
+  // slower, docs/history/r03.md)
   bf16x8 xf[KS][T];
 #pragma unroll
   for (int tt = 0; tt < T; ++tt) {
@@ -166,7 +126,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void mlp_ln_residual_bf16_kernel(
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks)
       xf[ks][tt] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(
-                                                  x_rsrc, (int)((row * (unsigned)ldx + 16 * ks + 8 * lh) * 2u), 0, PANGU_MLP_NT_X));
+                                                  x_rsrc, (int)((row * (unsigned)ldx + 16 * ks + 8 * lh) * 2u), 0, 0));
   }
   // ---- b1 and the epilogue's per-channel vectors -> LDS (fp32): as global loads in the epilogue (144 per lane, each
   // waited for at its use) they cost a quarter of the kernel
@@ -185,10 +145,6 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void mlp_ln_residual_bf16_kernel(
     __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, dst, 16, lane * 16, (st * NCH + ch) * WB + q * 1024, 0, 0);
   };
 
-#ifdef PANGU_MLP_STAMP
-  unsigned long long st_sync = 0, st_b = 0, st_all = 0, st_n = 0, st_last = 0;
-  const unsigned long long st_begin = stamp();
-#endif
   // second-product accumulators start from b2 of the lane's channels 32rt + (i&3) + 8(i>>2) + 4lh (no bias pass in the epilogue)
   f32x16 yacc[RT][T];
 #pragma unroll
@@ -214,7 +170,6 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void mlp_ln_residual_bf16_kernel(
       Pre, 0, TR == 2 ? (int)(((size_t)(M - 1) * ldp + HID) * sizeof(u16)) : 0, 0x00020000);
   // one address register for all T tiles (tile tt adds a scalar offset); rows past M are dropped by the range check
   const unsigned pre_off = ((unsigned)(m0 + lr) * (unsigned)ldp + 8 * lh) * 2u;
-  [[maybe_unused]] const unsigned pre_off8 = ((unsigned)(m0 + lr) * (unsigned)ldp + 4 * lh) * 2u;      // (8-B pieces: PANGU_MLP_PRE_VARIANT 2)
   const int pre_tile = __builtin_amdgcn_readfirstlane(32 * ldp * 2);
   auto store_pre = [&](int chunk) {
     if (TR != 2) return;
@@ -225,28 +180,16 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void mlp_ln_residual_bf16_kernel(
         // quads 2qp, 2qp+1 only: four packed registers live at a time (the kernel sits at the 512-register limit)
         unsigned a0 = pack_bf16x2(hg[tt][8 * qp], hg[tt][8 * qp + 1]), a1 = pack_bf16x2(hg[tt][8 * qp + 2], hg[tt][8 * qp + 3]);
         unsigned b0 = pack_bf16x2(hg[tt][8 * qp + 4], hg[tt][8 * qp + 5]), b1 = pack_bf16x2(hg[tt][8 * qp + 6], hg[tt][8 * qp + 7]);
-#if PANGU_MLP_PRE_VARIANT == 2
-        // no cross-lane exchange: each lane stores its own two 8-B pieces (hidden 8q + 4h .. +3 of quads 2qp, 2qp+1)
-        __builtin_amdgcn_raw_buffer_store_b64(u32x2{a0, a1}, p_rsrc, (int)pre_off8, tt * pre_tile + (chunk * 32 + 16 * qp) * 2, 0);
-        __builtin_amdgcn_raw_buffer_store_b64(u32x2{b0, b1}, p_rsrc, (int)pre_off8, tt * pre_tile + (chunk * 32 + 16 * qp + 8) * 2, 0);
-#else
-#if PANGU_MLP_PRE_VARIANT == 1
-        asm volatile("s_nop 7" : "+v"(a0), "+v"(a1), "+v"(b0), "+v"(b1));
-#endif
         const auto r0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
         const auto r1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
         u32x4 v = {r0[0], r1[0], r0[1], r1[1]};
-#if PANGU_MLP_PRE_VARIANT == 1
-        asm volatile("s_nop 7" : "+v"(v));
-#endif
-        __builtin_amdgcn_raw_buffer_store_b128(v, p_rsrc, (int)pre_off, tt * pre_tile + (chunk * 32 + 16 * qp) * 2, PANGU_MLP_NT_SIDE);
+        __builtin_amdgcn_raw_buffer_store_b128(v, p_rsrc, (int)pre_off, tt * pre_tile + (chunk * 32 + 16 * qp) * 2, 0);
         // Write-after-read hazard the compiler does not cover (ROCm 7.2, gfx950): a 16-B buffer store reads its data
         // registers over several cycles, and hipcc pads a following VALU write of those registers (s_nop) only when the
         // store's soffset is an immediate; with soffset in an SGPR (the steady-state loop here) the GELU's first
         // v_pk_mul_f32 re-used v[n:n+1] right behind the store and dword 1 of lanes 12-15 / 28-31 (+32) left with the
         // product's bits (found by the oracle test as isolated wrong elements in columns 18, 19, 26, 27 mod 32).
         asm volatile("s_nop 1" ::: "memory");
-#endif
         __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -257,7 +200,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void mlp_ln_residual_bf16_kernel(
   // drain iterations), so the steady-state body is one basic block.
   auto iteration = [&](int ch, int a /* ch % 3 */, auto g2, auto ge, auto g1, auto i1, auto i2) {
     constexpr bool G2 = decltype(g2)::value, GE = decltype(ge)::value, G1 = decltype(g1)::value;
-    constexpr bool I1 = decltype(i1)::value && !(ABL & 1), I2 = decltype(i2)::value && !(ABL & 1);
+    constexpr bool I1 = decltype(i1)::value, I2 = decltype(i2)::value;
     const int a1 = a + 1 >= NS ? a + 1 - NS : a + 1, a2 = a + 2 >= NS ? a + 2 - NS : a + 2;
     const unsigned char* w1 = ring1 + a * WB;              // W1 chunk ch
     const unsigned char* w2 = ring2 + a1 * WB;             // W2 chunk ch-2  ((ch-2) % 3 == (ch+1) % 3)
@@ -270,7 +213,6 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void mlp_ln_residual_bf16_kernel(
 #pragma unroll
       for (int n = n0; n < n1; ++n) {
         const int st = n / E, e = n % E;
-        if (ABL & 2) continue;
         float& x = hg[e >> 4][e & 15];
         float& t = gt[e];
         if (st == 0) t = x * x;
@@ -288,15 +230,6 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void mlp_ln_residual_bf16_kernel(
     auto gelu_step = [&](int g) {
       if (g > 0) gelu_ops(FRONT + (NOPS - FRONT) * (g - 1) / (NSTEPS - 1), FRONT + (NOPS - FRONT) * g / (NSTEPS - 1));
     };
-#if PANGU_MLP_PRE_AT_TOP
-    // TR: chunk ch-1's pre-activation leaves first, where the fewest registers are live (no fragments, no GELU temporaries)
-    if constexpr (GE) {
-      if (TR == 2) {
-        store_pre(ch - 1);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-#endif
     // ---- second product of chunk ch-2: 2 RT steps (row tile, k-step) of T MFMAs, fragment reads PD2 steps ahead
     if constexpr (G2) {
       constexpr int NSTEP = 2 * RT;
@@ -308,20 +241,16 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void mlp_ln_residual_bf16_kernel(
       for (int st = 0; st < PD2 && st < NSTEP; ++st) fa[st] = rd(st);
       if constexpr (GE) {
         __builtin_amdgcn_sched_barrier(0);
-        if (TR == 2 && !PANGU_MLP_PRE_AT_TOP) store_pre(ch - 1);      // chunk ch-1's pre-activation leaves under the first reads' flight
+        if (TR == 2) store_pre(ch - 1);      // chunk ch-1's pre-activation leaves under the first reads' flight
         gelu_ops(0, FRONT);                                // under the first reads' flight
       }
 #pragma unroll
       for (int st = 0; st < NSTEP; ++st) {
         if (st + PD2 < NSTEP) fa[st + PD2] = rd(st + PD2);
         __builtin_amdgcn_sched_barrier(0);
-        if (!(ABL & 8)) {
 #pragma unroll
-          for (int tt = 0; tt < T; ++tt)
-            yacc[st >> 1][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[st], hf[st & 1][tt], yacc[st >> 1][tt], 0, 0, 0);
-        } else {
-          asm volatile("" ::"v"(fa[st]), "v"(hf[0][0]));
-        }
+        for (int tt = 0; tt < T; ++tt)
+          yacc[st >> 1][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[st], hf[st & 1][tt], yacc[st >> 1][tt], 0, 0, 0);
         if constexpr (GE) gelu_step(st);
         if (I2 && st % (NSTEP / LPS) == 0) issue_piece(1, ch, a, st / (NSTEP / LPS));
         if (IGLP && GE) {
@@ -335,7 +264,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void mlp_ln_residual_bf16_kernel(
       }
     } else {
       if constexpr (GE) {
-        if (TR == 2 && !PANGU_MLP_PRE_AT_TOP) store_pre(ch - 1);
+        if (TR == 2) store_pre(ch - 1);
         gelu_ops(0, FRONT + (NOPS - FRONT) * (2 * RT - 1) / (NSTEPS - 1));
       }
       if (I2) {
@@ -343,10 +272,6 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void mlp_ln_residual_bf16_kernel(
         for (int i = 0; i < LPS; ++i) issue_piece(1, ch, a, i);
       }
     }
-#ifdef PANGU_MLP_STAMP
-    const unsigned long long t_mid = stamp();
-    if (G2 && G1) st_b += t_mid - st_last;
-#endif
     // ---- first product of chunk ch: KS steps of T MFMAs, fragment reads PD1 steps ahead; accumulators start from the
     // bias of this lane's hidden rows (i&3) + 8(i>>2) + 4lh
     if constexpr (G1) {
@@ -368,13 +293,9 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void mlp_ln_residual_bf16_kernel(
       for (int ks = 0; ks < KS; ++ks) {
         if (ks + PD1 < KS) fa[ks + PD1] = rd(ks + PD1);
         __builtin_amdgcn_sched_barrier(0);
-        if (!(ABL & 4)) {
 #pragma unroll
-          for (int tt = 0; tt < T; ++tt)
-            hacc[tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[ks], xf[ks][tt], hacc[tt], 0, 0, 0);
-        } else {
-          asm volatile("" ::"v"(fa[ks]));
-        }
+        for (int tt = 0; tt < T; ++tt)
+          hacc[tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[ks], xf[ks][tt], hacc[tt], 0, 0, 0);
         if constexpr (GE) gelu_step(2 * RT + ks);
         if (I1 && ks % (KS / LPS) == 0) issue_piece(0, ch + 2, a2, ks / (KS / LPS));
         if (IGLP && GE) {
@@ -423,27 +344,13 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void mlp_ln_residual_bf16_kernel(
 #pragma unroll
   for (int i = 0; i < LPS; ++i) issue_piece(0, 1, 1, i);
   sync(Int<LPS>{});                                       // W1 chunk 0 (and x, b1) landed; W1 chunk 1 in flight
-#ifdef PANGU_MLP_STAMP
-  const unsigned long long st_pro = stamp() - st_begin;
-#endif
   iteration(0, 0, N_{}, N_{}, Y{}, Y{}, Y{});
   sync(Int<LPW>{});
   iteration(1, 1, N_{}, Y{}, Y{}, Y{}, Y{});
   int a = 2;
   for (int ch = 2; ch < NCH - 2; ++ch) {
-#ifdef PANGU_MLP_STAMP
-    const unsigned long long t0 = stamp();
-#endif
     sync(Int<LPW>{});
-#ifdef PANGU_MLP_STAMP
-    st_last = stamp();
-    st_sync += st_last - t0;
-#endif
     iteration(ch, a, Y{}, Y{}, Y{}, Y{}, Y{});
-#ifdef PANGU_MLP_STAMP
-    st_all += stamp() - t0;
-    st_n += 1;
-#endif
     a = a + 1 == NS ? 0 : a + 1;
   }
   // ---- drain: chunks NCH-2, NCH-1 request no W1 any more; then two iterations without a first product
@@ -457,9 +364,6 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void mlp_ln_residual_bf16_kernel(
   sync(Int<0>{});
   iteration(NCH + 1, (NCH + 1) % NS, Y{}, N_{}, N_{}, N_{}, N_{});
   __syncthreads();                               // every wave is done with the rings: the patches may reuse them
-#ifdef PANGU_MLP_STAMP
-  const unsigned long long st_epi0 = stamp();
-#endif
 
   // ---- epilogue: lane holds Y^T[c = 32rt + (i&3) + 8(i>>2) + 4lh][token m0 + 32tt + lr]
   unsigned char* patch = ring1 + wave * (32 * PLD);
@@ -497,7 +401,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void mlp_ln_residual_bf16_kernel(
         const int f = lane + 64 * it, row = f / CPR, chk = f - row * CPR;
         const u32x4 v = *reinterpret_cast<const u32x4*>(patch + row * PLD + chk * 16);
         const unsigned off = tok0 + row < M ? ((unsigned)(tok0 + row) * (unsigned)ldm + chk * 8) * 2u : 0xFFFFFFFFu;
-        __builtin_amdgcn_raw_buffer_store_b128(v, m_rsrc, (int)off, 0, PANGU_MLP_NT_SIDE);
+        __builtin_amdgcn_raw_buffer_store_b128(v, m_rsrc, (int)off, 0, 0);
       }
     }
     // LayerNorm statistics: four independent partial sums (a single dependent add chain stalls the lone wave on every add)
@@ -540,18 +444,9 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void mlp_ln_residual_bf16_kernel(
       const int f = lane + 64 * it, row = f / CPR, chk = f - row * CPR;
       const u32x4 v = *reinterpret_cast<const u32x4*>(patch + row * PLD + chk * 16);
       const unsigned off = tok0 + row < M ? ((unsigned)(tok0 + row) * (unsigned)ldo + chk * 8) * 2u : 0xFFFFFFFFu;
-      __builtin_amdgcn_raw_buffer_store_b128(v, o_rsrc, (int)off, 0, PANGU_MLP_NT_OUT);
+      __builtin_amdgcn_raw_buffer_store_b128(v, o_rsrc, (int)off, 0, 0);
     }
   }
-#ifdef PANGU_MLP_STAMP
-  if (lane == 0) {
-    atomicAdd(&g_stamp[0], st_sync); atomicAdd(&g_stamp[1], st_b);
-    atomicAdd(&g_stamp[2], st_all - st_sync - st_b); atomicAdd(&g_stamp[3], st_n);
-    const unsigned long long t_end = stamp();
-    atomicAdd(&g_stamp[4], t_end - st_begin); atomicAdd(&g_stamp[5], 1ull);
-    atomicAdd(&g_stamp[6], st_pro); atomicAdd(&g_stamp[7], t_end - st_epi0);
-  }
-#endif
 }
 
 template <int C, int T, int NW, int TR = 0>
@@ -611,13 +506,3 @@ extern "C" int pangu_mlp_ln_residual_train_fwd_bf16(pangu_stream_t stream, const
 #undef PANGU_MLP_TR
   return PANGU_E_SHAPE;
 }
-
-#ifdef PANGU_MLP_STAMP
-extern "C" int pangu_mlp_stamp_read(unsigned long long* out8) {
-  hipDeviceSynchronize();
-  hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_stamp), sizeof(unsigned long long) * 8);
-  unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  hipMemcpyToSymbol(HIP_SYMBOL(g_stamp), z, sizeof(z));
-  return 0;
-}
-#endif

@@ -2,7 +2,6 @@
 // gather + LayerNorm, patch-embed gather, patch-recover scatter.  One wave per token row, float4 lanes,
 // wave-shuffle reductions; all permute/pad/crop steps of the reference are address arithmetic.
 #include "common.h"
-#include <stdlib.h>
 
 namespace {
 

@@ -1,7 +1,6 @@
 // bf16-I/O variants of the HBM-bound row kernels (fp32 statistics and arithmetic, bf16 loads/stores as 8-byte
 // quads per lane): post-norm residual, down/up-sample gather + LayerNorm, patch-embed gather.
 #include "common.h"
-#include <stdlib.h>
 
 namespace {
 

@@ -9,7 +9,6 @@
 // assignment make every transposing read conflict-free in its 32-lane half.
 // Grid = (128 x 64*TK output tiles) x (M splits); each workgroup adds its tile to dW with fp32 no-return atomics.
 #include "common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -207,7 +206,7 @@ extern "C" int pangu_linear_wgrad_bf16_ws(pangu_stream_t stream, const void* dC,
   hipStream_t s = (hipStream_t)stream;
   const u16* d = (const u16*)dC;
   const u16* a = (const u16*)A;
-  // LDS-DMA kernel for the large products (tools/bench_kernels.py wgrad_bf16, tools/ablate_wgrad.py; round 4, with a workspace):
+  // LDS-DMA kernel for the large products (tools/bench_kernels.py wgrad_bf16; round 4, with a workspace):
   // -14...-24 % at the qkv / MLP / down- and up-sampling shapes (>= 77 GFLOP) and -5 % at the C = 384 projections (38 GFLOP, N a
   // multiple of 384: one 12-wave tile column); the C = 192 projections and the patch embedding (38 GFLOP, N = 192: 4-wave tiles)
   // end in their partial tiles sooner than the extra workgroups pay (0.119 against 0.104 ms) and stay on the register-staged

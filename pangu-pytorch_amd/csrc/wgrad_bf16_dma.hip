@@ -23,29 +23,10 @@ typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned short u16;
 
-#ifdef PANGU_WGRAD_STAMP
-// Diagnostic build only (tools/ablate_wgrad.py): per-wave s_memtime sums over the K-steps: [0] own-DMA wait, [1] barrier,
-// [2] DMA issue, [3] first fragments (four dC + one A), [4] the 24 MFMAs with their A-fragment reads, [5] whole kernel, [6] steps.
-constexpr int STAMP_WAVES = 16384;
-__device__ unsigned long long g_wgrad_stamp[STAMP_WAVES * 8];
-__device__ __forceinline__ unsigned long long wg_stamp() {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-#define WG_STAMP(v) const unsigned long long v = wg_stamp()
-#define WG_ACC(k, a, b) st_sum[k] += (b) - (a)
-#else
-#define WG_STAMP(v)
-#define WG_ACC(k, a, b)
-#endif
-
 // Why the 12-wave tiles (round 4): 0.6x the staged bytes and LDS-DMA pieces per FLOP (36 KB and 36 pieces per 384 x 192 x 32
 // MACs against 20 KB and 20 pieces per 128 x 192 x 32), and a 4-slot ring keeps three slabs (108 KB) in flight where three 4-wave
 // workgroups hold one 20-KB slab each: the waves' wait for their own pieces drops from 360-560 to ~100 cycles per step.
-// In-kernel stamps (tools/ablate_wgrad.py, -DPANGU_WGRAD_STAMP), 12-wave step of ~2,150 cycles per wave: barrier 550 (skew: the
+// In-kernel stamps (a diagnostic build, round 4), 12-wave step of ~2,150 cycles per wave: barrier 550 (skew: the
 // SIMD's three waves share one MFMA pipe, 3 x 384 cycles), 3 piece requests 330, first fragments 335, MFMA loop 815.  Timing-only
 // ablations at M = 131,040, N = 1,536, K = 384 (0.164 ms as shipped then): no requests 0.145, and no barrier 0.141, and no
 // fragment reads 0.127 -- of which 0.062 is MFMA time at peak: the partial-tile stores + the reduce launch were ~0.05 ms, hence
@@ -189,24 +170,16 @@ __global__ __launch_bounds__(64 * NWN * NWK, MIN_WGS) void wgrad_bf16_dma_kernel
   for (int p = 0; p < S - 1; ++p)
     if (p < steps) issue();
   int rslot = 0;
-#ifdef PANGU_WGRAD_STAMP
-  unsigned long long st_sum[5] = {0, 0, 0, 0, 0};
-  const unsigned long long st_begin = wg_stamp();
-#endif
   for (int st = 0; st < steps; ++st) {
-    WG_STAMP(t0);
     // this wave's part of slab st has landed: the S - 2 younger slabs may still be in flight (the last steps just drain)
     if (S > 2 && st + S - 2 < steps) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER * (S - 2)) : "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    WG_STAMP(t1);
     __builtin_amdgcn_s_barrier();                          // ... and everybody's; the slot read at step st - 1 is free
     asm volatile("" ::: "memory");
-    WG_STAMP(t2);
     // Slab st + S - 1 goes to the slot read last at step st - 1.  A piece costs its wave ~100 cycles wherever it is issued
     // (stamps, round 4: here, spread between the MFMA groups, or at the end of the step all give the same step time; with 16
     // of 64 lanes active too: a per-instruction cost, not bytes), ~19 us of a 160-us launch.
     if (st + S - 1 < steps) issue();
-    WG_STAMP(t3);
     const unsigned sb = lds0 + (unsigned)(rslot * STAGE);
     rslot = rslot + 1 == S ? 0 : rslot + 1;
 #pragma unroll
@@ -231,7 +204,6 @@ __global__ __launch_bounds__(64 * NWN * NWK, MIN_WGS) void wgrad_bf16_dma_kernel
         asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(d0[i]), "+v"(d1[i]) : "n"(2 * PD));
         fd[i] = cat(d0[i], d1[i]);
       }
-      WG_STAMP(t4);
 #pragma unroll
       for (int j = 0; j < 6; ++j) {
         const int cur = j % NR, nxt = (j + PD) % NR;
@@ -255,23 +227,8 @@ __global__ __launch_bounds__(64 * NWN * NWK, MIN_WGS) void wgrad_bf16_dma_kernel
 #pragma unroll
         for (int i = 0; i < 4; ++i) dbacc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fd[i], ones, dbacc[i], 0, 0, 0);
       }
-      WG_STAMP(t5);
-      WG_ACC(0, t0, t1); WG_ACC(1, t1, t2); WG_ACC(2, t2, t3); WG_ACC(3, t3, t4); WG_ACC(4, t4, t5);
     }
   }
-#ifdef PANGU_WGRAD_STAMP
-  {
-    const unsigned long long st_end = wg_stamp();
-    const int w = blockIdx.x * NW + wave;
-    if (lane == 0 && w < STAMP_WAVES) {
-      unsigned long long* d = g_wgrad_stamp + (size_t)w * 8;
-      for (int k = 0; k < 5; ++k) d[k] += st_sum[k];
-      d[5] += st_end - st_begin;
-      d[6] += (unsigned long long)steps;
-      d[7] += 1;
-    }
-  }
-#endif
 
   // lane (lg, lc) of tile (i, j): dW[n = n0 + wn*64 + 16i + 4lg + r][k = k0 + wk*96 + 16j + lc]
   if (TWO_STAGE) {
@@ -407,20 +364,6 @@ int launch(hipStream_t s, const u16* dC, int lddc, const u16* A, int lda, float*
 }
 
 }  // namespace
-
-#ifdef PANGU_WGRAD_STAMP
-extern "C" int pangu_wgrad_stamp_read(unsigned long long* out8) {
-  (void)hipDeviceSynchronize();
-  static unsigned long long host[STAMP_WAVES * 8];
-  (void)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_wgrad_stamp), sizeof(host));
-  for (int k = 0; k < 8; ++k) out8[k] = 0;
-  for (int w = 0; w < STAMP_WAVES; ++w)
-    for (int k = 0; k < 8; ++k) out8[k] += host[(size_t)w * 8 + k];
-  for (size_t i = 0; i < (size_t)STAMP_WAVES * 8; ++i) host[i] = 0;
-  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_wgrad_stamp), host, sizeof(host));
-  return 0;
-}
-#endif
 
 // -> PANGU_OK when launched, 1 when the shape is not covered (the caller falls back to the register-staged kernel)
 int pangu_linear_wgrad_bf16_dma(hipStream_t s, const unsigned short* dC, int lddc, const unsigned short* A, int lda,

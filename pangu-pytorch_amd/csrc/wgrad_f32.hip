@@ -9,7 +9,6 @@
 // columns (conflict-free), lane half h supplying token 2s+h of k-step s.
 // All loads go through range-checked buffer descriptors (rows >= M read as 0, no divergent branches).
 #include "common.h"
-#include <stdlib.h>
 
 namespace {
 

@@ -3,8 +3,6 @@
 Token tensors are (B, N, C); B is folded into rows for projections / LayerNorm and looped for the
 geometry-dependent kernels (the reference itself is B=1 only, models/layers.py:219,227).
 """
-import os
-
 import torch
 
 from . import ops
@@ -39,8 +37,6 @@ def _tok2d(x):
         x = x.contiguous()
     return x.as_strided((B * N, C), (x.stride(1), 1), x.storage_offset())
 
-
-_FUSE_LN = os.environ.get("PANGU_F32_FUSE_LN", "1") != "0"       # A/B knob: 0 = separate GEMM + LN-residual launches
 
 def mlp(m, x2d):
     """Mlp.forward on its own (reference layers.py:264-270; the block never comes through here): differentiable."""
@@ -89,7 +85,7 @@ def earth_block(blk, x, Z, H, W, roll, out=None):
         o = torch.cat([ops.window_attention(qkv[b * N:(b + 1) * N], att.linear1.bias, esb, Z, H, W,
                                             att.head_number, roll, compact=cp) for b in range(B)], 0) if B > 1 else \
             ops.window_attention(qkv, att.linear1.bias, esb, Z, H, W, att.head_number, roll, compact=cp)
-        if _FUSE_LN and C in (192, 384):     # projection + post-norm residual in one launch (the GEMM tile spans the row)
+        if C in (192, 384):     # projection + post-norm residual in one launch (the GEMM tile spans the row)
             x1 = ops.linear_ln_residual(o, att.linear2.weight, att.linear2.bias, x2, blk.norm1.weight, blk.norm1.bias,
                                         branch_scale=s1)
         else:
@@ -101,7 +97,7 @@ def earth_block(blk, x, Z, H, W, roll, out=None):
     # of layer 0 / 3 on the autograd path; a partially frozen fine-tune (nothing upstream of this block trains) lands here
     o2 = None if out is None else (out if out.dim() == 2 else _tok2d(out))
     if s2 != 0.0:
-        if _FUSE_LN and C in (192, 384):
+        if C in (192, 384):
             h = ops.linear(x1, blk.linear.linear1.weight, blk.linear.linear1.bias, act=ops.ACT_GELU)
             x2o = ops.linear_ln_residual(h, blk.linear.linear2.weight, blk.linear.linear2.bias, x1, blk.norm2.weight,
                                          blk.norm2.bias, out=o2, branch_scale=s2)

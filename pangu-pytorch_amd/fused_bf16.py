@@ -1,7 +1,5 @@
 """bf16 inference forward of the whole model (BASELINE configs[2]/[4]): bf16 activations + bf16 weight shadows,
 fp32 LayerNorm / softmax / accumulation, fp32 output fields.  Same launch sequence as the fp32 path."""
-import os
-
 import torch
 
 from . import ops, ops_bf16 as ob
@@ -173,11 +171,6 @@ class WeightShadow:
                             mode=2, idx=lambda: ob.mlp_pack_index32(w1.shape[1], w1.device))
 
 
-_FUSE_LN = os.environ.get("PANGU_BF16_FUSE_LN", "1") != "0"      # A/B knob: 0 = separate GEMM + LN-residual launches
-_FUSE_QKV = os.environ.get("PANGU_BF16_FUSE_QKV", "1") != "0"    # A/B knob: 0 = QKV projection as its own GEMM launch
-_FUSE_MLP = os.environ.get("PANGU_BF16_FUSE_MLP", "1") != "0"    # A/B knob: 0 = MLP-up, MLP-down(+LN) as separate launches
-
-
 def _block(blk, sh, x, Z, H, W, roll, out=None):
     """x (N,C) bf16 -> (N,C) bf16.  DropPath (reference layers.py:250-251) is the identity in eval(); in train() mode under
     no_grad each branch draws its per-sample keep factor like the fp32 path (a dropped branch is not computed)."""
@@ -186,14 +179,10 @@ def _block(blk, sh, x, Z, H, W, roll, out=None):
     s1 = dp.sample_scale(blk.training) if hasattr(dp, "sample_scale") else 1.0
     s2 = dp.sample_scale(blk.training) if hasattr(dp, "sample_scale") else 1.0
     C = x.shape[1]
-    # projection + post-norm residual in one launch (the branch never round-trips HBM); C = 384: the 8-wave 128x384 tile
-    # loses what the fusion saves (measured), so stage 1/2 keeps the separate launches
-    ok = _FUSE_LN and x.is_contiguous() and s1 == 1.0 and s2 == 1.0
-    fuse = ok and C == 192
-    fuse_proj = fuse or (ok and C == 384)      # C = 384: the attention projection only (-1.2 % on the forward); MLP-down: see below
-    fuse_mlp = fuse
+    # attention projection + post-norm residual in one launch (the branch never round-trips HBM; -1.2 % on the forward at C = 384)
+    fuse_proj = x.is_contiguous() and s1 == 1.0 and s2 == 1.0 and C in (192, 384)
     if s1 != 0.0:
-        if _FUSE_QKV and C in (192, 384):
+        if C in (192, 384):
             # QKV projection inside the attention kernel: the (N, 3C) qkv tensor never reaches HBM
             o = ob.window_attention_qkv(x, sh.get(att.linear1.weight), att.linear1.bias, sh.get(att.earth_specific_bias),
                                         Z, H, W, att.head_number, roll)
@@ -213,15 +202,12 @@ def _block(blk, sh, x, Z, H, W, roll, out=None):
             out.copy_(x1)
             return out
         return x1
-    if _FUSE_MLP and C in (192, 384):
+    if C in (192, 384):
         # whole MLP branch + LayerNorm + residual in one launch: the (N, 4C) hidden activation never reaches HBM
         return ob.mlp_ln_residual(x1, sh.get_mlp(blk.linear.linear1.weight, blk.linear.linear2.weight),
                                   blk.linear.linear1.bias, blk.linear.linear2.bias, blk.norm2.weight, blk.norm2.bias,
                                   out=out, branch_scale=s2)
     h = ob.linear(x1, sh.get(blk.linear.linear1.weight), blk.linear.linear1.bias, act=ob.ACT_GELU)
-    if fuse_mlp:
-        return ob.linear_ln_residual(h, sh.get(blk.linear.linear2.weight), blk.linear.linear2.bias, x1, blk.norm2.weight,
-                                     blk.norm2.bias, out=out)
     m = ob.linear(h, sh.get(blk.linear.linear2.weight), blk.linear.linear2.bias)
     return ob.ln_residual(m, x1, blk.norm2.weight, blk.norm2.bias, out=out, branch_scale=s2)
 

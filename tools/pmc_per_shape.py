@@ -2,7 +2,7 @@
 """Per (kernel, grid size) effective clock and MFMA-busy fraction from ONE rocprofv3 --pmc pass that collected
 SQ_VALU_MFMA_BUSY_CYCLES and GRBM_GUI_ACTIVE (the `mfma` pass of tools/pmc_traffic.sh):
 
-  python tools/pmc_per_shape.py gpurun_out/pmc_<tag>_f32/mfma > profiles/<tag>_fwd_f32_per_shape.md
+  python tools/pmc_per_shape.py scratch/pmc_<tag>_f32/mfma > profiles/<tag>_fwd_f32_per_shape.md
 
 effective clock = GRBM_GUI_ACTIVE / 8 XCDs / dispatch duration (MI355X_MICROARCH.md, DVFS give-back); MFMA busy =
 SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE x 128).  Grid size separates the stage-0 launches (521 280 tokens, K = 192) from
