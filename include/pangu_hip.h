@@ -79,6 +79,20 @@ int pangu_linear_wgrad(pangu_stream_t stream, const float* dC, int lddc, const f
 int pangu_linear_wgrad_ws(pangu_stream_t stream, const float* dC, int lddc, const float* A, int lda, float* dW,
                           float* db, int M, int N, int K, float* workspace, long long workspace_bytes);
 
+/* ---- LoRA adapters (peft's lora.Linear on a frozen projection: reference finetune/lora_tune.py:124-135) --------------- */
+
+/* Adapter gradients of y = X W_eff^T + b, W_eff = W + s * B A, A [r][K], B [N][r], s = alpha / r:
+ *   dA[r][K] = s * (dY B)^T X        dB[N][r] = s * dY^T (X A^T)
+ * ONE pass over X [M][K] (row stride ldx) and dY [M][N] (row stride lddy); WRITES dA / dB (no accumulation).  Per-workgroup
+ * partials go through `workspace` (>= r*(K+N)*4 bytes, 16-B aligned; more lets more workgroups run) and one reduce launch:
+ * deterministic, no atomics.  r in {4, 8, 16, 32}; K, N multiples of 16 with K + N <= 1920; X, dY, A 16-B aligned. */
+int pangu_lora_wgrad_f32(pangu_stream_t stream, const float* dY, int lddy, const float* X, int ldx, const float* A,
+                         const float* B, float* dA, float* dB, int M, int N, int K, int r, float scaling, float* workspace,
+                         long long workspace_bytes);
+/* W_eff[N][K] = W + s * (B A), the rank sum in the fixed order 0..r-1 (dense fp32; r in {4, 8, 16, 32}); capturable. */
+int pangu_lora_merge_f32(pangu_stream_t stream, const float* W, const float* A, const float* B, float* W_eff, int N, int K,
+                         int r, float scaling);
+
 /* ---- Earth-specific window attention -------------------------------------------------------------- */
 
 /* Fused roll + window partition + (q*scale)k^T + earth_specific_bias + shift mask + softmax + .v +

@@ -160,6 +160,23 @@ class WeightShadow:
         padded = pad_k is not None and p.dim() >= 2 and p.numel() // p.shape[0] < pad_k
         return self._lookup(id(p), (p,), make, mode=None if padded else 0)
 
+    def get_lin(self, lin):
+        """bf16 shadow of a projection's weight: `get(lin.weight)` for a plain nn.Linear; for a LoraLinear the cast of its W_eff,
+        keyed by the stamps of W, A and B (made lazily, never a bulk-refresh job: those run before W_eff is current)."""
+        from .layers import LoraLinear
+        if type(lin) is not LoraLinear:
+            return self.get(lin.weight)
+        return self._lookup(("lora", id(lin)), (lin.weight, lin.lora_A, lin.lora_B),
+                            lambda: lin.effective_weight().to(torch.bfloat16).contiguous())
+
+    def get_mlp_lin(self, l1, l2):
+        """`get_mlp` of an Mlp's two projections, on W_eff where they carry adapters."""
+        from .layers import LoraLinear, eff_weight
+        if type(l1) is not LoraLinear and type(l2) is not LoraLinear:
+            return self.get_mlp(l1.weight, l2.weight)
+        params = tuple(p for l in (l1, l2) for p in ((l.weight, l.lora_A, l.lora_B) if type(l) is LoraLinear else (l.weight,)))
+        return self._lookup(("mlp-lora", id(l1), id(l2)), params, lambda: ob.pack_mlp_weights(eff_weight(l1), eff_weight(l2)))
+
     def get_t(self, p):
         """Transposed bf16 shadow (in, out): the `W` operand of the input-gradient GEMM dA = dC @ W."""
         return self._lookup(("t", id(p)), (p,),
@@ -184,16 +201,16 @@ def _block(blk, sh, x, Z, H, W, roll, out=None):
     if s1 != 0.0:
         if C in (192, 384):
             # QKV projection inside the attention kernel: the (N, 3C) qkv tensor never reaches HBM
-            o = ob.window_attention_qkv(x, sh.get(att.linear1.weight), att.linear1.bias, sh.get(att.earth_specific_bias),
+            o = ob.window_attention_qkv(x, sh.get_lin(att.linear1), att.linear1.bias, sh.get(att.earth_specific_bias),
                                         Z, H, W, att.head_number, roll)
         else:
-            qkv = ob.linear(x, sh.get(att.linear1.weight), att.linear1.bias)
+            qkv = ob.linear(x, sh.get_lin(att.linear1), att.linear1.bias)
             o = ob.window_attention(qkv, sh.get(att.linear1.bias), sh.get(att.earth_specific_bias), Z, H, W,
                                     att.head_number, roll)
         if fuse_proj:
-            x1 = ob.linear_ln_residual(o, sh.get(att.linear2.weight), att.linear2.bias, x, blk.norm1.weight, blk.norm1.bias)
+            x1 = ob.linear_ln_residual(o, sh.get_lin(att.linear2), att.linear2.bias, x, blk.norm1.weight, blk.norm1.bias)
         else:
-            y = ob.linear(o, sh.get(att.linear2.weight), att.linear2.bias)
+            y = ob.linear(o, sh.get_lin(att.linear2), att.linear2.bias)
             x1 = ob.ln_residual(y, x, blk.norm1.weight, blk.norm1.bias, branch_scale=s1)
     else:
         x1 = x
@@ -204,11 +221,11 @@ def _block(blk, sh, x, Z, H, W, roll, out=None):
         return x1
     if C in (192, 384):
         # whole MLP branch + LayerNorm + residual in one launch: the (N, 4C) hidden activation never reaches HBM
-        return ob.mlp_ln_residual(x1, sh.get_mlp(blk.linear.linear1.weight, blk.linear.linear2.weight),
+        return ob.mlp_ln_residual(x1, sh.get_mlp_lin(blk.linear.linear1, blk.linear.linear2),
                                   blk.linear.linear1.bias, blk.linear.linear2.bias, blk.norm2.weight, blk.norm2.bias,
                                   out=out, branch_scale=s2)
-    h = ob.linear(x1, sh.get(blk.linear.linear1.weight), blk.linear.linear1.bias, act=ob.ACT_GELU)
-    m = ob.linear(h, sh.get(blk.linear.linear2.weight), blk.linear.linear2.bias)
+    h = ob.linear(x1, sh.get_lin(blk.linear.linear1), blk.linear.linear1.bias, act=ob.ACT_GELU)
+    m = ob.linear(h, sh.get_lin(blk.linear.linear2), blk.linear.linear2.bias)
     return ob.ln_residual(m, x1, blk.norm2.weight, blk.norm2.bias, out=out, branch_scale=s2)
 
 
@@ -244,13 +261,13 @@ def forward(model, inp, inp_surface, statistics, maps, const_h, levels_reversed=
         cat = torch.empty((N, 2 * C), dtype=torch.bfloat16, device=dev)
         skip = _layer(model.layers[0], sh, x, 8, H4, W4, out=cat[:, :C])
         g = ob.downsample_ln(skip, model.downsample.norm.weight, model.downsample.norm.bias, 8, H4, W4)
-        x = ob.linear(g, sh.get(model.downsample.linear.weight))
+        x = ob.linear(g, sh.get_lin(model.downsample.linear))
         H2, W2 = (H4 + 1) // 2, W4 // 2
         x = _layer(model.layers[1], sh, x, 8, H2, W2)
         x = _layer(model.layers[2], sh, x, 8, H2, W2)
-        y = ob.linear(x, sh.get(model.upsample.linear1.weight))
+        y = ob.linear(x, sh.get_lin(model.upsample.linear1))
         g = ob.upsample_ln(y, model.upsample.norm.weight, model.upsample.norm.bias, 8, H2, W2, H4)
-        x = ob.linear(g, sh.get(model.upsample.linear2.weight))
+        x = ob.linear(g, sh.get_lin(model.upsample.linear2))
         _layer(model.layers[3], sh, x, 8, H4, W4, out=cat[:, C:])
         y_s = ob.linear(cat[:n_s], sh.get(rec.conv_surface.weight), rec.conv_surface.bias, out_dtype=torch.float32)
         y_u = ob.linear(cat[n_s:], sh.get(rec.conv.weight), rec.conv.bias, out_dtype=torch.float32)

@@ -51,6 +51,118 @@ class DropPath(nn.Module):
         return f"drop_prob={self.drop_prob:.3f}"
 
 
+class LoraLinear(nn.Linear):
+    """An nn.Linear with a LoRA adapter (peft's `lora.Linear`, reference finetune/lora_tune.py:124-135): y = x W_eff^T + b with
+    W_eff = W + scaling * lora_B @ lora_A, scaling = alpha / r.  `weight` / `bias` are the frozen base parameters under their own
+    names (the base state_dict keys do not change); `lora_A` (r, in) starts kaiming-uniform, `lora_B` (out, r) at zero, as peft
+    initialises them, so a fresh adapter computes exactly what the base layer computes.
+
+    The kernels never see A and B in the forward: they run on W_eff (`effective_weight()`), a derived tensor made by
+    `pangu_lora_merge_f32` and re-made only when the stamp (ops.param_stamp) of W, A or B changes -- like the bf16 weight
+    shadows, it is never pickled and is dropped by `.to()` / `invalidate_shadows`.  The adapter gradients come from
+    `pangu_lora_wgrad_f32` in the backward of the layer functions (autograd.py)."""
+
+    def __init__(self, in_features, out_features, bias=True, r=16, alpha=16, device=None, dtype=None):
+        super().__init__(in_features, out_features, bias=bias, device=device, dtype=dtype)
+        self._init_lora(r, alpha)
+
+    def _init_lora(self, r, alpha):
+        import math
+        self.r, self.lora_alpha = int(r), alpha
+        self.scaling = alpha / r
+        w = self.weight
+        self.lora_A = nn.Parameter(torch.empty((self.r, self.in_features), device=w.device, dtype=w.dtype))
+        self.lora_B = nn.Parameter(torch.zeros((self.out_features, self.r), device=w.device, dtype=w.dtype))
+        nn.init.kaiming_uniform_(self.lora_A, a=math.sqrt(5))
+        self._w_eff = None
+        self._w_eff_stamp = None
+
+    @classmethod
+    def from_linear(cls, lin, r, alpha):
+        """Adapt `lin` in place of it: the new module holds the SAME weight / bias Parameter objects."""
+        m = cls.__new__(cls)
+        nn.Module.__init__(m)
+        m.in_features, m.out_features = lin.in_features, lin.out_features
+        m.weight = lin.weight
+        m.bias = lin.bias
+        m._init_lora(r, alpha)
+        return m
+
+    def to_linear(self, weight=None):
+        """A plain nn.Linear holding this module's base Parameters (merge_lora folds W_eff into `weight` first)."""
+        lin = nn.Linear.__new__(nn.Linear)
+        nn.Module.__init__(lin)
+        lin.in_features, lin.out_features = self.in_features, self.out_features
+        lin.weight = self.weight
+        lin.bias = self.bias
+        return lin
+
+    def _stamp(self):
+        from . import ops
+        return (ops.param_stamp(self.weight), ops.param_stamp(self.lora_A), ops.param_stamp(self.lora_B), self.scaling)
+
+    def effective_weight(self):
+        """W_eff = W + scaling * B @ A (no autograd edge; fp32): the HIP kernel's result on a HIP device (fresh tensor per refresh,
+        so a backward still holding the previous one is unaffected), plain torch on the CPU."""
+        stamp = self._stamp()
+        if self._w_eff is not None and self._w_eff_stamp == stamp:
+            return self._w_eff
+        with torch.no_grad():
+            if self.weight.is_cuda:
+                from . import ops
+                with torch.cuda.device(self.weight.device):
+                    w = ops.lora_merge(self.weight.detach(), self.lora_A.detach(), self.lora_B.detach(), self.scaling)
+            else:
+                w = self.weight.detach() + self.scaling * (self.lora_B.detach() @ self.lora_A.detach())
+        self._w_eff, self._w_eff_stamp = w, stamp
+        return w
+
+    def drop_derived(self):
+        self._w_eff = None
+        self._w_eff_stamp = None
+
+    def forward(self, x):
+        """The module on its own, plain torch (peft's arithmetic; usable on the CPU)."""
+        return nn.functional.linear(x, self.weight, self.bias) + self.scaling * nn.functional.linear(
+            nn.functional.linear(x, self.lora_A), self.lora_B)
+
+    def _apply(self, fn, *args, **kwargs):
+        self.drop_derived()
+        return super()._apply(fn, *args, **kwargs)
+
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state["_w_eff"] = None
+        state["_w_eff_stamp"] = None
+        return state
+
+    def extra_repr(self):
+        return super().extra_repr() + f", r={self.r}, alpha={self.lora_alpha}"
+
+
+def _lora_args(loras):
+    """Trailing arguments of a layer Function's LoRA form: (scalings tuple, A1, B1, A2, B2, ..) with None for plain linears."""
+    out = [tuple(l[0] if l else None for l in loras)]
+    for l in loras:
+        out += [l[1], l[2]] if l else [None, None]
+    return tuple(out)
+
+
+def eff_weight(lin):
+    """THE accessor of every kernel call site for a projection's weight: `lin.weight` of a plain nn.Linear (the same tensor as
+    before adapters existed), W_eff of a LoraLinear."""
+    if type(lin) is LoraLinear:
+        return lin.effective_weight()
+    return lin.weight
+
+
+def lora_of(lin):
+    """(scaling, lora_A, lora_B) of a LoraLinear, None for a plain nn.Linear."""
+    if type(lin) is LoraLinear:
+        return (lin.scaling, lin.lora_A, lin.lora_B)
+    return None
+
+
 _ALLOWED_MODULE_TYPES = set()      # filled on first use (assert_plain_tree)
 
 
@@ -62,7 +174,7 @@ def assert_plain_tree(root, what):
     `root` must be one of this file's classes or the plain torch.nn class, without forward hooks (hooks on `root` itself run)."""
     allowed = _ALLOWED_MODULE_TYPES
     if not allowed:
-        allowed.update({nn.Linear, nn.Conv1d, nn.LayerNorm, nn.GELU, nn.Dropout, nn.Identity, nn.Sequential, DropPath,
+        allowed.update({nn.Linear, LoraLinear, nn.Conv1d, nn.LayerNorm, nn.GELU, nn.Dropout, nn.Identity, nn.Sequential, DropPath,
                         PatchEmbedding_pretrain, Mlp, EarthAttention3D, EarthSpecificBlock, EarthSpecificLayer, DownSample, UpSample,
                         PatchRecovery_pretrain})
     for m in root.modules():
@@ -77,7 +189,8 @@ def assert_plain_tree(root, what):
                            "never called (the HIP kernels read the parameters directly): the hook would be ignored")
     raise RuntimeError(f"{what} (MI355X build): sub-module '{name}' is {type(m).__module__}.{type(m).__name__}, not the plain "
                        "module the kernels read their parameters from; a wrapper's own arithmetic (LoRA adapters, "
-                       "parametrizations) would be bypassed and e.g. train nothing")
+                       "parametrizations) would be bypassed and e.g. train nothing; for LoRA use the native adapters, "
+                       "PanguModel.enable_lora()")
 
 
 class PatchEmbedding_pretrain(nn.Module):
@@ -155,12 +268,15 @@ class EarthAttention3D(nn.Module):
         m = None if mask is None else mask.detach().to(device=x.device, dtype=torch.float32).contiguous()
         with torch.cuda.device(x.device):
             if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-                y = AttentionWindowsFn.apply(xw, self.linear1.weight, self.linear1.bias, self.linear2.weight, self.linear2.bias,
-                                             self.earth_specific_bias, m, (n_lon, self.type_of_windows, self.head_number))
+                lora = (lora_of(self.linear1), lora_of(self.linear2))
+                y = AttentionWindowsFn.apply(xw, eff_weight(self.linear1), self.linear1.bias, eff_weight(self.linear2),
+                                             self.linear2.bias, self.earth_specific_bias, m,
+                                             (n_lon, self.type_of_windows, self.head_number),
+                                             *(_lora_args(lora) if any(lora) else ()))
             else:
-                qkv = ops.linear(xw, self.linear1.weight, self.linear1.bias)
+                qkv = ops.linear(xw, eff_weight(self.linear1), self.linear1.bias)
                 o = ops.attention_windows(qkv, self.earth_specific_bias[0], m, n_lon, self.type_of_windows, self.head_number)
-                y = ops.linear(o, self.linear2.weight, self.linear2.bias)
+                y = ops.linear(o, eff_weight(self.linear2), self.linear2.bias)
         return y.view(x.shape)
 
     def _construct_index(self):

@@ -433,6 +433,44 @@ def linear_wgrad(dc, a, want_bias=True, db_into=None):
     return dw, db
 
 
+LORA_RANKS = (4, 8, 16, 32)
+
+
+def lora_wgrad(dy, x, A, B, scaling):
+    """Adapter gradients of y = x @ (W + s B A)^T + b: (dA (r, K), dB (N, r)) = (s (dy B)^T x, s dy^T (x A^T)), one pass over the
+    row-strided x (M, K) and dy (M, N), deterministic (per-workgroup partials through the stream's weight-gradient workspace)."""
+    lib = _lib.load()
+    dp, lddy = _rows(dy, "lora_wgrad.dy")
+    xp, ldx = _rows(x, "lora_wgrad.x")
+    M, N = dy.shape
+    K = x.shape[1]
+    r = A.shape[0]
+    if x.shape[0] != M or tuple(A.shape) != (r, K) or tuple(B.shape) != (N, r):
+        raise RuntimeError(f"lora_wgrad: dy {tuple(dy.shape)} x {tuple(x.shape)} A {tuple(A.shape)} B {tuple(B.shape)}")
+    ws = wgrad_workspace(dy.device)
+    dA = torch.empty((r, K), dtype=torch.float32, device=dy.device)
+    dB = torch.empty((N, r), dtype=torch.float32, device=dy.device)
+    with _timed("lora_wgrad", 4.0 * M * (K + N)):          # bytes: the pass is HBM-bound (DESIGN.md, LoRA section)
+        _lib.check(lib.pangu_lora_wgrad_f32(_stream(dy), dp, lddy, xp, ldx, _chk(A, "lora_A"), _chk(B, "lora_B"), dA.data_ptr(),
+                                            dB.data_ptr(), M, N, K, r, float(scaling), ws.data_ptr(), _WGRAD_WS_BYTES), "lora_wgrad")
+    return dA, dB
+
+
+def lora_merge(W, A, B, scaling, out=None):
+    """W_eff = W + s * (B @ A) in fp32 (rank sum in a fixed order) -> a new (N, K) tensor, or into `out`."""
+    lib = _lib.load()
+    W2 = W.reshape(W.shape[0], -1)
+    N, K = W2.shape
+    r = A.shape[0]
+    if tuple(A.shape) != (r, K) or tuple(B.shape) != (N, r):
+        raise RuntimeError(f"lora_merge: W {tuple(W.shape)} A {tuple(A.shape)} B {tuple(B.shape)}")
+    if out is None:
+        out = torch.empty((N, K), dtype=torch.float32, device=W.device)
+    _lib.check(lib.pangu_lora_merge_f32(_stream(W), _chk(W2, "weight"), _chk(A, "lora_A"), _chk(B, "lora_B"), _chk(out, "W_eff"),
+                                        N, K, r, float(scaling)), "lora_merge")
+    return out
+
+
 def window_attention(qkv, qkv_bias, esb, Z, H, W, heads, shifted, want_lse=False, compact=False):
     """esb: the expanded (types, heads, 144, 144) table, or with compact=True the paper's compact table laid out
     (types, heads, 3312) (weights.compact_bias_table): same result bit for bit, 6.3x fewer bias bytes."""

@@ -109,6 +109,8 @@ class PanguModel(nn.Module):
         for m in self.modules():              # compact bias tables are derived from the parameters too
             if hasattr(m, "_esb_compact"):
                 m._esb_compact = None
+            if hasattr(m, "drop_derived"):    # ... and the LoRA layers' W_eff
+                m.drop_derived()
 
     def use_compact_bias(self, enable=True):
         """fp32 INFERENCE on the paper's compact Earth-specific bias (reference layers.py:306-357, :384-391: a
@@ -156,6 +158,8 @@ class PanguModel(nn.Module):
         for m in self.modules():              # derived from the parameters as well (device / dtype moves)
             if getattr(m, "_esb_compact", None) is not None:
                 m._esb_compact = None
+            if hasattr(m, "drop_derived"):
+                m.drop_derived()
         return out
 
     def __getstate__(self):
@@ -164,6 +168,80 @@ class PanguModel(nn.Module):
         state = self.__dict__.copy()
         state["_shadow"] = None
         return state
+
+    # ---- LoRA (reference finetune/lora_tune.py:124-135, peft LoraConfig(r=16, lora_alpha=16, target_modules=<every nn.Linear>,
+    # modules_to_save=["_output_layer.conv", "_output_layer.conv_surface"])) ------------------------------------------------
+
+    def enable_lora(self, r=16, alpha=16, target_modules=None, train_also=("_output_layer.conv", "_output_layer.conv_surface"),
+                    dropout=0.0):
+        """Replace each targeted nn.Linear IN PLACE by a layers.LoraLinear holding the same base Parameters (default: all 67, as
+        the reference does), and freeze everything except the adapters and the modules named in `train_also` (trained in full,
+        peft's `modules_to_save`).  target_modules: None, or names / name suffixes ("linear1", "attention.linear2", ...) as peft
+        matches them.  Returns the list of adapted module names."""
+        from .layers import LoraLinear
+        from .ops import LORA_RANKS
+        if r not in LORA_RANKS:
+            raise ValueError(f"enable_lora: r={r} is not supported; the adapter-gradient kernel covers r in {LORA_RANKS}")
+        if dropout > 0.0:
+            raise ValueError("enable_lora: lora_dropout > 0 is not implemented: dropout on the adapter input cannot be folded into "
+                             "W_eff = W + s*B@A, which the forward kernels run on (it needs a rank-r epilogue on the forward GEMMs)")
+        targets = None if target_modules is None else [target_modules] if isinstance(target_modules, str) else list(target_modules)
+
+        def hit(name):
+            return targets is None or any(name == t or name.endswith("." + t) for t in targets)
+
+        adapted = []
+        for name, mod in list(self.named_modules()):
+            for cname, child in list(mod.named_children()):
+                full = f"{name}.{cname}" if name else cname
+                if type(child) is nn.Linear and hit(full):
+                    setattr(mod, cname, LoraLinear.from_linear(child, r, alpha))
+                    adapted.append(full)
+        if not adapted:
+            raise ValueError(f"enable_lora: no nn.Linear matches target_modules={target_modules!r}")
+        mods = dict(self.named_modules())
+        train_also = tuple(train_also or ())
+        for t in train_also:
+            if t not in mods:
+                raise ValueError(f"enable_lora: train_also names no module: {t!r}")
+        for p in self.parameters():
+            p.requires_grad_(False)
+        for name, mod in self.named_modules():
+            if type(mod) is LoraLinear:
+                mod.lora_A.requires_grad_(True)
+                mod.lora_B.requires_grad_(True)
+        for t in train_also:
+            for p in mods[t].parameters():
+                p.requires_grad_(True)
+        self._lora_train_also = train_also
+        self.invalidate_shadows()
+        return adapted
+
+    def merge_lora(self):
+        """peft's `merge_and_unload`: fold each W_eff into its base weight and put plain nn.Linear modules back -- the 223-key
+        model (reference test_main.py, rollout.GraphedStep, use_compact_bias).  On a HIP device the merged weight IS the W_eff
+        tensor the unmerged forward ran on (bit for bit)."""
+        from .layers import LoraLinear
+        with torch.no_grad():
+            for name, mod in list(self.named_modules()):
+                for cname, child in list(mod.named_children()):
+                    if type(child) is LoraLinear:
+                        child.weight.copy_(child.effective_weight().view_as(child.weight))
+                        setattr(mod, cname, child.to_linear())
+        self._lora_train_also = ()
+        self.invalidate_shadows()
+        return self
+
+    def lora_state_dict(self):
+        """The adapter tensors (`*.lora_A`, `*.lora_B`) plus the parameters of the `train_also` modules: what a LoRA fine-tune
+        changes, i.e. what it needs to save."""
+        keep = tuple(t + "." for t in getattr(self, "_lora_train_also", ()))
+        return OrderedDict((k, v) for k, v in self.state_dict().items()
+                           if k.endswith(".lora_A") or k.endswith(".lora_B") or k.startswith(keep))
+
+    def has_lora(self):
+        from .layers import LoraLinear
+        return any(type(m) is LoraLinear for m in self.modules())
 
     def _init_weights(self, m):                                                # reference pangu_model.py:41-48
         if isinstance(m, nn.Linear):
@@ -220,6 +298,10 @@ class PanguModel(nn.Module):
         want_bf16 = self.compute_dtype == torch.bfloat16 or (
             torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16)
         rev = bool(levels_reversed)
+        if grad_path and want_bf16 and self.has_lora():
+            raise RuntimeError("PanguModel: bf16 training with LoRA adapters is not implemented (the bf16 autograd path's fused "
+                               "MLP / QKV kernels do not keep the operands the adapter gradients need); train in fp32, or "
+                               "run bf16 inference under torch.no_grad()")
         if grad_path and not self.training and getattr(self, "eval_grad_mode", "save") == "recompute":
             return _EvalRecomputeFn.apply(self, (statistics, maps, const_h, want_bf16, rev), input, input_surface, *self.parameters())
         return self._forward_dispatch(input, input_surface, statistics, maps, const_h, want_bf16, grad_path, rev)

@@ -272,7 +272,10 @@ class GraphedTrainStep:
     The bf16 weight shadows the graph reads are re-made IN PLACE after every optimizer step (WeightShadow.refresh_in_place)."""
 
     def __init__(self, model, optimizer, batch, statistics, maps, const_h, stats_last=None, warmup=2):
-        from .layers import DropPath
+        from .layers import DropPath, LoraLinear
+        if any(type(m) is LoraLinear for m in model.modules()):
+            raise RuntimeError("GraphedTrainStep: the model carries LoRA adapters, whose W_eff = W + s*B@A would go stale inside the "
+                               "replayed graph; use train.train_step (or merge_lora() first)")
         if model.training and any(isinstance(m, DropPath) and m.drop_prob > 0.0 for m in model.modules()):
             raise RuntimeError("GraphedTrainStep: stochastic depth is active (model.train() with DropPath rates > 0): a captured step "
                                "cannot skip dropped branches; call model.eval() or use train.train_step")

@@ -86,3 +86,40 @@ def compact_bias(expanded):
     out.index_add_(0, idx, e)
     cnt.index_add_(0, idx, torch.ones_like(idx, dtype=e.dtype))
     return out / cnt.view(-1, 1, 1)
+
+
+def lora_from_peft(sd, adapter="default"):
+    """A `peft_model.state_dict()` as reference finetune/lora_tune.py saves it -> the keys of `PanguModel.enable_lora()`:
+    `base_model.model.` prefix stripped; `X.base_layer.weight` / `.bias` -> `X.weight` / `X.bias`; `X.lora_A.<adapter>.weight`
+    -> `X.lora_A` (likewise lora_B); `X.modules_to_save.<adapter>.*` -> `X.*` (the trained copy); `X.original_module.*` dropped
+    (the untrained copy peft keeps next to it).  Keys of other adapters are dropped too.
+    peft is not a dependency of this project: the mapping follows peft's documented key layout and is tested on synthesised key
+    sets, not on a checkpoint written by peft itself."""
+    out = {}
+    for k, v in sd.items():
+        if k.startswith("base_model.model."):
+            k = k[len("base_model.model."):]
+        if ".original_module." in k:
+            continue
+        if ".modules_to_save." in k:
+            head, tail = k.split(".modules_to_save.", 1)
+            name, _, rest = tail.partition(".")
+            if name != adapter:
+                continue
+            out[f"{head}.{rest}"] = v
+            continue
+        hit = False
+        for ab in ("lora_A", "lora_B"):
+            tag = f".{ab}."
+            if tag in k:
+                head, tail = k.split(tag, 1)
+                if tail == f"{adapter}.weight":
+                    out[f"{head}.{ab}"] = v
+                hit = True
+                break
+        if hit:
+            continue
+        if ".lora_embedding_" in k or ".lora_magnitude_vector." in k:
+            continue
+        out[k.replace(".base_layer.", ".")] = v
+    return out
