@@ -240,6 +240,32 @@ int pangu_patch_recover_gather_bwd(pangu_stream_t stream, const float* d_output,
 int pangu_lat_weighted_sums(pangu_stream_t stream, const float* pred, const float* target, const float* lat_weight,
                             float* out, int planes, int H, int W);
 
+/* ---- ensembles (Pangu-Weather paper: initial states perturbed with Perlin noise) ------------------------------------- */
+
+/* Adds amplitude[var] * std[plane] * noise, in place, to E member states upper [E][5][13][H][W] and surface [E][4][H][W]
+ * (member strides in elements, multiples of 4; upper / surface 16-B aligned).  noise = sum_{o < octaves} persistence^o *
+ * perlin_o, 2-D Perlin gradient noise with period * 2^o lattice cells around the longitude circle (W % that == 0, wrapping at
+ * the dateline; the octaves' lattice columns plus one each sum to at most 1024; octaves 1..8).  Plane p = var*13 + level
+ * (upper), 65 + var (surface); amplitude [9], upper_std [65], surface_std [4] are device arrays.  Member e is global member
+ * first_member + e: its noise depends on (seed, member, plane, position) alone.  control != 0 leaves member 0 untouched.
+ * The definition is pinned in csrc/ensemble.hip.  W % 4 == 0. */
+int pangu_ensemble_perturb_f32(pangu_stream_t stream, float* upper, long long upper_member_stride, float* surface,
+                               long long surface_member_stride, int E, int first_member, int H, int W, const float* amplitude,
+                               const float* upper_std, const float* surface_std, unsigned int seed, int octaves, int period,
+                               float persistence, int control);
+
+/* Latitude-weighted ensemble scores per plane of members [E][planes][H][W] (member stride in elements), 2 <= E <= 128, W % 4 == 0:
+ *   out[plane] = { rmse_mean = sqrt(sum w (m-y)^2 / N), acc_mean = sum w (m-c)(y-c) / sqrt(sum w (m-c)^2 sum w (y-c)^2),
+ *                  spread = sqrt(sum w var / N), crps = sum w crps_fair / N }
+ * with N = H*W, lat_weight w [H], m the ensemble mean, var the unbiased member variance, c = clim[plane] and
+ * crps_fair = (1/E) sum_i |x_i - y| - 1/(2E(E-1)) sum_i sum_j |x_i - x_j|.  target y [planes][H][W] may be NULL (then only
+ * spread is computed, the rest is NaN; clim may be NULL too).  mean_out / std_out [planes][H][W] (may be NULL) receive the
+ * mean and the square root of var.  Per-workgroup partials go through workspace (>= planes * ceil(H / 4) * 32 bytes) and one
+ * fixed-order reduce launch: deterministic, no atomics.  out 16-B aligned. */
+int pangu_ensemble_stats_f32(pangu_stream_t stream, const float* members, long long member_stride, int E, const float* target,
+                             const float* clim, const float* lat_weight, float* out, float* mean_out, float* std_out,
+                             float* workspace, long long workspace_bytes, int planes, int H, int W);
+
 /* ---- bf16 variants (BASELINE configs[2], [4]) --------------------------------------------------------------
  * Activations and weight shadows are bf16 (raw uint16 bit patterns); biases, LayerNorm parameters, softmax and all
  * accumulation stay fp32.  Same semantics and layouts as the fp32 entry points above. */
