@@ -17,38 +17,56 @@ def _wt(w):
     return w.reshape(w.shape[0], -1).t().contiguous()
 
 
-def _lora_grads(ctx, lora, ab, pairs):
-    """LoRA form of a layer Function's backward: pairs = [(i, dy, x)] for each adapted linear i (lora[i] is its scaling, ab[2i],
-    ab[2i+1] its A / B) -> flat list of (dA, dB) per linear of `lora` (None where not adapted or not needed)."""
-    out = [None] * (2 * len(lora))
-    need = ctx.needs_input_grad[-len(ab):]
-    for i, dy, x in pairs:
-        if lora[i] is not None and (need[2 * i] or need[2 * i + 1]):
-            out[2 * i], out[2 * i + 1] = ops.lora_wgrad(dy, x, ab[2 * i], ab[2 * i + 1], lora[i])
-    return out
+def _adapters(ctx, ab, n):
+    """The `ad` argument of _wgrad for each of a Function's n projections, in the order of its `lora` scalings (None where not
+    adapted, and for all n when the Function ran without adapters).  ab: the saved (A, B) pairs, the Function's trailing inputs."""
+    if ctx.lora is None:
+        return (None,) * n
+    p = len(ctx.needs_input_grad) - len(ab)
+    return tuple(None if s is None else (s, ab[2 * i], ab[2 * i + 1], p + 2 * i) for i, s in enumerate(ctx.lora))
+
+
+def _wgrad(ctx, dy, x, w, b=None, ad=None, db_into=None, shape=None):
+    """Parameter gradients of one projection y = x @ W_eff^T (+ b), W_eff = W (+ s B A when adapted).  w / b: input positions of
+    the base weight and bias (b None: no bias); ad: None or (s, A, B, input position of A), from _adapters.  ops.linear_wgrad runs
+    only if W or b asks for a gradient, ops.lora_wgrad only if A or B does -> (dW (in `shape` if given), db, dA, dB), None where
+    not computed.  Both run at the same point of the backward, so an adapter keeps no activation gradient alive for longer."""
+    need = ctx.needs_input_grad
+    dw = db = da = dbb = None
+    if need[w] or (b is not None and need[b]):
+        dw, db = ops.linear_wgrad(dy, x, want_bias=b is not None, db_into=db_into)
+        if shape is not None:
+            dw = dw.reshape(shape)
+    if ad is not None and (need[ad[3]] or need[ad[3] + 1]):
+        da, dbb = ops.lora_wgrad(dy, x, ad[1], ad[2], ad[0])
+    return dw, db, da, dbb
 
 
 def _keep_needed(ctx, grads):
-    """LoRA form: gradients of inputs that do not ask for one (the frozen base parameters -- e.g. the LayerNorm-affine and
-    bias-table gradients that the backward kernels write on every call) are discarded instead of returned."""
+    """One gradient per input (inputs past the end of `grads` get None).  Gradients of inputs that do not ask for one (the frozen
+    base parameters of a LoRA run -- e.g. the LayerNorm-affine and bias-table gradients that the backward kernels write on every
+    call) are discarded instead of returned."""
     need = ctx.needs_input_grad
-    return tuple(g if i < len(need) and need[i] else None for i, g in enumerate(grads))
+    return tuple(g if n else None for g, n in zip(tuple(grads) + (None,) * len(need), need))
 
 
 class EarthBlockFn(torch.autograd.Function):
     """reference models/layers.py:183-253 (+ attention :360-421, Mlp :264-270) for one sample."""
 
+    # the inputs in order; A / B of the adapted projections follow `lora` (the order of its scalings)
+    _INPUTS = ("x", "n1w", "n1b", "n2w", "n2b", "m1w", "m1b", "m2w", "m2b", "esb", "a1w", "a1b", "a2w", "a2b", "geom", "s1", "s2",
+               "dst", "lora", "m1A", "m1B", "m2A", "m2B", "a1A", "a1B", "a2A", "a2B")
+
     @staticmethod
     def forward(ctx, x, n1w, n1b, n2w, n2b, m1w, m1b, m2w, m2b, esb, a1w, a1b, a2w, a2b, geom, s1, s2, dst=None, lora=None, *ab):
         # dst: optional 1-tuple holding the (N, C) row-strided tensor the block writes its result into (one half of the
         # skip-concat buffer of reference pangu_model.py:81); wrapped so that autograd does not see a tensor argument.
-        # LoRA form: lora = scalings of (linear.linear1, linear.linear2, attention.linear1, attention.linear2), None where not
-        # adapted; m1w / m2w / a1w / a2w are then the W_eff tensors (no gradient) and ab = (A, B) per linear
+        # lora: scalings of (linear.linear1, linear.linear2, attention.linear1, attention.linear2), None where not adapted, or None
+        # without adapters (layers.lora_args); m1w / m2w / a1w / a2w are then the W_eff tensors and ab = (A, B) per linear
         out = dst[0] if dst else None
         Z, H, W, heads, shifted = geom
-        ctx.geom, ctx.s1, ctx.s2 = geom, s1, s2
-        ctx.lora = lora
-        saved = [x, n1w, n2w, m1w, m2w, esb, a1w, a1b, a2w] + ([a for a in ab] if lora is not None else [])
+        ctx.geom, ctx.s1, ctx.s2, ctx.lora = geom, s1, s2, lora
+        saved = [x, n1w, n2w, m1w, m2w, esb, a1w, a1b, a2w, *ab]
         x1 = x
         if s1 != 0.0:
             qkv = ops.linear(x, a1w, a1b)
@@ -77,26 +95,25 @@ class EarthBlockFn(torch.autograd.Function):
         # (every atomically accumulated gradient buffer of the whole backward pass comes out of ONE zero fill: ops._zeros)
         Z, H, W, heads, shifted = ctx.geom
         s1, s2 = ctx.s1, ctx.s2
-        sv = list(ctx.saved_tensors)
+        sv = ctx.saved_tensors
         x, n1w, n2w, m1w, m2w, esb, a1w, a1b, a2w = sv[:9]
-        lora = ctx.lora
-        nab = 8 if lora is not None else 0
-        ab = sv[9:9 + nab]
-        rest = sv[9 + nab:]
-        if lora is not None:
-            return EarthBlockFn._backward_lora(ctx, dout, x, n1w, n2w, m1w, m2w, esb, a1w, a1b, a2w, rest, lora, ab)
+        ab = sv[9:9 + 2 * len(ctx.lora or ())]
+        rest = sv[9 + len(ab):]
+        ad_m1, ad_m2, ad_a1, ad_a2 = _adapters(ctx, ab, 4)
+        need = dict(zip(EarthBlockFn._INPUTS, ctx.needs_input_grad))
+        g = {}
         if s1 != 0.0:
             qkv, o, lse, y = rest[:4]
             rest = rest[4:]
-        g = {k: None for k in ("n1w", "n1b", "n2w", "n2b", "m1w", "m1b", "m2w", "m2b", "esb", "a1w", "a1b", "a2w", "a2b")}
         dx1 = dout
+        # _wgrad's input positions: m1w 5, m1b 6, m2w 7, m2b 8, a1w 10, a1b 11, a2w 12, a2b 13
         if s2 != 0.0:
             x1, pre, h, m = rest
             dm, g["n2w"], g["n2b"] = ops.ln_residual_bwd(dout, m, n2w, s2)
-            g["m2w"], g["m2b"] = ops.linear_wgrad(dm, h)
+            g["m2w"], g["m2b"], g["m2A"], g["m2B"] = _wgrad(ctx, dm, h, 7, 8, ad_m2)
             dpre = ops.linear(dm, _wt(m2w), None, act=ops.ACT_GELU_BWD, aux=pre)
             del dm
-            g["m1w"], g["m1b"] = ops.linear_wgrad(dpre, x1)
+            g["m1w"], g["m1b"], g["m1A"], g["m1B"] = _wgrad(ctx, dpre, x1, 5, 6, ad_m1)
             if dout.is_contiguous():      # residual gradient added in the GEMM epilogue (no extra pass over N x C)
                 dx1 = ops.linear(dpre, _wt(m1w), act=ops.ACT_ADD, aux=dout)
             else:
@@ -106,15 +123,16 @@ class EarthBlockFn(torch.autograd.Function):
         dx = dx1
         if s1 != 0.0:
             dy, g["n1w"], g["n1b"] = ops.ln_residual_bwd(dx1, y, n1w, s1)
-            g["a2w"], g["a2b"] = ops.linear_wgrad(dy, o)
+            g["a2w"], g["a2b"], g["a2A"], g["a2B"] = _wgrad(ctx, dy, o, 12, 13, ad_a2)
             do = ops.linear(dy, _wt(a2w))
             del dy
+            # (the bias-table gradient goes straight into the DP flat buffer)
             dqkv, dqb_pad, desb = ops.window_attention_bwd(qkv, a1b, esb[0], o, lse, do, Z, H, W, heads, shifted,
-                                                           desb_out=ops.grad_slot(esb))      # straight into the DP flat buffer
+                                                           desb_out=ops.grad_slot(esb) if need["esb"] else None)
             del do
             g["esb"] = desb.unsqueeze(0)
             # linear1's bias gradient = column sums of dqkv + the pad-slot term already in dqb_pad: the kernel adds into that buffer
-            g["a1w"], g["a1b"] = ops.linear_wgrad(dqkv, x, db_into=dqb_pad)
+            g["a1w"], g["a1b"], g["a1A"], g["a1B"] = _wgrad(ctx, dqkv, x, 10, 11, ad_a1, db_into=dqb_pad)
             if dx1.is_contiguous():
                 dx = ops.linear(dqkv, _wt(a1w), act=ops.ACT_ADD, aux=dx1)
             else:
@@ -122,81 +140,12 @@ class EarthBlockFn(torch.autograd.Function):
                 dx += dx1
         elif not dx.is_contiguous():
             dx = dx.contiguous()
-        ops.fill_dropped_grads(g, {"n1w": n1w, "n1b": n1w, "n2w": n2w, "n2b": n2w, "m1w": m1w, "m1b": m1w[:, 0], "m2w": m2w, "m2b": n2w,
-                                   "esb": esb, "a1w": a1w, "a1b": a1b, "a2w": a2w, "a2b": n1w})
-        return (dx, g["n1w"], g["n1b"], g["n2w"], g["n2b"], g["m1w"], g["m1b"], g["m2w"], g["m2b"], g["esb"],
-                g["a1w"], g["a1b"], g["a2w"], g["a2b"], None, None, None, None, None)
-
-    @staticmethod
-    def _backward_lora(ctx, dout, x, n1w, n2w, m1w, m2w, esb, a1w, a1b, a2w, rest, lora, ab):
-        """The backward with adapters: each adapted linear gets (dA, dB) from ops.lora_wgrad where the plain form calls
-        ops.linear_wgrad; the weight-gradient GEMMs of frozen base weights are skipped (a base weight / bias that DOES ask for a
-        gradient -- not adapted, or unfrozen by hand -- still gets it from linear_wgrad)."""
-        Z, H, W, heads, shifted = ctx.geom
-        s1, s2 = ctx.s1, ctx.s2
-        need = ctx.needs_input_grad
-        # input positions: m1w 5, m1b 6, m2w 7, m2b 8, a1w 10, a1b 11, a2w 12, a2b 13
-        want = lambda *pos: any(need[p] for p in pos)
-        g = {}
-        pairs = []
-        if s1 != 0.0:
-            qkv, o, lse, y = rest[:4]
-            rest = rest[4:]
-        dx1 = dout
-        if s2 != 0.0:
-            x1, pre, h, m = rest
-            dm, g["n2w"], g["n2b"] = ops.ln_residual_bwd(dout, m, n2w, s2)
-            if want(7, 8):
-                g["m2w"], g["m2b"] = ops.linear_wgrad(dm, h)
-            pairs.append((1, dm, h))
-            dpre = ops.linear(dm, _wt(m2w), None, act=ops.ACT_GELU_BWD, aux=pre)
-            if want(5, 6):
-                g["m1w"], g["m1b"] = ops.linear_wgrad(dpre, x1)
-            pairs.append((0, dpre, x1))
-            gl = _lora_grads(ctx, lora, ab, pairs)
-            pairs = []
-            g.update({"m1A": gl[0], "m1B": gl[1], "m2A": gl[2], "m2B": gl[3]})
-            del dm
-            if dout.is_contiguous():
-                dx1 = ops.linear(dpre, _wt(m1w), act=ops.ACT_ADD, aux=dout)
-            else:
-                dx1 = ops.linear(dpre, _wt(m1w))
-                dx1 += dout
-            del dpre
-        dx = dx1
-        if s1 != 0.0:
-            dy, g["n1w"], g["n1b"] = ops.ln_residual_bwd(dx1, y, n1w, s1)
-            if want(12, 13):
-                g["a2w"], g["a2b"] = ops.linear_wgrad(dy, o)
-            pairs.append((3, dy, o))
-            do = ops.linear(dy, _wt(a2w))
-            dqkv, dqb_pad, desb = ops.window_attention_bwd(qkv, a1b, esb[0], o, lse, do, Z, H, W, heads, shifted,
-                                                           desb_out=ops.grad_slot(esb) if need[9] else None)
-            del do
-            g["esb"] = desb.unsqueeze(0)
-            if want(10, 11):
-                g["a1w"], g["a1b"] = ops.linear_wgrad(dqkv, x, db_into=dqb_pad)
-            pairs.append((2, dqkv, x))
-            gl = _lora_grads(ctx, lora, ab, pairs)
-            g.update({"a1A": gl[4], "a1B": gl[5], "a2A": gl[6], "a2B": gl[7]})
-            del dy
-            if dx1.is_contiguous():
-                dx = ops.linear(dqkv, _wt(a1w), act=ops.ACT_ADD, aux=dx1)
-            else:
-                dx = ops.linear(dqkv, _wt(a1w))
-                dx += dx1
-        elif not dx.is_contiguous():
-            dx = dx.contiguous()
-        names = ["n1w", "n1b", "n2w", "n2b", "m1w", "m1b", "m2w", "m2b", "esb", "a1w", "a1b", "a2w", "a2b"]
-        abn = ["m1A", "m1B", "m2A", "m2B", "a1A", "a1B", "a2A", "a2B"]
-        shapes = {"n1w": n1w, "n1b": n1w, "n2w": n2w, "n2b": n2w, "m1w": m1w, "m1b": m1w[:, 0], "m2w": m2w, "m2b": n2w,
-                  "esb": esb, "a1w": a1w, "a1b": a1b, "a2w": a2w, "a2b": n1w}
-        shapes.update({k: t for k, t in zip(abn, ab) if t is not None})
-        # only what asks for a gradient is filled for a dropped branch (the frozen base tensors get nothing)
-        ops.fill_dropped_grads(g, {k: shapes[k] for k, p in zip(names + abn, list(range(1, 14)) + list(range(19, 27)))
-                                   if k in shapes and need[p]})
-        grads = (dx,) + tuple(g.get(k) for k in names) + (None,) * 5 + tuple(g.get(k) for k in abn)
-        return _keep_needed(ctx, grads)
+        g["x"] = dx
+        like = {"n1w": n1w, "n1b": n1w, "n2w": n2w, "n2b": n2w, "m1w": m1w, "m1b": m1w[:, 0], "m2w": m2w, "m2b": n2w, "esb": esb,
+                "a1w": a1w, "a1b": a1b, "a2w": a2w, "a2b": n1w, **dict(zip(EarthBlockFn._INPUTS[19:], ab))}
+        # only what asks for a gradient is filled for a dropped branch (frozen base tensors get nothing)
+        ops.fill_dropped_grads(g, {k: t for k, t in like.items() if need.get(k)})
+        return _keep_needed(ctx, [g.get(k) for k in EarthBlockFn._INPUTS])
 
 
 class AttentionWindowsFn(torch.autograd.Function):
@@ -205,38 +154,26 @@ class AttentionWindowsFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xw, w1, b1, w2, b2, esb, mask, geom, lora=None, *ab):
-        # LoRA form: lora = scalings of (linear1, linear2), w1 / w2 the W_eff tensors, ab = (A1, B1, A2, B2)
+        # lora: scalings of (linear1, linear2) (layers.lora_args), w1 / w2 then the W_eff tensors, ab = (A1, B1, A2, B2)
         n_lon, types, heads = geom
         qkv = ops.linear(xw, w1, b1)
         o = ops.attention_windows(qkv, esb[0], mask, n_lon, types, heads)
-        ctx.save_for_backward(xw, qkv, o, w1, w2, esb, *([mask] if mask is not None else []))
-        ctx.geom, ctx.lora, ctx.ab = geom, lora, ab
+        ctx.save_for_backward(xw, qkv, o, w1, w2, esb, mask, *ab)
+        ctx.geom, ctx.lora = geom, lora
         return ops.linear(o, w2, b2)
 
     @staticmethod
     def backward(ctx, dy):
-        xw, qkv, o, w1, w2, esb, *rest = ctx.saved_tensors
-        mask = rest[0] if rest else None
+        xw, qkv, o, w1, w2, esb, mask, *ab = ctx.saved_tensors
+        ad1, ad2 = _adapters(ctx, ab, 2)
         n_lon, types, heads = ctx.geom
         dy = dy.contiguous()
-        if ctx.lora is not None:
-            need = ctx.needs_input_grad
-            dw2 = db2 = dw1 = db1 = None
-            if need[3] or need[4]:
-                dw2, db2 = ops.linear_wgrad(dy, o)
-            do = ops.linear(dy, _wt(w2))
-            dqkv, desb = ops.attention_windows_bwd(qkv, esb[0], mask, do, n_lon, types, heads)
-            if need[1] or need[2]:
-                dw1, db1 = ops.linear_wgrad(dqkv, xw)
-            gl = _lora_grads(ctx, ctx.lora, ctx.ab, [(0, dqkv, xw), (1, dy, o)])
-            dx = ops.linear(dqkv, _wt(w1))
-            return _keep_needed(ctx, (dx, dw1, db1, dw2, db2, desb.unsqueeze(0), None, None, None, *gl))
-        dw2, db2 = ops.linear_wgrad(dy, o)
+        dw2, db2, dA2, dB2 = _wgrad(ctx, dy, o, 3, 4, ad2)
         do = ops.linear(dy, _wt(w2))
         dqkv, desb = ops.attention_windows_bwd(qkv, esb[0], mask, do, n_lon, types, heads)
-        dw1, db1 = ops.linear_wgrad(dqkv, xw)
+        dw1, db1, dA1, dB1 = _wgrad(ctx, dqkv, xw, 1, 2, ad1)
         dx = ops.linear(dqkv, _wt(w1))
-        return dx, dw1, db1, dw2, db2, desb.unsqueeze(0), None, None
+        return _keep_needed(ctx, (dx, dw1, db1, dw2, db2, desb.unsqueeze(0), None, None, None, dA1, dB1, dA2, dB2))
 
 
 class MlpFn(torch.autograd.Function):
@@ -244,31 +181,22 @@ class MlpFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, lora=None, *ab):
-        # LoRA form: lora = scalings of (linear1, linear2), w1 / w2 the W_eff tensors, ab = (A1, B1, A2, B2)
+        # lora: scalings of (linear1, linear2) (layers.lora_args), w1 / w2 then the W_eff tensors, ab = (A1, B1, A2, B2)
         pre = torch.empty((x.shape[0], w1.shape[0]), dtype=x.dtype, device=x.device)
         h = ops.linear(x, w1, b1, act=ops.ACT_GELU, aux=pre)
-        ctx.save_for_backward(x, pre, h, w1, w2)
-        ctx.lora, ctx.ab = lora, ab
+        ctx.save_for_backward(x, pre, h, w1, w2, *ab)
+        ctx.lora = lora
         return ops.linear(h, w2, b2)
 
     @staticmethod
     def backward(ctx, dm):
-        x, pre, h, w1, w2 = ctx.saved_tensors
+        x, pre, h, w1, w2, *ab = ctx.saved_tensors
+        ad1, ad2 = _adapters(ctx, ab, 2)
         dm = dm.contiguous()
-        if ctx.lora is not None:
-            need = ctx.needs_input_grad
-            dw2 = db2 = dw1 = db1 = None
-            if need[3] or need[4]:
-                dw2, db2 = ops.linear_wgrad(dm, h)
-            dpre = ops.linear(dm, _wt(w2), None, act=ops.ACT_GELU_BWD, aux=pre)
-            if need[1] or need[2]:
-                dw1, db1 = ops.linear_wgrad(dpre, x)
-            gl = _lora_grads(ctx, ctx.lora, ctx.ab, [(0, dpre, x), (1, dm, h)])
-            return _keep_needed(ctx, (ops.linear(dpre, _wt(w1)), dw1, db1, dw2, db2, None, *gl))
-        dw2, db2 = ops.linear_wgrad(dm, h)
+        dw2, db2, dA2, dB2 = _wgrad(ctx, dm, h, 3, 4, ad2)
         dpre = ops.linear(dm, _wt(w2), None, act=ops.ACT_GELU_BWD, aux=pre)
-        dw1, db1 = ops.linear_wgrad(dpre, x)
-        return ops.linear(dpre, _wt(w1)), dw1, db1, dw2, db2
+        dw1, db1, dA1, dB1 = _wgrad(ctx, dpre, x, 1, 2, ad1)
+        return _keep_needed(ctx, (ops.linear(dpre, _wt(w1)), dw1, db1, dw2, db2, None, dA1, dB1, dA2, dB2))
 
 
 def refuse_constant_grads(maps, const_h, statistics=()):
@@ -301,11 +229,8 @@ class PatchEmbedFn(torch.autograd.Function):
         n_s = a_s.shape[0]
         dx = dx.contiguous()
         need = ctx.needs_input_grad
-        dsw = dsb = dcw = dcb = None
-        if any(need[:4]):
-            dsw, dsb = ops.linear_wgrad(dx[:n_s], a_s)
-            dcw, dcb = ops.linear_wgrad(dx[n_s:], a_u)
-            dcw, dsw = dcw.reshape(ctx.shapes[0]), dsw.reshape(ctx.shapes[1])
+        dsw, dsb = _wgrad(ctx, dx[:n_s], a_s, 2, 3, shape=ctx.shapes[1])[:2]
+        dcw, dcb = _wgrad(ctx, dx[n_s:], a_u, 0, 1, shape=ctx.shapes[0])[:2]
         d_in = d_in_s = None
         if need[4] or need[5]:
             LAT, LON, rev = ctx.geom
@@ -313,7 +238,7 @@ class PatchEmbedFn(torch.autograd.Function):
             da_s = ops.linear(dx[:n_s], _wt(sw)[:64].contiguous())
             da_u = ops.linear(dx[n_s:], _wt(cw)[:160].contiguous())
             d_in, d_in_s = ops.patch_embed_gather_bwd(da_s, da_u, s_std, u_std, LAT, LON, rev)
-        return (dcw, dcb, dsw, dsb, d_in if need[4] else None, d_in_s if need[5] else None) + (None,) * 7
+        return _keep_needed(ctx, (dcw, dcb, dsw, dsb, d_in, d_in_s))
 
 
 class DownSampleFn(torch.autograd.Function):
@@ -325,32 +250,25 @@ class DownSampleFn(torch.autograd.Function):
         # down-sampling backward kernel instead of by autograd's elementwise add): see autograd_bf16.DownSampleFnBF16
         Z, H, W = geom
         g = ops.downsample_ln(x, nw, nb, Z, H, W)
-        ctx.save_for_backward(x, g, lw, nw)
+        ctx.save_for_backward(x, g, lw, nw, *ab)
         ctx.geom, ctx.skip_grad = geom, skip_grad
-        ctx.lora, ctx.ab = lora, ab          # LoRA form: lw is W_eff, ab = (A, B)
+        ctx.lora = lora          # (scaling,) of an adapted linear (layers.lora_args): lw is then W_eff, ab = (A, B)
         if skip_grad is not None:
             skip_grad[1] = True
         return ops.linear(g, lw)
 
     @staticmethod
     def backward(ctx, dout):
-        x, g, lw, nw = ctx.saved_tensors
+        x, g, lw, nw, *ab = ctx.saved_tensors
         Z, H, W = ctx.geom
         dout = dout.contiguous()
-        gl = []
-        if ctx.lora is not None:
-            dlw = ops.linear_wgrad(dout, g, want_bias=False)[0] if ctx.needs_input_grad[1] else None
-            gl = _lora_grads(ctx, ctx.lora, ctx.ab, [(0, dout, g)])
-        else:
-            dlw, _ = ops.linear_wgrad(dout, g, want_bias=False)
+        dlw, _, dA, dB = _wgrad(ctx, dout, g, 1, ad=_adapters(ctx, ab, 1)[0])
         dg = ops.linear(dout, _wt(lw))
         add = None
         if ctx.skip_grad is not None:
             add, ctx.skip_grad[0] = ctx.skip_grad[0], None
         dx, dnw, dnb = ops.downsample_ln_bwd(dg, x, nw, Z, H, W, add=add)
-        if ctx.lora is not None:
-            return _keep_needed(ctx, (dx, dlw, dnw, dnb, None, None, None, *gl))
-        return dx, dlw, dnw, dnb, None, None
+        return _keep_needed(ctx, (dx, dlw, dnw, dnb, None, None, None, dA, dB))
 
 
 class UpSampleFn(torch.autograd.Function):
@@ -358,35 +276,26 @@ class UpSampleFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, l1w, l2w, nw, nb, geom, lora=None, *ab):
-        # LoRA form: lora = scalings of (linear1, linear2), l1w / l2w the W_eff tensors, ab = (A1, B1, A2, B2)
-        ctx.lora, ctx.ab = lora, ab
+        # lora: scalings of (linear1, linear2) (layers.lora_args), l1w / l2w then the W_eff tensors, ab = (A1, B1, A2, B2)
         Z, H2, W2, H = geom
         y = ops.linear(x, l1w)
         g = ops.upsample_ln(y, nw, nb, Z, H2, W2, H)
-        ctx.save_for_backward(x, y, g, l1w, l2w, nw)
-        ctx.geom = geom
+        ctx.save_for_backward(x, y, g, l1w, l2w, nw, *ab)
+        ctx.geom, ctx.lora = geom, lora
         return ops.linear(g, l2w)
 
     @staticmethod
     def backward(ctx, dout):
-        x, y, g, l1w, l2w, nw = ctx.saved_tensors
+        x, y, g, l1w, l2w, nw, *ab = ctx.saved_tensors
+        ad1, ad2 = _adapters(ctx, ab, 2)
         Z, H2, W2, H = ctx.geom
         dout = dout.contiguous()
-        if ctx.lora is not None:
-            need = ctx.needs_input_grad
-            dl2w = ops.linear_wgrad(dout, g, want_bias=False)[0] if need[2] else None
-            dg = ops.linear(dout, _wt(l2w))
-            dy, dnw, dnb = ops.upsample_ln_bwd(dg, y, nw, Z, H2, W2, H)
-            dl1w = ops.linear_wgrad(dy, x, want_bias=False)[0] if need[1] else None
-            gl = _lora_grads(ctx, ctx.lora, ctx.ab, [(0, dy, x), (1, dout, g)])
-            dx = ops.linear(dy, _wt(l1w))
-            return _keep_needed(ctx, (dx, dl1w, dl2w, dnw, dnb, None, None, *gl))
-        dl2w, _ = ops.linear_wgrad(dout, g, want_bias=False)
+        dl2w, _, dA2, dB2 = _wgrad(ctx, dout, g, 2, ad=ad2)
         dg = ops.linear(dout, _wt(l2w))
         dy, dnw, dnb = ops.upsample_ln_bwd(dg, y, nw, Z, H2, W2, H)
-        dl1w, _ = ops.linear_wgrad(dy, x, want_bias=False)
+        dl1w, _, dA1, dB1 = _wgrad(ctx, dy, x, 1, ad=ad1)
         dx = ops.linear(dy, _wt(l1w))
-        return dx, dl1w, dl2w, dnw, dnb, None
+        return _keep_needed(ctx, (dx, dl1w, dl2w, dnw, dnb, None, None, dA1, dB1, dA2, dB2))
 
 
 class PatchRecoverFn(torch.autograd.Function):
@@ -406,12 +315,12 @@ class PatchRecoverFn(torch.autograd.Function):
         x, cw, sw = ctx.saved_tensors
         n_s, LAT, LON = ctx.geom
         dy_u, dy_s = ops.patch_recover_gather_bwd(d_out.contiguous(), d_out_s.contiguous())
-        dcw, dcb = ops.linear_wgrad(dy_u, x[n_s:])
-        dsw, dsb = ops.linear_wgrad(dy_s, x[:n_s])
+        dcw, dcb = _wgrad(ctx, dy_u, x[n_s:], 1, 2, shape=cw.shape)[:2]
+        dsw, dsb = _wgrad(ctx, dy_s, x[:n_s], 3, 4, shape=sw.shape)[:2]
         dx = torch.empty((x.shape[0], x.shape[1]), dtype=torch.float32, device=x.device)
         ops.linear(dy_s, _wt(sw), out=dx[:n_s])
         ops.linear(dy_u, _wt(cw), out=dx[n_s:])
-        return dx, dcw.reshape(cw.shape), dcb, dsw.reshape(sw.shape), dsb, None
+        return _keep_needed(ctx, (dx, dcw, dcb, dsw, dsb))
 
 
 class PatchRecoverHalvesFn(torch.autograd.Function):
@@ -438,8 +347,8 @@ class PatchRecoverHalvesFn(torch.autograd.Function):
         n_s, LAT, LON = ctx.geom
         C = cat.shape[1] // 2
         dy_u, dy_s = ops.patch_recover_gather_bwd(d_out.contiguous(), d_out_s.contiguous())
-        dcw, dcb = ops.linear_wgrad(dy_u, cat[n_s:])
-        dsw, dsb = ops.linear_wgrad(dy_s, cat[:n_s])
+        dcw, dcb = _wgrad(ctx, dy_u, cat[n_s:], 2, 3, shape=cw.shape)[:2]
+        dsw, dsb = _wgrad(ctx, dy_s, cat[:n_s], 4, 5, shape=sw.shape)[:2]
         wt_s, wt_u = _wt(sw), _wt(cw)                                      # (2C, 64), (2C, 160): rows = input channels
         d_skip = torch.empty((cat.shape[0], C), dtype=torch.float32, device=cat.device)
         d_x = torch.empty_like(d_skip)
@@ -452,4 +361,4 @@ class PatchRecoverHalvesFn(torch.autograd.Function):
             # (if autograd pruned that node -- `torch.autograd.grad(loss, inputs=[layer-3 parameters])` -- nothing consumes the
             # slot: it is emptied when this backward pass ends instead of pinning 200-400 MB until the next forward)
             torch.autograd.Variable._execution_engine.queue_callback(lambda sg=sg: sg.__setitem__(0, None))
-        return d_skip, d_x, dcw.reshape(cw.shape), dcb, dsw.reshape(sw.shape), dsb, None, None
+        return _keep_needed(ctx, (d_skip, d_x, dcw, dcb, dsw, dsb))

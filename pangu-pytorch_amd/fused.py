@@ -10,18 +10,6 @@ from .autograd import DownSampleFn, EarthBlockFn, MlpFn, PatchEmbedFn, PatchReco
 from . import layers as _layers      # (layers imports this module: attribute access at call time)
 
 
-def _w(lin):
-    return _layers.eff_weight(lin)
-
-
-def lora_of(lin):
-    return _layers.lora_of(lin)
-
-
-def _lora_args(loras):
-    return _layers._lora_args(loras)
-
-
 def _train_path(module, *tensors):
     """Autograd path iff grad mode is on and something upstream (a parameter or an activation) needs a gradient."""
     if not torch.is_grad_enabled():
@@ -54,11 +42,10 @@ def _tok2d(x):
 def mlp(m, x2d):
     """Mlp.forward on its own (reference layers.py:264-270; the block never comes through here): differentiable."""
     if _train_path(m, x2d):
-        lora = (lora_of(m.linear1), lora_of(m.linear2))
-        return MlpFn.apply(x2d.contiguous(), _w(m.linear1), m.linear1.bias, _w(m.linear2), m.linear2.bias,
-                           *(_lora_args(lora) if any(lora) else ()))
-    h = ops.linear(x2d, _w(m.linear1), m.linear1.bias, act=ops.ACT_GELU)
-    return ops.linear(h, _w(m.linear2), m.linear2.bias)
+        return MlpFn.apply(x2d.contiguous(), _layers.eff_weight(m.linear1), m.linear1.bias, _layers.eff_weight(m.linear2),
+                           m.linear2.bias, *_layers.lora_args(m.linear1, m.linear2))
+    h = ops.linear(x2d, _layers.eff_weight(m.linear1), m.linear1.bias, act=ops.ACT_GELU)
+    return ops.linear(h, _layers.eff_weight(m.linear2), m.linear2.bias)
 
 
 def earth_block(blk, x, Z, H, W, roll, out=None):
@@ -71,15 +58,15 @@ def earth_block(blk, x, Z, H, W, roll, out=None):
         # out as a 2-D (N, C) row-strided tensor (B = 1): the block function writes its result there (a half of the
         # skip-concat buffer, PanguModel._forward_f32) -- no copy
         direct = out is not None and out.dim() == 2 and B == 1
-        lora = (lora_of(blk.linear.linear1), lora_of(blk.linear.linear2), lora_of(att.linear1), lora_of(att.linear2))
-        extra = ((out,) if direct else None,) + (_lora_args(lora) if any(lora) else ())
+        extra = ((out,) if direct else None,) + _layers.lora_args(blk.linear.linear1, blk.linear.linear2, att.linear1, att.linear2)
         for xb in _samples(x):
             s1 = dp.sample_scale(blk.training) if hasattr(dp, "sample_scale") else 1.0
             s2 = dp.sample_scale(blk.training) if hasattr(dp, "sample_scale") else 1.0
             outs.append(EarthBlockFn.apply(
                 xb, blk.norm1.weight, blk.norm1.bias, blk.norm2.weight, blk.norm2.bias,
-                _w(blk.linear.linear1), blk.linear.linear1.bias, _w(blk.linear.linear2), blk.linear.linear2.bias,
-                att.earth_specific_bias, _w(att.linear1), att.linear1.bias, _w(att.linear2), att.linear2.bias,
+                _layers.eff_weight(blk.linear.linear1), blk.linear.linear1.bias,
+                _layers.eff_weight(blk.linear.linear2), blk.linear.linear2.bias, att.earth_specific_bias,
+                _layers.eff_weight(att.linear1), att.linear1.bias, _layers.eff_weight(att.linear2), att.linear2.bias,
                 (Z, H, W, att.head_number, bool(roll)), s1, s2, *extra))
         y = _stack(outs, B)
         if out is not None and not direct:
@@ -90,7 +77,7 @@ def earth_block(blk, x, Z, H, W, roll, out=None):
     s1 = dp.sample_scale(blk.training) if hasattr(dp, "sample_scale") else 1.0
     s2 = dp.sample_scale(blk.training) if hasattr(dp, "sample_scale") else 1.0
     if s1 != 0.0:
-        qkv = ops.linear(x2, _w(att.linear1), att.linear1.bias)                      # (B*N, 3C)
+        qkv = ops.linear(x2, _layers.eff_weight(att.linear1), att.linear1.bias)      # (B*N, 3C)
         # inference on the paper's compact bias table (PanguModel.use_compact_bias): 10 MB instead of 62 MB per block
         esb_c = getattr(att, "_esb_compact", None)
         if esb_c is not None:                 # stale table (weights changed since it was folded): the expanded parameter
@@ -103,10 +90,10 @@ def earth_block(blk, x, Z, H, W, roll, out=None):
                                             att.head_number, roll, compact=cp) for b in range(B)], 0) if B > 1 else \
             ops.window_attention(qkv, att.linear1.bias, esb, Z, H, W, att.head_number, roll, compact=cp)
         if C in (192, 384):     # projection + post-norm residual in one launch (the GEMM tile spans the row)
-            x1 = ops.linear_ln_residual(o, _w(att.linear2), att.linear2.bias, x2, blk.norm1.weight, blk.norm1.bias,
-                                        branch_scale=s1)
+            x1 = ops.linear_ln_residual(o, _layers.eff_weight(att.linear2), att.linear2.bias, x2, blk.norm1.weight,
+                                        blk.norm1.bias, branch_scale=s1)
         else:
-            y = ops.linear(o, _w(att.linear2), att.linear2.bias)
+            y = ops.linear(o, _layers.eff_weight(att.linear2), att.linear2.bias)
             x1 = ops.ln_residual(y, x2, blk.norm1.weight, blk.norm1.bias, branch_scale=s1)
     else:
         x1 = x2
@@ -115,9 +102,9 @@ def earth_block(blk, x, Z, H, W, roll, out=None):
     o2 = None if out is None else (out if out.dim() == 2 else _tok2d(out))
     if s2 != 0.0:
         if C in (192, 384):
-            h = ops.linear(x1, _w(blk.linear.linear1), blk.linear.linear1.bias, act=ops.ACT_GELU)
-            x2o = ops.linear_ln_residual(h, _w(blk.linear.linear2), blk.linear.linear2.bias, x1, blk.norm2.weight,
-                                         blk.norm2.bias, out=o2, branch_scale=s2)
+            h = ops.linear(x1, _layers.eff_weight(blk.linear.linear1), blk.linear.linear1.bias, act=ops.ACT_GELU)
+            x2o = ops.linear_ln_residual(h, _layers.eff_weight(blk.linear.linear2), blk.linear.linear2.bias, x1,
+                                         blk.norm2.weight, blk.norm2.bias, out=o2, branch_scale=s2)
         else:
             m = mlp(blk.linear, x1)
             x2o = ops.ln_residual(m, x1, blk.norm2.weight, blk.norm2.bias, out=o2, branch_scale=s2)
@@ -160,36 +147,32 @@ def patch_embed(m, inp, inp_surface, statistics, maps, const_h, levels_reversed=
 def down_sample(m, x, Z, H, W, skip_grad=None):
     B, N, C = x.shape
     if _train_path(m, x):
-        lora = (lora_of(m.linear),)
-        extra = _lora_args(lora) if any(lora) else ()
-        return _stack([DownSampleFn.apply(xb, _w(m.linear), m.norm.weight, m.norm.bias, (Z, H, W), skip_grad if B == 1 else None,
-                                          *extra) for xb in _samples(x)], B)
+        return _stack([DownSampleFn.apply(xb, _layers.eff_weight(m.linear), m.norm.weight, m.norm.bias, (Z, H, W),
+                                          skip_grad if B == 1 else None, *_layers.lora_args(m.linear)) for xb in _samples(x)], B)
     outs = []
     for b in range(B):
         g = ops.downsample_ln(_tok2d(x[b:b + 1]), m.norm.weight, m.norm.bias, Z, H, W)
-        outs.append(ops.linear(g, _w(m.linear)))
+        outs.append(ops.linear(g, _layers.eff_weight(m.linear)))
     return torch.stack(outs, 0) if B > 1 else outs[0].unsqueeze(0)
 
 
 def up_sample(m, x, Z, H2, W2, H, out=None):
     B, N, C2 = x.shape
     if _train_path(m, x):
-        lora = (lora_of(m.linear1), lora_of(m.linear2))
-        extra = _lora_args(lora) if any(lora) else ()
-        y = _stack([UpSampleFn.apply(xb, _w(m.linear1), _w(m.linear2), m.norm.weight, m.norm.bias,
-                                     (Z, H2, W2, H), *extra) for xb in _samples(x)], B)
+        y = _stack([UpSampleFn.apply(xb, _layers.eff_weight(m.linear1), _layers.eff_weight(m.linear2), m.norm.weight, m.norm.bias,
+                                     (Z, H2, W2, H), *_layers.lora_args(m.linear1, m.linear2)) for xb in _samples(x)], B)
         if out is not None:
             out.copy_(y)
             return out
         return y
-    y = ops.linear(_tok2d(x), _w(m.linear1))                          # (B*N, 4Co)
+    y = ops.linear(_tok2d(x), _layers.eff_weight(m.linear1))          # (B*N, 4Co)
     Co = y.shape[1] // 4
     Nf = Z * H * 2 * W2
     if out is None:
         out = torch.empty((B, Nf, Co), dtype=torch.float32, device=x.device)
     for b in range(B):
         g = ops.upsample_ln(y[b * N:(b + 1) * N], m.norm.weight, m.norm.bias, Z, H2, W2, H)
-        ops.linear(g, _w(m.linear2), out=_tok2d(out[b:b + 1]))
+        ops.linear(g, _layers.eff_weight(m.linear2), out=_tok2d(out[b:b + 1]))
     return out
 
 

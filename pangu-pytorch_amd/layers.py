@@ -140,14 +140,6 @@ class LoraLinear(nn.Linear):
         return super().extra_repr() + f", r={self.r}, alpha={self.lora_alpha}"
 
 
-def _lora_args(loras):
-    """Trailing arguments of a layer Function's LoRA form: (scalings tuple, A1, B1, A2, B2, ..) with None for plain linears."""
-    out = [tuple(l[0] if l else None for l in loras)]
-    for l in loras:
-        out += [l[1], l[2]] if l else [None, None]
-    return tuple(out)
-
-
 def eff_weight(lin):
     """THE accessor of every kernel call site for a projection's weight: `lin.weight` of a plain nn.Linear (the same tensor as
     before adapters existed), W_eff of a LoraLinear."""
@@ -156,11 +148,13 @@ def eff_weight(lin):
     return lin.weight
 
 
-def lora_of(lin):
-    """(scaling, lora_A, lora_B) of a LoraLinear, None for a plain nn.Linear."""
-    if type(lin) is LoraLinear:
-        return (lin.scaling, lin.lora_A, lin.lora_B)
-    return None
+def lora_args(*lins):
+    """The trailing `lora, *ab` arguments of a layer Function (autograd.py) for its projections `lins`: the tuple of scalings, then
+    lora_A, lora_B of each projection (None in every place of a plain nn.Linear); nothing when no projection is adapted."""
+    ad = [(l.scaling, l.lora_A, l.lora_B) if type(l) is LoraLinear else (None, None, None) for l in lins]
+    if all(s is None for s, _, _ in ad):
+        return ()
+    return (tuple(s for s, _, _ in ad),) + tuple(t for _, A, B in ad for t in (A, B))
 
 
 _ALLOWED_MODULE_TYPES = set()      # filled on first use (assert_plain_tree)
@@ -268,11 +262,9 @@ class EarthAttention3D(nn.Module):
         m = None if mask is None else mask.detach().to(device=x.device, dtype=torch.float32).contiguous()
         with torch.cuda.device(x.device):
             if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-                lora = (lora_of(self.linear1), lora_of(self.linear2))
                 y = AttentionWindowsFn.apply(xw, eff_weight(self.linear1), self.linear1.bias, eff_weight(self.linear2),
                                              self.linear2.bias, self.earth_specific_bias, m,
-                                             (n_lon, self.type_of_windows, self.head_number),
-                                             *(_lora_args(lora) if any(lora) else ()))
+                                             (n_lon, self.type_of_windows, self.head_number), *lora_args(self.linear1, self.linear2))
             else:
                 qkv = ops.linear(xw, eff_weight(self.linear1), self.linear1.bias)
                 o = ops.attention_windows(qkv, self.earth_specific_bias[0], m, n_lon, self.type_of_windows, self.head_number)

@@ -56,21 +56,46 @@ def test_earth_attention3d_forward_on_windows(P, golden_dir, C, roll):
         assert ((y2.cpu() - ref2).abs().max() / ref2.abs().max()).item() < 1e-4
 
 
+def _adapt(P, root, parent, names, seed):
+    """Swap parent.<name> for a LoraLinear (r = 16, alpha = 32) with random non-zero A / B; freeze every parameter of `root` but
+    the adapters."""
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    for n in names:
+        lin = P.layers.LoraLinear.from_linear(getattr(parent, n), 16, 32)
+        with torch.no_grad():
+            lin.lora_A.copy_(torch.randn(lin.lora_A.shape, generator=g) * 0.05)
+            lin.lora_B.copy_(torch.randn(lin.lora_B.shape, generator=g) * 0.05)
+        setattr(parent, n, lin)
+    for k, q in root.named_parameters():
+        q.requires_grad_(k.endswith(("lora_A", "lora_B")))
+
+
+@pytest.mark.parametrize("adapted", [False, True], ids=["base", "lora"])
 @pytest.mark.parametrize("C,roll", [(192, True), (384, False)])
-def test_earth_attention3d_module_backward(P, C, roll):
+def test_earth_attention3d_module_backward(P, C, roll, adapted):
     """The module on its own is differentiable like the reference's (layers.py:360-421 under autograd): gradients of the input
-    windows and of all five parameters == torch autograd over the oracle's restatement."""
+    windows and of all five parameters == torch autograd over the oracle's restatement.  Adapted (LoRA on linear1 / linear2, the
+    base frozen): dx, dA, dB == that autograd with W_eff = W + s B A built under it; the frozen base tensors get no gradient."""
     st = cases.STAGES[C]
     blk = P.layers.EarthSpecificBlock(C, 0.0, st["heads"], device="cuda").cuda().eval()
     pre = cases.block_prefix(C, roll)
     blk.load_state_dict({k: synth.synth_param(pre + k, s, "cuda") for k, s in cases.block_param_shapes(C).items()})
     att = blk.attention
+    lins = ("linear1", "linear2")
+    if adapted:
+        _adapt(P, blk, att, lins, C + int(roll))
     xw = cases.attention_window_input(C, 2, "cuda").requires_grad_(True)
     mask = blk.gen_mask(torch.zeros(1, st["Z"], st["H"] + 5, 24, C, device="cuda")) if roll else None
     y = att(xw, mask)
     cot = cases.cotangent("attn_windows", y.shape, "cuda")
     (y * cot).sum().backward()
     p = {k: v.requires_grad_(True) for k, v in cases.block_params(C, roll).items()}
+    ab = {}
+    if adapted:
+        for n in lins:
+            mod = getattr(att, n)
+            ab[n] = A, B = tuple(t.detach().cpu().requires_grad_(True) for t in (mod.lora_A, mod.lora_B))
+            p[pre + f"attention.{n}.weight"] = p[pre + f"attention.{n}.weight"] + mod.scaling * (B @ A)
     xr = xw.detach().cpu().requires_grad_(True)
     names = ("attention.linear1.weight", "attention.linear1.bias", "attention.linear2.weight", "attention.linear2.bias",
              "attention.earth_specific_bias")
@@ -78,25 +103,50 @@ def test_earth_attention3d_module_backward(P, C, roll):
     (ref * cot.cpu()).sum().backward()
     rel = lambda a, b: ((a.detach().cpu() - b).abs().max() / b.abs().max()).item()
     assert rel(y, ref.detach()) < 1e-4 and rel(xw.grad, xr.grad) < 1e-4
+    if adapted:
+        for n, (A, B) in ab.items():
+            mod = getattr(att, n)
+            assert rel(mod.lora_A.grad, A.grad) < 1e-4 and rel(mod.lora_B.grad, B.grad) < 1e-4, n
+        for k, q in blk.named_parameters():
+            if not k.endswith(("lora_A", "lora_B")):
+                assert q.grad is None, k                                         # frozen base tensors: nothing returned
+        return
     for n in names:
         q = dict(blk.named_parameters())[n]
         assert q.grad is not None and rel(q.grad, p[pre + n].grad) < 1e-4, n
 
 
-def test_mlp_module_backward(P):
-    """`blk.linear(x)` (Mlp.forward on its own, reference layers.py:264-270) under autograd == torch on the same weights."""
+@pytest.mark.parametrize("adapted", [False, True], ids=["base", "lora"])
+def test_mlp_module_backward(P, adapted):
+    """`blk.linear(x)` (Mlp.forward on its own, reference layers.py:264-270) under autograd == torch on the same weights.  Adapted
+    (LoRA on both projections, the base frozen): dx, dA, dB == torch with W_eff = W + s B A built under autograd; the frozen base
+    tensors get no gradient."""
     C = 192
     m = P.layers.Mlp(C, 0).cuda()
+    if adapted:
+        _adapt(P, m, m, ("linear1", "linear2"), 7)
     x = synth.uniform((3, 50, C), 5, 1.5).cuda().requires_grad_(True)
     y = m(x)
     cot = synth.uniform(tuple(y.shape), 6).cuda()
     (y * cot).sum().backward()
     xr = x.detach().clone().requires_grad_(True)
     w1, b1, w2, b2 = (t.detach().clone().requires_grad_(True) for t in (m.linear1.weight, m.linear1.bias, m.linear2.weight, m.linear2.bias))
-    ref = torch.nn.functional.gelu(xr @ w1.t() + b1) @ w2.t() + b2
+    we1, we2 = w1, w2
+    if adapted:
+        ab = [tuple(t.detach().clone().requires_grad_(True) for t in (lin.lora_A, lin.lora_B)) for lin in (m.linear1, m.linear2)]
+        we1 = w1 + m.linear1.scaling * (ab[0][1] @ ab[0][0])
+        we2 = w2 + m.linear2.scaling * (ab[1][1] @ ab[1][0])
+    ref = torch.nn.functional.gelu(xr @ we1.t() + b1) @ we2.t() + b2
     (ref * cot).sum().backward()
     rel = lambda a, b: ((a - b).abs().max() / b.abs().max()).item()
     assert rel(y.detach(), ref.detach()) < 1e-4 and rel(x.grad, xr.grad) < 1e-4
+    if adapted:
+        for lin, (A, B) in zip((m.linear1, m.linear2), ab):
+            assert rel(lin.lora_A.grad, A.grad) < 1e-4 and rel(lin.lora_B.grad, B.grad) < 1e-4
+        for k, q in m.named_parameters():
+            if not k.endswith(("lora_A", "lora_B")):
+                assert q.grad is None, k                                         # frozen base tensors: nothing returned
+        return
     for q, r in ((m.linear1.weight, w1), (m.linear1.bias, b1), (m.linear2.weight, w2), (m.linear2.bias, b2)):
         assert rel(q.grad, r.grad) < 1e-4
 
