@@ -26,15 +26,16 @@ def _adapters(ctx, ab, n):
     return tuple(None if s is None else (s, ab[2 * i], ab[2 * i + 1], p + 2 * i) for i, s in enumerate(ctx.lora))
 
 
-def _wgrad(ctx, dy, x, w, b=None, ad=None, db_into=None, shape=None):
+def _wgrad(ctx, dy, x, w, b=None, ad=None, db_into=None, shape=None, op=ops.linear_wgrad):
     """Parameter gradients of one projection y = x @ W_eff^T (+ b), W_eff = W (+ s B A when adapted).  w / b: input positions of
-    the base weight and bias (b None: no bias); ad: None or (s, A, B, input position of A), from _adapters.  ops.linear_wgrad runs
-    only if W or b asks for a gradient, ops.lora_wgrad only if A or B does -> (dW (in `shape` if given), db, dA, dB), None where
-    not computed.  Both run at the same point of the backward, so an adapter keeps no activation gradient alive for longer."""
+    the base weight and bias (b None: no bias); ad: None or (s, A, B, input position of A), from _adapters.  `op` (ops.linear_wgrad,
+    or ops_bf16.linear_wgrad for the bf16 Functions) runs only if W or b asks for a gradient, ops.lora_wgrad only if A or B does
+    -> (dW (in `shape` if given), db, dA, dB), None where not computed.  Both run at the same point of the backward, so an adapter
+    keeps no activation gradient alive for longer."""
     need = ctx.needs_input_grad
     dw = db = da = dbb = None
     if need[w] or (b is not None and need[b]):
-        dw, db = ops.linear_wgrad(dy, x, want_bias=b is not None, db_into=db_into)
+        dw, db = op(dy, x, want_bias=b is not None, db_into=db_into)
         if shape is not None:
             dw = dw.reshape(shape)
     if ad is not None and (need[ad[3]] or need[ad[3] + 1]):

@@ -1,11 +1,17 @@
 """bf16 mixed-precision training path (BASELINE configs[2]): fp32 master parameters and fp32 parameter gradients,
 bf16 weight shadows / activations / activation gradients, fp32 LayerNorm + softmax + accumulation.
 
-Same kernel sequence as autograd.py on the bf16 entry points; saved activations are bf16 (32 GB instead of 64 GB)."""
+Same kernel sequence and gradient contract as autograd.py on the bf16 entry points (parameters saved, weight gradients only
+where asked, returns through _keep_needed); saved activations are bf16 (32 GB instead of 64 GB)."""
+import functools
+
 import torch
 
 from . import ops
 from . import ops_bf16 as ob
+from .autograd import _keep_needed, _wgrad as _wgrad_f32
+
+_wgrad = functools.partial(_wgrad_f32, op=ob.linear_wgrad)
 
 
 # MLP branch of the training forward (mode 1, C = 192 / 384 with contiguous rows): ONE launch that keeps the hidden activation on
@@ -16,6 +22,9 @@ from . import ops_bf16 as ob
 # removed in round 4; so were the QKV-inside-attention training forward, +0.3 ms, and weight gradients on a second stream,
 # +0.5 ms.  DESIGN.md keeps the numbers.)
 class EarthBlockFnBF16(torch.autograd.Function):
+    _INPUTS = ("x", "n1w", "n1b", "n2w", "n2b", "m1w", "m1b", "m2w", "m2b", "esb", "a1w", "a1b", "a2w", "a2b", "geom", "s1", "s2",
+               "sh", "dst")
+
     @staticmethod
     def forward(ctx, x, n1w, n1b, n2w, n2b, m1w, m1b, m2w, m2b, esb, a1w, a1b, a2w, a2b, geom, s1, s2, sh, dst=None):
         # dst: optional 1-tuple holding a (N, C) row-strided view the block writes its result into (a half of the skip-concat
@@ -23,8 +32,7 @@ class EarthBlockFnBF16(torch.autograd.Function):
         out = dst[0] if dst else None
         Z, H, W, heads, shifted = geom
         ctx.geom, ctx.s1, ctx.s2, ctx.sh = geom, s1, s2, sh
-        ctx.params = (n1w, n2w, m1w, m2w, esb, a1w, a1b, a2w, m1b)
-        saved = [x]
+        saved = [x, n1w, n2w, m1w, m2w, esb, a1w, a1b, a2w]
         x1 = x
         if s1 != 0.0:
             qkv = ob.linear(x, sh.get(a1w), a1b)
@@ -57,15 +65,14 @@ class EarthBlockFnBF16(torch.autograd.Function):
         # (every atomically accumulated gradient buffer of the whole backward pass comes out of ONE zero fill: ops._zeros)
         Z, H, W, heads, shifted = ctx.geom
         s1, s2, sh = ctx.s1, ctx.s2, ctx.sh
-        n1w, n2w, m1w, m2w, esb, a1w, a1b, a2w, m1b = ctx.params
-        sv = list(ctx.saved_tensors)
-        x, rest = sv[0], sv[1:]
+        x, n1w, n2w, m1w, m2w, esb, a1w, a1b, a2w, *rest = ctx.saved_tensors
+        need = dict(zip(EarthBlockFnBF16._INPUTS, ctx.needs_input_grad))
+        g = {}
         if s1 != 0.0:
             qkv, o, lse, y = rest[:4]
             rest = rest[4:]
-        g = {k: None for k in ("n1w", "n1b", "n2w", "n2b", "m1w", "m1b", "m2w", "m2b", "esb", "a1w", "a1b", "a2w", "a2b")}
-        dqb_pad = None
         dx1 = dout
+        # _wgrad's input positions: m1w 5, m1b 6, m2w 7, m2b 8, a1w 10, a1b 11, a2w 12, a2b 13
         if s2 != 0.0:
             mode = ctx.mlp_mode
             if mode == 1:
@@ -74,12 +81,12 @@ class EarthBlockFnBF16(torch.autograd.Function):
                 x1, pre, h, m = rest
             dm, g["n2w"], g["n2b"] = ob.ln_residual_bwd(dout, m, n2w, s2)
             if mode == 1:                  # h = GELU(pre) comes out of the data-gradient GEMM's epilogue (never stored by the forward)
-                dpre, h = ob.linear_gelu_bwd(dm, sh.get_t(m2w), pre)
+                dpre, h = ob.linear_gelu_bwd(dm, sh.get_t(m2w), pre, want_h=need["m2w"] or need["m2b"])
             else:
                 dpre = ob.linear(dm, sh.get_t(m2w), None, act=ob.ACT_GELU_BWD, aux=pre)
-            g["m2w"], g["m2b"] = ob.linear_wgrad(dm, h)
+            g["m2w"], g["m2b"] = _wgrad(ctx, dm, h, 7, 8)[:2]
             del dm, h
-            g["m1w"], g["m1b"] = ob.linear_wgrad(dpre, x1)
+            g["m1w"], g["m1b"] = _wgrad(ctx, dpre, x1, 5, 6)[:2]
             if dout.is_contiguous():      # residual gradient added in the GEMM epilogue (no extra pass over N x C)
                 dx1 = ob.linear(dpre, sh.get_t(m1w), act=ob.ACT_ADD, aux=dout)
             else:
@@ -89,19 +96,16 @@ class EarthBlockFnBF16(torch.autograd.Function):
         dx = dx1
         if s1 != 0.0:
             dy, g["n1w"], g["n1b"] = ob.ln_residual_bwd(dx1, y, n1w, s1)
-            g["a2w"], g["a2b"] = ob.linear_wgrad(dy, o)
+            g["a2w"], g["a2b"] = _wgrad(ctx, dy, o, 12, 13)[:2]
             do = ob.linear(dy, sh.get_t(a2w))
             del dy
+            # (the bias-table gradient goes straight into the DP flat buffer)
             dqkv, dqb_pad, desb = ob.window_attention_bwd(qkv, sh.get(a1b), sh.get(esb), o, lse, do, Z, H, W, heads, shifted,
-                                                          desb_out=ops.grad_slot(esb))       # straight into the DP flat buffer
+                                                          desb_out=ops.grad_slot(esb) if need["esb"] else None)
             del do
             g["esb"] = desb.unsqueeze(0)
-            # linear1's bias gradient = column sums of dqkv (real tokens) + the pad-slot term the attention backward already
-            # accumulated into dqb_pad: the weight-gradient kernel adds its sums into that buffer
-            fuse_db = dqb_pad is not None and dqb_pad.is_contiguous()
-            g["a1w"], g["a1b"] = ob.linear_wgrad(dqkv, x, db_into=dqb_pad if fuse_db else None)
-            if fuse_db:
-                dqb_pad = None
+            # linear1's bias gradient = column sums of dqkv + the pad-slot term already in dqb_pad: the kernel adds into that buffer
+            g["a1w"], g["a1b"] = _wgrad(ctx, dqkv, x, 10, 11, db_into=dqb_pad)[:2]
             if dx1.is_contiguous():
                 dx = ob.linear(dqkv, sh.get_t(a1w), act=ob.ACT_ADD, aux=dx1)
             else:
@@ -109,12 +113,12 @@ class EarthBlockFnBF16(torch.autograd.Function):
                 dx += dx1
         elif not dx.is_contiguous():
             dx = dx.contiguous()
-        if dqb_pad is not None:
-            g["a1b"] += dqb_pad
-        ops.fill_dropped_grads(g, {"n1w": n1w, "n1b": n1w, "n2w": n2w, "n2b": n2w, "m1w": m1w, "m1b": m1b, "m2w": m2w, "m2b": n2w,
-                                   "esb": esb, "a1w": a1w, "a1b": a1b, "a2w": a2w, "a2b": n1w})
-        return (dx, g["n1w"], g["n1b"], g["n2w"], g["n2b"], g["m1w"], g["m1b"], g["m2w"], g["m2b"], g["esb"],
-                g["a1w"], g["a1b"], g["a2w"], g["a2b"], None, None, None, None, None)
+        g["x"] = dx
+        if s1 == 0.0 or s2 == 0.0:        # a dropped branch: only what asks for a gradient is filled (frozen parameters get nothing)
+            like = {"n1w": n1w, "n1b": n1w, "n2w": n2w, "n2b": n2w, "m1w": m1w, "m1b": m1w[:, 0], "m2w": m2w, "m2b": n2w,
+                    "esb": esb, "a1w": a1w, "a1b": a1b, "a2w": a2w, "a2b": n1w}
+            ops.fill_dropped_grads(g, {k: t for k, t in like.items() if need[k]})
+        return _keep_needed(ctx, [g.get(k) for k in EarthBlockFnBF16._INPUTS])
 
 
 class PatchEmbedFnBF16(torch.autograd.Function):
@@ -125,33 +129,29 @@ class PatchEmbedFnBF16(torch.autograd.Function):
         x = torch.empty((n_s + a_u.shape[0], cw.shape[0]), dtype=torch.bfloat16, device=inp.device)
         ob.linear(a_s, sh.get(sw, pad_k=128), sb, out=x[:n_s])
         ob.linear(a_u, sh.get(cw), cb, out=x[n_s:])
-        ctx.save_for_backward(a_s, a_u, s_std, u_std)
-        ctx.shapes, ctx.geom = (cw.shape, sw.shape), (inp.shape[-2], inp.shape[-1], bool(levels_reversed))
-        ctx.sh, ctx.params = sh, (cw, sw)
+        ctx.save_for_backward(a_s, a_u, cw, sw, s_std, u_std)
+        ctx.geom, ctx.sh = (inp.shape[-2], inp.shape[-1], bool(levels_reversed)), sh
         return x
 
     @staticmethod
     def backward(ctx, dx):
-        a_s, a_u, s_std, u_std = ctx.saved_tensors
+        a_s, a_u, cw, sw, s_std, u_std = ctx.saved_tensors
         n_s = a_s.shape[0]
         need = ctx.needs_input_grad
-        dsw = dsb = dcw = dcb = None
-        if any(need[:4]):
-            dsw, dsb = ob.linear_wgrad(dx[:n_s], a_s)                 # (192, 128): columns 112.. are padding
-            dcw, dcb = ob.linear_wgrad(dx[n_s:], a_u)
-            k_s = ctx.shapes[1][1]
-            dcw, dsw = dcw.reshape(ctx.shapes[0]), dsw[:, :k_s].reshape(ctx.shapes[1])
+        dsw, dsb = _wgrad(ctx, dx[:n_s], a_s, 2, 3)[:2]
+        if dsw is not None:
+            dsw = dsw[:, :sw.shape[1]].reshape(sw.shape)                # (192, 128): columns 112.. are padding
+        dcw, dcb = _wgrad(ctx, dx[n_s:], a_u, 0, 1, shape=cw.shape)[:2]
         d_in = d_in_s = None
         if need[4] or need[5]:
             # the raw fields asked for their gradient (reference layers.py:40-93 is plain autograd): dA for the columns with a field
             # behind them (bf16 operands, fp32 result), then the fp32 scatter adjoint of the gather, divided by the std
             LAT, LON, rev = ctx.geom
-            cw, sw = ctx.params
             dx = dx.contiguous()
             da_s = ob.linear(dx[:n_s], ctx.sh.get_t(sw)[:64].contiguous(), out_dtype=torch.float32)
             da_u = ob.linear(dx[n_s:], ctx.sh.get_t(cw)[:160].contiguous(), out_dtype=torch.float32)
             d_in, d_in_s = ops.patch_embed_gather_bwd(da_s, da_u, s_std, u_std, LAT, LON, rev)
-        return (dcw, dcb, dsw, dsb, d_in if need[4] else None, d_in_s if need[5] else None) + (None,) * 8
+        return _keep_needed(ctx, (dcw, dcb, dsw, dsb, d_in, d_in_s))
 
 
 class DownSampleFnBF16(torch.autograd.Function):
@@ -162,25 +162,24 @@ class DownSampleFnBF16(torch.autograd.Function):
         # the backward below sums the two inside the down-sampling kernel (no elementwise add over the 200 MB)
         Z, H, W = geom
         g = ob.downsample_ln(x, nw, nb, Z, H, W)
-        ctx.save_for_backward(x, g)
-        ctx.geom, ctx.sh, ctx.params, ctx.skip_grad = geom, sh, (lw, nw), skip_grad
+        ctx.save_for_backward(x, g, lw, nw)
+        ctx.geom, ctx.sh, ctx.skip_grad = geom, sh, skip_grad
         if skip_grad is not None:
             skip_grad[1] = True                  # armed: this node's backward will consume the slot
         return ob.linear(g, sh.get(lw))
 
     @staticmethod
     def backward(ctx, dout):
-        x, g = ctx.saved_tensors
-        lw, nw = ctx.params
+        x, g, lw, nw = ctx.saved_tensors
         Z, H, W = ctx.geom
         dout = dout.contiguous()
-        dlw, _ = ob.linear_wgrad(dout, g, want_bias=False)
+        dlw = _wgrad(ctx, dout, g, 1)[0]
         dg = ob.linear(dout, ctx.sh.get_t(lw))
         add = None
         if ctx.skip_grad is not None:
             add, ctx.skip_grad[0] = ctx.skip_grad[0], None
         dx, dnw, dnb = ob.downsample_ln_bwd(dg, x, nw, Z, H, W, add=add)
-        return dx, dlw, dnw, dnb, None, None, None
+        return _keep_needed(ctx, (dx, dlw, dnw, dnb))
 
 
 class UpSampleFnBF16(torch.autograd.Function):
@@ -189,22 +188,21 @@ class UpSampleFnBF16(torch.autograd.Function):
         Z, H2, W2, H = geom
         y = ob.linear(x, sh.get(l1w))
         g = ob.upsample_ln(y, nw, nb, Z, H2, W2, H)
-        ctx.save_for_backward(x, y, g)
-        ctx.geom, ctx.sh, ctx.params = geom, sh, (l1w, l2w, nw)
+        ctx.save_for_backward(x, y, g, l1w, l2w, nw)
+        ctx.geom, ctx.sh = geom, sh
         return ob.linear(g, sh.get(l2w))
 
     @staticmethod
     def backward(ctx, dout):
-        x, y, g = ctx.saved_tensors
-        l1w, l2w, nw = ctx.params
+        x, y, g, l1w, l2w, nw = ctx.saved_tensors
         Z, H2, W2, H = ctx.geom
         dout = dout.contiguous()
-        dl2w, _ = ob.linear_wgrad(dout, g, want_bias=False)
+        dl2w = _wgrad(ctx, dout, g, 2)[0]
         dg = ob.linear(dout, ctx.sh.get_t(l2w))
         dy, dnw, dnb = ob.upsample_ln_bwd(dg, y, nw, Z, H2, W2, H)
-        dl1w, _ = ob.linear_wgrad(dy, x, want_bias=False)
+        dl1w = _wgrad(ctx, dy, x, 1)[0]
         dx = ob.linear(dy, ctx.sh.get_t(l1w))
-        return dx, dl1w, dl2w, dnw, dnb, None, None
+        return _keep_needed(ctx, (dx, dl1w, dl2w, dnw, dnb))
 
 
 class PatchRecoverFnBF16(torch.autograd.Function):
@@ -218,24 +216,22 @@ class PatchRecoverFnBF16(torch.autograd.Function):
         ctx.skip_grad = skip_grad
         n_s, LAT, LON = geom
         N, C = skip.shape
-        adjacent = (skip.stride() == (2 * C, 1) and x.stride() == (2 * C, 1) and x.data_ptr() == skip.data_ptr() + 2 * C
-                    and skip.untyped_storage().data_ptr() == x.untyped_storage().data_ptr())
-        cat = torch.as_strided(skip, (N, 2 * C), (2 * C, 1), skip.storage_offset()) if adjacent else torch.cat((skip, x), dim=-1)
+        assert skip.stride() == (2 * C, 1) and x.stride() == (2 * C, 1) and x.data_ptr() == skip.data_ptr() + 2 * C
+        cat = torch.as_strided(skip, (N, 2 * C), (2 * C, 1), skip.storage_offset())
         y_s = ob.linear(cat[:n_s], sh.get(sw), sb, out_dtype=torch.float32)
         y_u = ob.linear(cat[n_s:], sh.get(cw), cb, out_dtype=torch.float32)
-        ctx.save_for_backward(cat)
-        ctx.geom, ctx.sh, ctx.params = geom, sh, (cw, sw)
+        ctx.save_for_backward(cat, cw, sw)
+        ctx.geom, ctx.sh = geom, sh
         return ops.patch_recover_scatter(y_u, y_s, LAT, LON)
 
     @staticmethod
     def backward(ctx, d_out, d_out_s):
-        (cat,) = ctx.saved_tensors
-        cw, sw = ctx.params
+        cat, cw, sw = ctx.saved_tensors
         n_s, LAT, LON = ctx.geom
         C = cat.shape[1] // 2
         dy_u, dy_s = ob.patch_recover_gather_bwd(d_out.contiguous(), d_out_s.contiguous())
-        dcw, dcb = ob.linear_wgrad(dy_u, cat[n_s:])
-        dsw, dsb = ob.linear_wgrad(dy_s, cat[:n_s])
+        dcw, dcb = _wgrad(ctx, dy_u, cat[n_s:], 2, 3, shape=cw.shape)[:2]
+        dsw, dsb = _wgrad(ctx, dy_s, cat[:n_s], 4, 5, shape=sw.shape)[:2]
         wt_s, wt_u = ctx.sh.get_t(sw), ctx.sh.get_t(cw)                    # (2C, 64), (2C, 160): rows = input channels
         d_skip = torch.empty((cat.shape[0], C), dtype=cat.dtype, device=cat.device)
         d_x = torch.empty_like(d_skip)
@@ -248,7 +244,7 @@ class PatchRecoverFnBF16(torch.autograd.Function):
             # (if autograd pruned that node -- `torch.autograd.grad(loss, inputs=[layer-3 parameters])` -- nothing consumes the
             # slot: it is emptied when this backward pass ends instead of pinning 200-400 MB until the next forward)
             torch.autograd.Variable._execution_engine.queue_callback(lambda sg=sg: sg.__setitem__(0, None))
-        return d_skip, d_x, dcw.reshape(cw.shape), dcb, dsw.reshape(sw.shape), dsb, None, None, None
+        return _keep_needed(ctx, (d_skip, d_x, dcw, dcb, dsw, dsb))
 
 
 def forward_train(model, inp, inp_surface, statistics, maps, const_h, levels_reversed=False):

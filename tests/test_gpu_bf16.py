@@ -487,6 +487,111 @@ def test_block_backward_bf16_vs_fp32(P, golden_dir):
     assert dxe < 2e-2 and worst[0] < 2e-2
 
 
+# Frozen-subset gradients against the all-trainable run, as the relative max-difference per tensor (rel_err).  Not bit for bit:
+# the LayerNorm-affine and bias gradients accumulate with fp32 atomics in a run-dependent order.  Each bound is 4x the worst
+# per-tensor difference between two all-trainable runs of the test's own configuration on commit d96eaea (where the frozen runs
+# launch the same kernels as the all-trainable one), and never below 1e-6 (accumulation-order noise of fp32 sums).
+FROZEN_BLOCK_TOL = max(4 * 1.076e-6, 1e-6)     # B1, measured on d96eaea: 1.076e-6 (norm1.weight; dx and 13 parameters)
+FROZEN_MODEL_TOL = max(4 * 7.245e-7, 1e-6)     # B2, measured on d96eaea: 7.245e-7 (_output_layer.conv_surface.weight)
+
+
+def _bf16_block(P):
+    """The block of test_block_backward_bf16_vs_fp32 (C = 192, roll, W = 24, eval()), its bf16 input, cotangent and geometry."""
+    C, roll, W = 192, True, 24
+    st = cases.STAGES[C]
+    blk = P.layers.EarthSpecificBlock(C, 0.0, st["heads"], device="cuda").cuda().eval()
+    pre = cases.block_prefix(C, roll)
+    blk.load_state_dict({k: synth.synth_param(pre + k, s, "cuda") for k, s in cases.block_param_shapes(C).items()})
+    x = cases.block_input(C, W, "cuda")
+    cot = cases.cotangent(f"block_{C}_{int(roll)}", x.shape, "cuda")[0]
+    return blk, x[0].to(BF), cot, (st["Z"], st["H"], W, st["heads"], roll)
+
+
+def _bf16_block_apply(blk, x, geom, sh):
+    from pangu_pytorch_amd import autograd_bf16 as AB
+    att = blk.attention
+    return AB.EarthBlockFnBF16.apply(x, blk.norm1.weight, blk.norm1.bias, blk.norm2.weight, blk.norm2.bias,
+                                     blk.linear.linear1.weight, blk.linear.linear1.bias, blk.linear.linear2.weight,
+                                     blk.linear.linear2.bias, att.earth_specific_bias, att.linear1.weight, att.linear1.bias,
+                                     att.linear2.weight, att.linear2.bias, geom, 1.0, 1.0, sh)
+
+
+def test_block_backward_bf16_frozen_subsets(P):
+    """EarthBlockFnBF16 with all parameters trainable, only `linear.*` trainable, and all frozen (x asking for a gradient): frozen
+    parameters get None, the backward launches one weight-gradient GEMM per projection whose weight or bias trains (4, 2, 0),
+    and dx and the trainable gradients match the all-trainable run within FROZEN_BLOCK_TOL."""
+    from pangu_pytorch_amd import fused_bf16
+    blk, xb, cot, geom = _bf16_block(P)
+    sh = fused_bf16.WeightShadow()
+    runs = {}
+    for name, trains, launches in (("all", lambda k: True, 4), ("linear", lambda k: k.startswith("linear."), 2),
+                                   ("none", lambda k: False, 0)):
+        for k, p in blk.named_parameters():
+            p.requires_grad_(trains(k))
+            p.grad = None
+        x = xb.clone().requires_grad_(True)
+        loss = (_bf16_block_apply(blk, x, geom, sh).float() * cot).sum()
+        P.ops.timing_start()
+        loss.backward()
+        n = P.ops.timing_stop("wgrad_bf16")[2]
+        grads = {"x": x.grad}
+        for k, p in blk.named_parameters():
+            if trains(k):
+                grads[k] = p.grad
+            else:
+                assert p.grad is None, (name, k)
+        assert all(g is not None for g in grads.values()), name
+        runs[name] = grads
+        errs = {k: rel_err(g, runs["all"][k]) for k, g in grads.items()}
+        print(f"{name}: wgrad_bf16 launches {n}; worst rel max-difference to the all-trainable run {max(errs.values()):.2e}")
+        assert n == launches, (name, n)
+        assert max(errs.values()) <= FROZEN_BLOCK_TOL, (name, errs)
+
+
+@pytest.mark.parametrize("param", ["norm2.weight", "attention.linear2.weight"])
+def test_bf16_inplace_parameter_edit_before_backward_raises(P, param):
+    """A parameter edited in place between the bf16 block's forward and its backward: the backward must refuse (as the fp32 path
+    does) instead of computing gradients from the new weights and bf16 shadows re-made from them."""
+    from pangu_pytorch_amd import fused_bf16
+    blk, xb, cot, geom = _bf16_block(P)
+    loss = (_bf16_block_apply(blk, xb.clone().requires_grad_(True), geom, fused_bf16.WeightShadow()).float() * cot).sum()
+    with torch.no_grad():
+        blk.get_parameter(param).mul_(1.5)
+    with pytest.raises(RuntimeError, match="modified by an inplace operation"):
+        loss.backward()
+
+
+def test_partially_frozen_finetune_bf16(P):
+    """bf16 counterpart of test_gpu_hardening.py::test_partially_frozen_finetune_f32: the whole model with only `_output_layer`
+    trainable -- the frozen parameters get None, the trainable gradients match the all-trainable run within FROZEN_MODEL_TOL."""
+    from pangu_pytorch_amd import train
+    trainable = "_output_layer"
+    m = P.PanguModel(device="cuda").cuda().eval()
+    m.load_state_dict(synth.fill_state_dict(cases.model_param_shapes(), "cuda"))
+    m.set_compute_dtype(BF)
+    inp, inp_s, stats, maps, const_h = cases.model_inputs("cuda")
+    tgt, tgt_s = cases.model_targets("cuda")
+    out, out_s = m(inp, inp_s, stats, maps, const_h)
+    train.weighted_l1_loss(out, out_s, tgt, tgt_s).backward()
+    ref = {k: p.grad.clone() for k, p in m.named_parameters() if k.startswith(trainable)}
+    assert ref
+    m.zero_grad(set_to_none=True)
+    del out, out_s
+    for k, p in m.named_parameters():
+        p.requires_grad_(k.startswith(trainable))
+    out, out_s = m(inp, inp_s, stats, maps, const_h)
+    train.weighted_l1_loss(out, out_s, tgt, tgt_s).backward()
+    errs = {}
+    for k, p in m.named_parameters():
+        if k.startswith(trainable):
+            assert p.grad is not None, k
+            errs[k] = rel_err(p.grad, ref[k])
+        else:
+            assert p.grad is None, k
+    print(f"bf16 partially frozen: worst rel max-difference to the all-trainable run {max(errs.values()):.2e}")
+    assert max(errs.values()) <= FROZEN_MODEL_TOL, errs
+
+
 def test_full_training_step_bf16(P):
     """Whole bf16 training step runs, loss close to the fp32 step's, gradients finite and close in rel-L2."""
     from pangu_pytorch_amd import train
