@@ -6,15 +6,48 @@ activations and needs no block re-computation (the reference re-runs every block
 models/layers.py:115-119).
 
 Gradient of a projection y = a @ W^T + b:   da = dy @ W  (the forward GEMM with W^T),  dW, db = wgrad(dy, a).
+
+The layer Functions of the whole-model training step serve both precisions.  Their `sh` input is None for fp32, or the model's
+fused_bf16.WeightShadow for bf16 mixed precision (BASELINE configs[2]): fp32 master parameters and parameter gradients, bf16
+weight shadows / activations / activation gradients (32 GB saved instead of 64 GB), fp32 LayerNorm + softmax + accumulation.
 """
 import torch
 
 from . import ops
+from . import ops_bf16 as ob
 
 
 def _wt(w):
     """(out,in[,1]) weight -> contiguous (in,out): the `W` operand of ops.linear for the input gradient."""
     return w.reshape(w.shape[0], -1).t().contiguous()
+
+
+class _F32:
+    """fp32: the kernels of `ops`, reading the parameters themselves."""
+    k, dtype = ops, torch.float32
+    f32_out = {}                                            # ops.linear writes fp32 as it is
+    w = staticmethod(lambda p: p)                           # forward GEMM operand
+    wt = staticmethod(_wt)                                  # input-gradient GEMM operand
+    table = staticmethod(lambda p: p[0] if p.dim() == 5 else p)      # attention's bias table / QKV bias
+
+
+class _BF16:
+    """bf16: the kernels of `ops_bf16`, reading the bf16 images that the WeightShadow `sh` keeps of the fp32 parameters."""
+    k, dtype = ob, torch.bfloat16
+    f32_out = {"out_dtype": torch.float32}                  # for the GEMMs whose result leaves the bf16 domain
+
+    def __init__(self, sh):
+        self.w, self.wt, self.table = sh.get, sh.get_t, sh.get
+
+
+def _precision(sh, lora=None):
+    """What separates the two precisions of a layer Function outside its explicit branches: kernel module `k`, operand accessors
+    `w` / `wt` / `table`, activation `dtype`, `f32_out`."""
+    if sh is None:
+        return _F32
+    if lora is not None:
+        raise RuntimeError("bf16 layer Functions take no LoRA adapters (PanguModel.forward refuses bf16 training with adapters)")
+    return _BF16(sh)
 
 
 def _adapters(ctx, ab, n):
@@ -26,16 +59,16 @@ def _adapters(ctx, ab, n):
     return tuple(None if s is None else (s, ab[2 * i], ab[2 * i + 1], p + 2 * i) for i, s in enumerate(ctx.lora))
 
 
-def _wgrad(ctx, dy, x, w, b=None, ad=None, db_into=None, shape=None, op=ops.linear_wgrad):
+def _wgrad(ctx, dy, x, w, b=None, ad=None, db_into=None, shape=None):
     """Parameter gradients of one projection y = x @ W_eff^T (+ b), W_eff = W (+ s B A when adapted).  w / b: input positions of
-    the base weight and bias (b None: no bias); ad: None or (s, A, B, input position of A), from _adapters.  `op` (ops.linear_wgrad,
-    or ops_bf16.linear_wgrad for the bf16 Functions) runs only if W or b asks for a gradient, ops.lora_wgrad only if A or B does
+    the base weight and bias (b None: no bias); ad: None or (s, A, B, input position of A), from _adapters.  linear_wgrad (of ctx.pr:
+    _precision) runs only if W or b asks for a gradient, ops.lora_wgrad only if A or B does
     -> (dW (in `shape` if given), db, dA, dB), None where not computed.  Both run at the same point of the backward, so an adapter
     keeps no activation gradient alive for longer."""
     need = ctx.needs_input_grad
     dw = db = da = dbb = None
     if need[w] or (b is not None and need[b]):
-        dw, db = op(dy, x, want_bias=b is not None, db_into=db_into)
+        dw, db = ctx.pr.k.linear_wgrad(dy, x, want_bias=b is not None, db_into=db_into)
         if shape is not None:
             dw = dw.reshape(shape)
     if ad is not None and (need[ad[3]] or need[ad[3] + 1]):
@@ -56,31 +89,45 @@ class EarthBlockFn(torch.autograd.Function):
 
     # the inputs in order; A / B of the adapted projections follow `lora` (the order of its scalings)
     _INPUTS = ("x", "n1w", "n1b", "n2w", "n2b", "m1w", "m1b", "m2w", "m2b", "esb", "a1w", "a1b", "a2w", "a2b", "geom", "s1", "s2",
-               "dst", "lora", "m1A", "m1B", "m2A", "m2B", "a1A", "a1B", "a2A", "a2B")
+               "dst", "sh", "lora", "m1A", "m1B", "m2A", "m2B", "a1A", "a1B", "a2A", "a2B")
 
     @staticmethod
-    def forward(ctx, x, n1w, n1b, n2w, n2b, m1w, m1b, m2w, m2b, esb, a1w, a1b, a2w, a2b, geom, s1, s2, dst=None, lora=None, *ab):
+    def forward(ctx, x, n1w, n1b, n2w, n2b, m1w, m1b, m2w, m2b, esb, a1w, a1b, a2w, a2b, geom, s1, s2, dst=None, sh=None, lora=None,
+                *ab):
         # dst: optional 1-tuple holding the (N, C) row-strided tensor the block writes its result into (one half of the
         # skip-concat buffer of reference pangu_model.py:81); wrapped so that autograd does not see a tensor argument.
         # lora: scalings of (linear.linear1, linear.linear2, attention.linear1, attention.linear2), None where not adapted, or None
         # without adapters (layers.lora_args); m1w / m2w / a1w / a2w are then the W_eff tensors and ab = (A, B) per linear
         out = dst[0] if dst else None
         Z, H, W, heads, shifted = geom
+        ctx.pr = pr = _precision(sh, lora)
+        K = pr.k
         ctx.geom, ctx.s1, ctx.s2, ctx.lora = geom, s1, s2, lora
         saved = [x, n1w, n2w, m1w, m2w, esb, a1w, a1b, a2w, *ab]
         x1 = x
         if s1 != 0.0:
-            qkv = ops.linear(x, a1w, a1b)
-            o, lse = ops.window_attention(qkv, a1b, esb[0], Z, H, W, heads, shifted, want_lse=True)
-            y = ops.linear(o, a2w, a2b)
+            qkv = K.linear(x, pr.w(a1w), a1b)
+            o, lse = K.window_attention(qkv, pr.table(a1b), pr.table(esb), Z, H, W, heads, shifted, want_lse=True)
+            y = K.linear(o, pr.w(a2w), a2b)
             # (a dropped MLP branch -- s2 == 0 -- makes x1 the block's result: written straight into `out`, no copy afterwards)
-            x1 = ops.ln_residual(y, x, n1w, n1b, branch_scale=s1, out=out if s2 == 0.0 else None)
+            x1 = K.ln_residual(y, x, n1w, n1b, branch_scale=s1, out=out if s2 == 0.0 else None)
             saved += [qkv, o, lse, y]
-        if s2 != 0.0:
+        # MLP branch of the bf16 training forward (mode 1, C = 192 / 384 with contiguous rows): ONE launch that keeps the hidden
+        # activation on chip and writes only what the backward needs (pre, m); the backward's data-gradient GEMM re-creates
+        # h = GELU(pre) for the W2 weight gradient.  Mode 0, what fp32, other widths and row-strided inputs take: three launches
+        # (MLP-up + GELU writing pre AND h, MLP-down, LayerNorm + residual), +2.3-3.1 ms per bf16 step where mode 1 applies.
+        # (Recomputing the MLP-up GEMM in the backward instead of saving `pre` -- the reference's answer to activation memory,
+        # layers.py:115-119 -- measured +2.7 ms per step and was removed in round 4; so were the QKV-inside-attention training
+        # forward, +0.3 ms, and weight gradients on a second stream, +0.5 ms.  DESIGN.md keeps the numbers.)
+        ctx.mlp_mode = mode = 1 if (sh is not None and x.shape[1] in (192, 384) and x1.is_contiguous()) else 0
+        if s2 != 0.0 and mode:
+            x2, pre, m = ob.mlp_ln_residual_train(x1, sh.get_mlp(m1w, m2w), m1b, m2b, n2w, n2b, branch_scale=s2, out=out)
+            saved += [x1, pre, m]
+        elif s2 != 0.0:
             pre = torch.empty((x.shape[0], m1w.shape[0]), dtype=x.dtype, device=x.device)
-            h = ops.linear(x1, m1w, m1b, act=ops.ACT_GELU, aux=pre)
-            m = ops.linear(h, m2w, m2b)
-            x2 = ops.ln_residual(m, x1, n2w, n2b, out=out, branch_scale=s2)
+            h = K.linear(x1, pr.w(m1w), m1b, act=ops.ACT_GELU, aux=pre)
+            m = K.linear(h, pr.w(m2w), m2b)
+            x2 = K.ln_residual(m, x1, n2w, n2b, out=out, branch_scale=s2)
             saved += [x1, pre, h, m]
         elif out is not None:
             if x1 is not out:
@@ -95,7 +142,8 @@ class EarthBlockFn(torch.autograd.Function):
     def backward(ctx, dout):
         # (every atomically accumulated gradient buffer of the whole backward pass comes out of ONE zero fill: ops._zeros)
         Z, H, W, heads, shifted = ctx.geom
-        s1, s2 = ctx.s1, ctx.s2
+        s1, s2, pr = ctx.s1, ctx.s2, ctx.pr
+        K = pr.k
         sv = ctx.saved_tensors
         x, n1w, n2w, m1w, m2w, esb, a1w, a1b, a2w = sv[:9]
         ab = sv[9:9 + 2 * len(ctx.lora or ())]
@@ -109,43 +157,53 @@ class EarthBlockFn(torch.autograd.Function):
         dx1 = dout
         # _wgrad's input positions: m1w 5, m1b 6, m2w 7, m2b 8, a1w 10, a1b 11, a2w 12, a2b 13
         if s2 != 0.0:
-            x1, pre, h, m = rest
-            dm, g["n2w"], g["n2b"] = ops.ln_residual_bwd(dout, m, n2w, s2)
-            g["m2w"], g["m2b"], g["m2A"], g["m2B"] = _wgrad(ctx, dm, h, 7, 8, ad_m2)
-            dpre = ops.linear(dm, _wt(m2w), None, act=ops.ACT_GELU_BWD, aux=pre)
-            del dm
+            if ctx.mlp_mode == 1:
+                x1, pre, m = rest
+            else:
+                x1, pre, h, m = rest
+            dm, g["n2w"], g["n2b"] = K.ln_residual_bwd(dout, m, n2w, s2)
+            # the W2 weight gradient is launched before the GELU-backward GEMM in fp32, after it in bf16 (where mode 1 gets h from it)
+            if pr is _F32:
+                g["m2w"], g["m2b"], g["m2A"], g["m2B"] = _wgrad(ctx, dm, h, 7, 8, ad_m2)
+            if ctx.mlp_mode == 1:          # h = GELU(pre) comes out of the data-gradient GEMM's epilogue (never stored by the forward)
+                dpre, h = ob.linear_gelu_bwd(dm, pr.wt(m2w), pre, want_h=need["m2w"] or need["m2b"])
+            else:
+                dpre = K.linear(dm, pr.wt(m2w), None, act=ops.ACT_GELU_BWD, aux=pre)
+            if pr is not _F32:
+                g["m2w"], g["m2b"] = _wgrad(ctx, dm, h, 7, 8)[:2]
+            del dm, h
             g["m1w"], g["m1b"], g["m1A"], g["m1B"] = _wgrad(ctx, dpre, x1, 5, 6, ad_m1)
             if dout.is_contiguous():      # residual gradient added in the GEMM epilogue (no extra pass over N x C)
-                dx1 = ops.linear(dpre, _wt(m1w), act=ops.ACT_ADD, aux=dout)
+                dx1 = K.linear(dpre, pr.wt(m1w), act=ops.ACT_ADD, aux=dout)
             else:
-                dx1 = ops.linear(dpre, _wt(m1w))
+                dx1 = K.linear(dpre, pr.wt(m1w))
                 dx1 += dout
             del dpre
         dx = dx1
         if s1 != 0.0:
-            dy, g["n1w"], g["n1b"] = ops.ln_residual_bwd(dx1, y, n1w, s1)
+            dy, g["n1w"], g["n1b"] = K.ln_residual_bwd(dx1, y, n1w, s1)
             g["a2w"], g["a2b"], g["a2A"], g["a2B"] = _wgrad(ctx, dy, o, 12, 13, ad_a2)
-            do = ops.linear(dy, _wt(a2w))
+            do = K.linear(dy, pr.wt(a2w))
             del dy
             # (the bias-table gradient goes straight into the DP flat buffer)
-            dqkv, dqb_pad, desb = ops.window_attention_bwd(qkv, a1b, esb[0], o, lse, do, Z, H, W, heads, shifted,
-                                                           desb_out=ops.grad_slot(esb) if need["esb"] else None)
+            dqkv, dqb_pad, desb = K.window_attention_bwd(qkv, pr.table(a1b), pr.table(esb), o, lse, do, Z, H, W, heads, shifted,
+                                                         desb_out=ops.grad_slot(esb) if need["esb"] else None)
             del do
             g["esb"] = desb.unsqueeze(0)
             # linear1's bias gradient = column sums of dqkv + the pad-slot term already in dqb_pad: the kernel adds into that buffer
             g["a1w"], g["a1b"], g["a1A"], g["a1B"] = _wgrad(ctx, dqkv, x, 10, 11, ad_a1, db_into=dqb_pad)
             if dx1.is_contiguous():
-                dx = ops.linear(dqkv, _wt(a1w), act=ops.ACT_ADD, aux=dx1)
+                dx = K.linear(dqkv, pr.wt(a1w), act=ops.ACT_ADD, aux=dx1)
             else:
-                dx = ops.linear(dqkv, _wt(a1w))
+                dx = K.linear(dqkv, pr.wt(a1w))
                 dx += dx1
         elif not dx.is_contiguous():
             dx = dx.contiguous()
         g["x"] = dx
-        like = {"n1w": n1w, "n1b": n1w, "n2w": n2w, "n2b": n2w, "m1w": m1w, "m1b": m1w[:, 0], "m2w": m2w, "m2b": n2w, "esb": esb,
-                "a1w": a1w, "a1b": a1b, "a2w": a2w, "a2b": n1w, **dict(zip(EarthBlockFn._INPUTS[19:], ab))}
-        # only what asks for a gradient is filled for a dropped branch (frozen base tensors get nothing)
-        ops.fill_dropped_grads(g, {k: t for k, t in like.items() if need.get(k)})
+        if s1 == 0.0 or s2 == 0.0:        # a dropped branch: only what asks for a gradient is filled (frozen parameters get nothing)
+            like = {"n1w": n1w, "n1b": n1w, "n2w": n2w, "n2b": n2w, "m1w": m1w, "m1b": m1w[:, 0], "m2w": m2w, "m2b": n2w, "esb": esb,
+                    "a1w": a1w, "a1b": a1b, "a2w": a2w, "a2b": n1w, **dict(zip(EarthBlockFn._INPUTS[20:], ab))}
+            ops.fill_dropped_grads(g, {k: t for k, t in like.items() if need.get(k)})
         return _keep_needed(ctx, [g.get(k) for k in EarthBlockFn._INPUTS])
 
 
@@ -160,7 +218,7 @@ class AttentionWindowsFn(torch.autograd.Function):
         qkv = ops.linear(xw, w1, b1)
         o = ops.attention_windows(qkv, esb[0], mask, n_lon, types, heads)
         ctx.save_for_backward(xw, qkv, o, w1, w2, esb, mask, *ab)
-        ctx.geom, ctx.lora = geom, lora
+        ctx.geom, ctx.lora, ctx.pr = geom, lora, _F32
         return ops.linear(o, w2, b2)
 
     @staticmethod
@@ -186,7 +244,7 @@ class MlpFn(torch.autograd.Function):
         pre = torch.empty((x.shape[0], w1.shape[0]), dtype=x.dtype, device=x.device)
         h = ops.linear(x, w1, b1, act=ops.ACT_GELU, aux=pre)
         ctx.save_for_backward(x, pre, h, w1, w2, *ab)
-        ctx.lora = lora
+        ctx.lora, ctx.pr = lora, _F32
         return ops.linear(h, w2, b2)
 
     @staticmethod
@@ -214,30 +272,40 @@ class PatchEmbedFn(torch.autograd.Function):
     (`input.requires_grad_()`, plain autograd in the reference): d_input = scatter-adjoint of the gather of (dx @ W) / std."""
 
     @staticmethod
-    def forward(ctx, cw, cb, sw, sb, inp, inp_s, s_mean, s_std, u_mean, u_std, maps, const_h, levels_reversed=False):
-        a_s, a_u = ops.patch_embed_gather(inp, inp_s, s_mean, s_std, u_mean, u_std, maps, const_h, levels_reversed)
+    def forward(ctx, cw, cb, sw, sb, inp, inp_s, s_mean, s_std, u_mean, u_std, maps, const_h, levels_reversed=False, sh=None):
+        ctx.pr = pr = _precision(sh)
+        a_s, a_u = pr.k.patch_embed_gather(inp, inp_s, s_mean, s_std, u_mean, u_std, maps, const_h, levels_reversed)
         n_s = a_s.shape[0]
-        x = torch.empty((n_s + a_u.shape[0], cw.shape[0]), dtype=torch.float32, device=inp.device)
-        ops.linear(a_s, sw, sb, out=x[:n_s])
-        ops.linear(a_u, cw, cb, out=x[n_s:])
+        x = torch.empty((n_s + a_u.shape[0], cw.shape[0]), dtype=pr.dtype, device=inp.device)
+        # the bf16 gather writes the surface rows 128 wide (112 columns + padding): its GEMM takes a weight image padded alike
+        pr.k.linear(a_s, sw if sh is None else sh.get(sw, pad_k=128), sb, out=x[:n_s])
+        pr.k.linear(a_u, pr.w(cw), cb, out=x[n_s:])
         ctx.save_for_backward(a_s, a_u, cw, sw, s_std, u_std)
-        ctx.shapes, ctx.geom = (cw.shape, sw.shape), (inp.shape[-2], inp.shape[-1], bool(levels_reversed))
+        ctx.geom = (inp.shape[-2], inp.shape[-1], bool(levels_reversed))
         return x
 
     @staticmethod
     def backward(ctx, dx):
         a_s, a_u, cw, sw, s_std, u_std = ctx.saved_tensors
+        pr = ctx.pr
         n_s = a_s.shape[0]
-        dx = dx.contiguous()
+        if pr is _F32:
+            dx = dx.contiguous()
         need = ctx.needs_input_grad
-        dsw, dsb = _wgrad(ctx, dx[:n_s], a_s, 2, 3, shape=ctx.shapes[1])[:2]
-        dcw, dcb = _wgrad(ctx, dx[n_s:], a_u, 0, 1, shape=ctx.shapes[0])[:2]
+        dsw, dsb = _wgrad(ctx, dx[:n_s], a_s, 2, 3)[:2]
+        if dsw is not None:
+            if pr is not _F32:
+                dsw = dsw[:, :sw.shape[1]]                              # (192, 128): columns 112.. are padding
+            dsw = dsw.reshape(sw.shape)
+        dcw, dcb = _wgrad(ctx, dx[n_s:], a_u, 0, 1, shape=cw.shape)[:2]
         d_in = d_in_s = None
         if need[4] or need[5]:
+            # the raw fields asked for their gradient: dA for the A-matrix columns with a field behind them, the first 64 of 112
+            # (surface) / 160 of 192 (upper), as an fp32 result; then the fp32 scatter adjoint of the gather, divided by the std
             LAT, LON, rev = ctx.geom
-            # only the A-matrix columns with a field behind them: the first 64 of 112 (surface) / 160 of 192 (upper)
-            da_s = ops.linear(dx[:n_s], _wt(sw)[:64].contiguous())
-            da_u = ops.linear(dx[n_s:], _wt(cw)[:160].contiguous())
+            dx = dx.contiguous()
+            da_s = pr.k.linear(dx[:n_s], pr.wt(sw)[:64].contiguous(), **pr.f32_out)
+            da_u = pr.k.linear(dx[n_s:], pr.wt(cw)[:160].contiguous(), **pr.f32_out)
             d_in, d_in_s = ops.patch_embed_gather_bwd(da_s, da_u, s_std, u_std, LAT, LON, rev)
         return _keep_needed(ctx, (dcw, dcb, dsw, dsb, d_in, d_in_s))
 
@@ -246,17 +314,19 @@ class DownSampleFn(torch.autograd.Function):
     """reference models/layers.py:432-459 for one sample."""
 
     @staticmethod
-    def forward(ctx, x, lw, nw, nb, geom, skip_grad=None, lora=None, *ab):
-        # skip_grad: one-slot list shared with PatchRecoverHalvesFn (the skip connection's other gradient, summed inside the
-        # down-sampling backward kernel instead of by autograd's elementwise add): see autograd_bf16.DownSampleFnBF16
+    def forward(ctx, x, lw, nw, nb, geom, skip_grad=None, sh=None, lora=None, *ab):
+        # skip_grad: a one-slot list shared with PatchRecoverHalvesFn -- x is the skip connection (reference pangu_model.py:62, :81),
+        # whose OTHER gradient (through the channel concat) that function leaves in the slot instead of handing it to autograd:
+        # the backward below sums the two inside the down-sampling kernel (no elementwise add over the 200-400 MB)
         Z, H, W = geom
-        g = ops.downsample_ln(x, nw, nb, Z, H, W)
+        ctx.pr = pr = _precision(sh, lora)
+        g = pr.k.downsample_ln(x, nw, nb, Z, H, W)
         ctx.save_for_backward(x, g, lw, nw, *ab)
         ctx.geom, ctx.skip_grad = geom, skip_grad
         ctx.lora = lora          # (scaling,) of an adapted linear (layers.lora_args): lw is then W_eff, ab = (A, B)
         if skip_grad is not None:
-            skip_grad[1] = True
-        return ops.linear(g, lw)
+            skip_grad[1] = True                  # armed: this node's backward will consume the slot
+        return pr.k.linear(g, pr.w(lw))
 
     @staticmethod
     def backward(ctx, dout):
@@ -264,39 +334,41 @@ class DownSampleFn(torch.autograd.Function):
         Z, H, W = ctx.geom
         dout = dout.contiguous()
         dlw, _, dA, dB = _wgrad(ctx, dout, g, 1, ad=_adapters(ctx, ab, 1)[0])
-        dg = ops.linear(dout, _wt(lw))
+        dg = ctx.pr.k.linear(dout, ctx.pr.wt(lw))
         add = None
         if ctx.skip_grad is not None:
             add, ctx.skip_grad[0] = ctx.skip_grad[0], None
-        dx, dnw, dnb = ops.downsample_ln_bwd(dg, x, nw, Z, H, W, add=add)
-        return _keep_needed(ctx, (dx, dlw, dnw, dnb, None, None, None, dA, dB))
+        dx, dnw, dnb = ctx.pr.k.downsample_ln_bwd(dg, x, nw, Z, H, W, add=add)
+        return _keep_needed(ctx, (dx, dlw, dnw, dnb, None, None, None, None, dA, dB))
 
 
 class UpSampleFn(torch.autograd.Function):
     """reference models/layers.py:474-499 for one sample."""
 
     @staticmethod
-    def forward(ctx, x, l1w, l2w, nw, nb, geom, lora=None, *ab):
+    def forward(ctx, x, l1w, l2w, nw, nb, geom, sh=None, lora=None, *ab):
         # lora: scalings of (linear1, linear2) (layers.lora_args), l1w / l2w then the W_eff tensors, ab = (A1, B1, A2, B2)
         Z, H2, W2, H = geom
-        y = ops.linear(x, l1w)
-        g = ops.upsample_ln(y, nw, nb, Z, H2, W2, H)
+        ctx.pr = pr = _precision(sh, lora)
+        y = pr.k.linear(x, pr.w(l1w))
+        g = pr.k.upsample_ln(y, nw, nb, Z, H2, W2, H)
         ctx.save_for_backward(x, y, g, l1w, l2w, nw, *ab)
         ctx.geom, ctx.lora = geom, lora
-        return ops.linear(g, l2w)
+        return pr.k.linear(g, pr.w(l2w))
 
     @staticmethod
     def backward(ctx, dout):
         x, y, g, l1w, l2w, nw, *ab = ctx.saved_tensors
         ad1, ad2 = _adapters(ctx, ab, 2)
         Z, H2, W2, H = ctx.geom
+        pr = ctx.pr
         dout = dout.contiguous()
         dl2w, _, dA2, dB2 = _wgrad(ctx, dout, g, 2, ad=ad2)
-        dg = ops.linear(dout, _wt(l2w))
-        dy, dnw, dnb = ops.upsample_ln_bwd(dg, y, nw, Z, H2, W2, H)
+        dg = pr.k.linear(dout, pr.wt(l2w))
+        dy, dnw, dnb = pr.k.upsample_ln_bwd(dg, y, nw, Z, H2, W2, H)
         dl1w, _, dA1, dB1 = _wgrad(ctx, dy, x, 1, ad=ad1)
-        dx = ops.linear(dy, _wt(l1w))
-        return _keep_needed(ctx, (dx, dl1w, dl2w, dnw, dnb, None, None, dA1, dB1, dA2, dB2))
+        dx = pr.k.linear(dy, pr.wt(l1w))
+        return _keep_needed(ctx, (dx, dl1w, dl2w, dnw, dnb, None, None, None, dA1, dB1, dA2, dB2))
 
 
 class PatchRecoverFn(torch.autograd.Function):
@@ -308,7 +380,7 @@ class PatchRecoverFn(torch.autograd.Function):
         y_s = ops.linear(x[:n_s], sw, sb)
         y_u = ops.linear(x[n_s:], cw, cb)
         ctx.save_for_backward(x, cw, sw)
-        ctx.geom = geom
+        ctx.geom, ctx.pr = geom, _F32
         return ops.patch_recover_scatter(y_u, y_s, LAT, LON)
 
     @staticmethod
@@ -330,14 +402,15 @@ class PatchRecoverHalvesFn(torch.autograd.Function):
     its own DENSE gradient in the backward (two N = C products instead of row-strided views of one N = 2C product)."""
 
     @staticmethod
-    def forward(ctx, skip, x, cw, cb, sw, sb, geom, skip_grad=None):
+    def forward(ctx, skip, x, cw, cb, sw, sb, geom, skip_grad=None, sh=None):
         ctx.skip_grad = skip_grad
+        ctx.pr = pr = _precision(sh)
         n_s, LAT, LON = geom
         N, C = skip.shape
-        assert skip.stride() == (2 * C, 1) and x.stride() == (2 * C, 1) and x.data_ptr() == skip.data_ptr() + 4 * C
+        assert skip.stride() == (2 * C, 1) and x.stride() == (2 * C, 1) and x.data_ptr() == skip.data_ptr() + skip.element_size() * C
         cat = torch.as_strided(skip, (N, 2 * C), (2 * C, 1), skip.storage_offset())
-        y_s = ops.linear(cat[:n_s], sw, sb)
-        y_u = ops.linear(cat[n_s:], cw, cb)
+        y_s = pr.k.linear(cat[:n_s], pr.w(sw), sb, **pr.f32_out)
+        y_u = pr.k.linear(cat[n_s:], pr.w(cw), cb, **pr.f32_out)
         ctx.save_for_backward(cat, cw, sw)
         ctx.geom = geom
         return ops.patch_recover_scatter(y_u, y_s, LAT, LON)
@@ -347,15 +420,16 @@ class PatchRecoverHalvesFn(torch.autograd.Function):
         cat, cw, sw = ctx.saved_tensors
         n_s, LAT, LON = ctx.geom
         C = cat.shape[1] // 2
-        dy_u, dy_s = ops.patch_recover_gather_bwd(d_out.contiguous(), d_out_s.contiguous())
+        pr = ctx.pr
+        dy_u, dy_s = pr.k.patch_recover_gather_bwd(d_out.contiguous(), d_out_s.contiguous())
         dcw, dcb = _wgrad(ctx, dy_u, cat[n_s:], 2, 3, shape=cw.shape)[:2]
         dsw, dsb = _wgrad(ctx, dy_s, cat[:n_s], 4, 5, shape=sw.shape)[:2]
-        wt_s, wt_u = _wt(sw), _wt(cw)                                      # (2C, 64), (2C, 160): rows = input channels
-        d_skip = torch.empty((cat.shape[0], C), dtype=torch.float32, device=cat.device)
+        wt_s, wt_u = pr.wt(sw), pr.wt(cw)                                  # (2C, 64), (2C, 160): rows = input channels
+        d_skip = torch.empty((cat.shape[0], C), dtype=cat.dtype, device=cat.device)
         d_x = torch.empty_like(d_skip)
         for dst, rows in ((d_skip, slice(0, C)), (d_x, slice(C, 2 * C))):
-            ops.linear(dy_s, wt_s[rows], out=dst[:n_s])
-            ops.linear(dy_u, wt_u[rows], out=dst[n_s:])
+            pr.k.linear(dy_s, wt_s[rows], out=dst[:n_s])
+            pr.k.linear(dy_u, wt_u[rows], out=dst[n_s:])
         sg = ctx.skip_grad
         if sg is not None and sg[1] and ctx.needs_input_grad[0]:
             sg[0], d_skip = d_skip, None          # the down-sampling backward adds it in its own pass (DownSampleFn)

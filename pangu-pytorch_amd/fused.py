@@ -39,6 +39,34 @@ def _tok2d(x):
     return x.as_strided((B * N, C), (x.stride(1), 1), x.storage_offset())
 
 
+def drop_path_scales(blk):
+    """The block's two DropPath keep factors (reference layers.py:250-251), drawn attention branch first."""
+    dp = blk.drop_path
+    if not hasattr(dp, "sample_scale"):
+        return 1.0, 1.0
+    return dp.sample_scale(blk.training), dp.sample_scale(blk.training)
+
+
+def embed_constants(statistics, maps, const_h, LAT, LON, dev):
+    """The normalisation statistics and constant maps as the patch-embedding gather reads them: contiguous fp32 on `dev`
+    -> s_mean (4,), s_std (4,), u_mean (13, 5), u_std (13, 5), maps (3, 4*H4, LON), const_h (13, LAT, LON)."""
+    f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()
+    s_mean, s_std, u_mean, u_std = statistics
+    return (f32(s_mean).reshape(-1), f32(s_std).reshape(-1), f32(u_mean).reshape(13, 5), f32(u_std).reshape(13, 5),
+            f32(maps).reshape(3, 4 * ((LAT + 3) // 4), LON), f32(const_h).reshape(13, LAT, LON))
+
+
+def concat_halves(x):
+    """The skip-concat buffer of reference pangu_model.py:81 for the autograd path, as its two (N, C) halves: layer 0 / layer 3
+    write their results straight into them, so the concat costs no copy.  The halves SHARE the storage of one (N, 2C) buffer
+    without being autograd views of it (a view returned by a custom Function whose base is written again -- the other half -- is
+    refused by autograd).  x: (N, C) or (1, N, C), giving shape, dtype and device."""
+    N, C = x.shape[-2:]
+    cat = torch.empty((N, 2 * C), dtype=x.dtype, device=x.device)
+    return [torch.empty(0, dtype=x.dtype, device=x.device).set_(cat.untyped_storage(), cat.storage_offset() + off, (N, C), (2 * C, 1))
+            for off in (0, C)]
+
+
 def mlp(m, x2d):
     """Mlp.forward on its own (reference layers.py:264-270; the block never comes through here): differentiable."""
     if _train_path(m, x2d):
@@ -52,16 +80,14 @@ def earth_block(blk, x, Z, H, W, roll, out=None):
     """x (B,N,C) -> (B,N,C).  reference layers.py:183-253 as 5 kernel launches per sample (qkv, attention core, proj+LN+residual, MLP-up+GELU, MLP-down+LN+residual)."""
     B, N, C = x.shape
     att = blk.attention
-    dp = blk.drop_path
     if _train_path(blk, x):
         outs = []
         # out as a 2-D (N, C) row-strided tensor (B = 1): the block function writes its result there (a half of the
         # skip-concat buffer, PanguModel._forward_f32) -- no copy
         direct = out is not None and out.dim() == 2 and B == 1
-        extra = ((out,) if direct else None,) + _layers.lora_args(blk.linear.linear1, blk.linear.linear2, att.linear1, att.linear2)
+        extra = ((out,) if direct else None, None) + _layers.lora_args(blk.linear.linear1, blk.linear.linear2, att.linear1, att.linear2)
         for xb in _samples(x):
-            s1 = dp.sample_scale(blk.training) if hasattr(dp, "sample_scale") else 1.0
-            s2 = dp.sample_scale(blk.training) if hasattr(dp, "sample_scale") else 1.0
+            s1, s2 = drop_path_scales(blk)
             outs.append(EarthBlockFn.apply(
                 xb, blk.norm1.weight, blk.norm1.bias, blk.norm2.weight, blk.norm2.bias,
                 _layers.eff_weight(blk.linear.linear1), blk.linear.linear1.bias,
@@ -74,8 +100,7 @@ def earth_block(blk, x, Z, H, W, roll, out=None):
             return out
         return y
     x2 = _tok2d(x)
-    s1 = dp.sample_scale(blk.training) if hasattr(dp, "sample_scale") else 1.0
-    s2 = dp.sample_scale(blk.training) if hasattr(dp, "sample_scale") else 1.0
+    s1, s2 = drop_path_scales(blk)
     if s1 != 0.0:
         qkv = ops.linear(x2, _layers.eff_weight(att.linear1), att.linear1.bias)      # (B*N, 3C)
         # inference on the paper's compact bias table (PanguModel.use_compact_bias): 10 MB instead of 62 MB per block
@@ -120,25 +145,19 @@ def earth_block(blk, x, Z, H, W, roll, out=None):
 
 def patch_embed(m, inp, inp_surface, statistics, maps, const_h, levels_reversed=False):
     """reference layers.py:40-93 -> (B, 8*181*360, 192)."""
-    s_mean, s_std, u_mean, u_std = statistics
     B = inp.shape[0]
     LAT, LON = inp.shape[-2], inp.shape[-1]
     H4, W4 = (LAT + 3) // 4, LON // 4
     n_s, n_u = H4 * W4, 7 * H4 * W4
     dim = m.conv.weight.shape[0]
     x = torch.empty((B, n_s + n_u, dim), dtype=torch.float32, device=inp.device)
-    f32 = lambda t: t.to(device=inp.device, dtype=torch.float32).contiguous()
-    s_mean, s_std = f32(s_mean).reshape(-1), f32(s_std).reshape(-1)
-    u_mean, u_std = f32(u_mean).reshape(13, 5), f32(u_std).reshape(13, 5)
-    maps_c = f32(maps).reshape(3, 4 * H4, LON)
-    const_c = f32(const_h).reshape(13, LAT, LON)
+    consts = embed_constants(statistics, maps, const_h, LAT, LON, inp.device)
     if _train_path(m, inp, inp_surface):
         return _stack([PatchEmbedFn.apply(m.conv.weight, m.conv.bias, m.conv_surface.weight, m.conv_surface.bias,
-                                          inp[b].contiguous(), inp_surface[b].contiguous(), s_mean, s_std, u_mean,
-                                          u_std, maps_c, const_c, levels_reversed) for b in range(B)], B)
+                                          inp[b].contiguous(), inp_surface[b].contiguous(), *consts, levels_reversed)
+                       for b in range(B)], B)
     for b in range(B):
-        a_s, a_u = ops.patch_embed_gather(inp[b].contiguous(), inp_surface[b].contiguous(), s_mean, s_std, u_mean,
-                                          u_std, maps_c, const_c, levels_reversed)
+        a_s, a_u = ops.patch_embed_gather(inp[b].contiguous(), inp_surface[b].contiguous(), *consts, levels_reversed)
         ops.linear(a_s, m.conv_surface.weight, m.conv_surface.bias, out=x[b, :n_s])
         ops.linear(a_u, m.conv.weight, m.conv.bias, out=x[b, n_s:])
     return x
@@ -148,7 +167,7 @@ def down_sample(m, x, Z, H, W, skip_grad=None):
     B, N, C = x.shape
     if _train_path(m, x):
         return _stack([DownSampleFn.apply(xb, _layers.eff_weight(m.linear), m.norm.weight, m.norm.bias, (Z, H, W),
-                                          skip_grad if B == 1 else None, *_layers.lora_args(m.linear)) for xb in _samples(x)], B)
+                                          skip_grad if B == 1 else None, None, *_layers.lora_args(m.linear)) for xb in _samples(x)], B)
     outs = []
     for b in range(B):
         g = ops.downsample_ln(_tok2d(x[b:b + 1]), m.norm.weight, m.norm.bias, Z, H, W)
@@ -160,7 +179,7 @@ def up_sample(m, x, Z, H2, W2, H, out=None):
     B, N, C2 = x.shape
     if _train_path(m, x):
         y = _stack([UpSampleFn.apply(xb, _layers.eff_weight(m.linear1), _layers.eff_weight(m.linear2), m.norm.weight, m.norm.bias,
-                                     (Z, H2, W2, H), *_layers.lora_args(m.linear1, m.linear2)) for xb in _samples(x)], B)
+                                     (Z, H2, W2, H), None, *_layers.lora_args(m.linear1, m.linear2)) for xb in _samples(x)], B)
         if out is not None:
             out.copy_(y)
             return out

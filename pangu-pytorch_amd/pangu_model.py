@@ -308,11 +308,11 @@ class PanguModel(nn.Module):
 
     def _forward_dispatch(self, input, input_surface, statistics, maps, const_h, want_bf16, grad_path, levels_reversed=False):
         if want_bf16:
-            from . import autograd_bf16, fused_bf16
+            from . import fused_bf16
             if self._shadow is None:
                 self._shadow = fused_bf16.WeightShadow()
             if grad_path:
-                return autograd_bf16.forward_train(self, input, input_surface, statistics, maps, const_h, levels_reversed)
+                return fused_bf16.forward_train(self, input, input_surface, statistics, maps, const_h, levels_reversed)
             return fused_bf16.forward(self, input, input_surface, statistics, maps, const_h, levels_reversed)
         if self._compact_bias and not grad_path:
             self._build_compact_bias()            # no-op while the tables exist (dropped with the weight shadows)
@@ -325,13 +325,9 @@ class PanguModel(nn.Module):
         # skip connection: layer 0 writes its result into the left half, layer 3 into the right half of one
         # (B,N,2C) buffer, so the channel concat of reference pangu_model.py:81 costs no copy
         if grad_path and B == 1:
-            # autograd path, one sample: layer 0 / layer 3 write straight into the two halves of one (N, 2C) buffer, given
-            # to autograd as tensors that SHARE its storage without being views of it (a view returned by a custom Function
-            # whose base is written again -- the other half -- is refused)
+            # autograd path, one sample: layer 0 / layer 3 write straight into the two halves of one (N, 2C) buffer
             from . import fused
-            cat = torch.empty((N, 2 * C), dtype=x.dtype, device=x.device)
-            halves = [torch.empty(0, dtype=x.dtype, device=x.device).set_(cat.untyped_storage(), cat.storage_offset() + off, (N, C), (2 * C, 1))
-                      for off in (0, C)]
+            halves = fused.concat_halves(x)
             skip = self.layers[0](x, 8, 181, 360, out=halves[0])
             skip_grad = [None, False]         # the skip connection's concat-path gradient, summed inside the down-sampling backward
             x = self.downsample(skip, 8, 181, 360, skip_grad=skip_grad)

@@ -389,14 +389,14 @@ def test_dropped_branch_gradient_policy(P, dt):
             blk.drop_path.sample_scale = lambda training: next(seq)
             x = cases.block_input(C, W, "cuda")
             if dt == "bf16":
-                from pangu_pytorch_amd import autograd_bf16, fused_bf16
+                from pangu_pytorch_amd import autograd, fused_bf16
                 att = blk.attention
                 s1, s2 = blk.drop_path.sample_scale(True), blk.drop_path.sample_scale(True)
-                y = autograd_bf16.EarthBlockFnBF16.apply(
+                y = autograd.EarthBlockFn.apply(
                     x[0].to(torch.bfloat16).requires_grad_(True), blk.norm1.weight, blk.norm1.bias, blk.norm2.weight, blk.norm2.bias,
                     blk.linear.linear1.weight, blk.linear.linear1.bias, blk.linear.linear2.weight, blk.linear.linear2.bias,
                     att.earth_specific_bias, att.linear1.weight, att.linear1.bias, att.linear2.weight, att.linear2.bias,
-                    (st["Z"], st["H"], W, att.head_number, roll), s1, s2, fused_bf16.WeightShadow(), None)
+                    (st["Z"], st["H"], W, att.head_number, roll), s1, s2, None, fused_bf16.WeightShadow())
             else:
                 y = blk(x.requires_grad_(True), st["Z"], st["H"], W, roll)
             (y.float() * cases.cotangent("dp", y.shape, "cuda")).sum().backward()

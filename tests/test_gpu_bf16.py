@@ -458,7 +458,7 @@ def test_block_backward_bf16_vs_fp32(P, golden_dir):
     C, roll = 192, True
     tag = f"block_{C}_{int(roll)}"
     st = cases.STAGES[C]
-    from pangu_pytorch_amd import autograd_bf16 as AB, fused_bf16
+    from pangu_pytorch_amd import autograd as AB, fused_bf16
     blk = P.layers.EarthSpecificBlock(C, 0.0, st["heads"], device="cuda").cuda().eval()
     pre = cases.block_prefix(C, roll)
     blk.load_state_dict({k: synth.synth_param(pre + k, s, "cuda") for k, s in cases.block_param_shapes(C).items()})
@@ -474,11 +474,11 @@ def test_block_backward_bf16_vs_fp32(P, golden_dir):
     att = blk.attention
     sh = fused_bf16.WeightShadow()
     xb = x[0].to(BF).requires_grad_(True)
-    yb = AB.EarthBlockFnBF16.apply(xb, blk.norm1.weight, blk.norm1.bias, blk.norm2.weight, blk.norm2.bias,
-                                   blk.linear.linear1.weight, blk.linear.linear1.bias, blk.linear.linear2.weight,
-                                   blk.linear.linear2.bias, att.earth_specific_bias, att.linear1.weight, att.linear1.bias,
-                                   att.linear2.weight, att.linear2.bias, (st["Z"], st["H"], 24, st["heads"], roll), 1.0,
-                                   1.0, sh)
+    yb = AB.EarthBlockFn.apply(xb, blk.norm1.weight, blk.norm1.bias, blk.norm2.weight, blk.norm2.bias,
+                               blk.linear.linear1.weight, blk.linear.linear1.bias, blk.linear.linear2.weight,
+                               blk.linear.linear2.bias, att.earth_specific_bias, att.linear1.weight, att.linear1.bias,
+                               att.linear2.weight, att.linear2.bias, (st["Z"], st["H"], 24, st["heads"], roll), 1.0,
+                               1.0, None, sh)
     (yb.float() * cot[0]).sum().backward()
     l2 = lambda a, b: ((a.double() - b.double()).norm() / b.double().norm()).item()
     worst = max((l2(p.grad, ref[k]), k) for k, p in blk.named_parameters())
@@ -508,16 +508,16 @@ def _bf16_block(P):
 
 
 def _bf16_block_apply(blk, x, geom, sh):
-    from pangu_pytorch_amd import autograd_bf16 as AB
+    from pangu_pytorch_amd import autograd as AB
     att = blk.attention
-    return AB.EarthBlockFnBF16.apply(x, blk.norm1.weight, blk.norm1.bias, blk.norm2.weight, blk.norm2.bias,
-                                     blk.linear.linear1.weight, blk.linear.linear1.bias, blk.linear.linear2.weight,
-                                     blk.linear.linear2.bias, att.earth_specific_bias, att.linear1.weight, att.linear1.bias,
-                                     att.linear2.weight, att.linear2.bias, geom, 1.0, 1.0, sh)
+    return AB.EarthBlockFn.apply(x, blk.norm1.weight, blk.norm1.bias, blk.norm2.weight, blk.norm2.bias,
+                                 blk.linear.linear1.weight, blk.linear.linear1.bias, blk.linear.linear2.weight,
+                                 blk.linear.linear2.bias, att.earth_specific_bias, att.linear1.weight, att.linear1.bias,
+                                 att.linear2.weight, att.linear2.bias, geom, 1.0, 1.0, None, sh)
 
 
 def test_block_backward_bf16_frozen_subsets(P):
-    """EarthBlockFnBF16 with all parameters trainable, only `linear.*` trainable, and all frozen (x asking for a gradient): frozen
+    """The bf16 EarthBlockFn with all parameters trainable, only `linear.*` trainable, and all frozen (x asking for a gradient): frozen
     parameters get None, the backward launches one weight-gradient GEMM per projection whose weight or bias trains (4, 2, 0),
     and dx and the trainable gradients match the all-trainable run within FROZEN_BLOCK_TOL."""
     from pangu_pytorch_amd import fused_bf16
@@ -733,7 +733,7 @@ def test_block_bf16_drift_within_2x_of_reference_autocast(P, golden_dir, C, roll
     models/pangu_model.py:41-48; synth.param_spec_refinit) the HIP bf16 block -- training forward and no-grad forward -- drifts
     from fp32 by no more than 2x what the reference's own CPU autocast(bfloat16) block does on the same input
     (tests/golden/refinit.npz: 4.2e-3 rel-L2, recorded by oracle/gen_golden.py refinit)."""
-    from pangu_pytorch_amd import autograd_bf16 as AB, fused_bf16
+    from pangu_pytorch_amd import autograd as AB, fused_bf16
     g = np.load(os.path.join(golden_dir, "refinit.npz"))
     tag = f"refinit_block_{C}_{int(roll)}"
     st = cases.STAGES[C]
@@ -750,11 +750,11 @@ def test_block_bf16_drift_within_2x_of_reference_autocast(P, golden_dir, C, roll
     ref_drift = float(g[tag + ".autocast_drift"][0])
     att, shd = blk.attention, fused_bf16.WeightShadow()
     xb = x[0].to(BF)
-    yb_train = AB.EarthBlockFnBF16.apply(xb.clone().requires_grad_(True), blk.norm1.weight, blk.norm1.bias, blk.norm2.weight,
-                                         blk.norm2.bias, blk.linear.linear1.weight, blk.linear.linear1.bias,
-                                         blk.linear.linear2.weight, blk.linear.linear2.bias, att.earth_specific_bias,
-                                         att.linear1.weight, att.linear1.bias, att.linear2.weight, att.linear2.bias,
-                                         (st["Z"], st["H"], 24, st["heads"], roll), 1.0, 1.0, shd).detach()
+    yb_train = AB.EarthBlockFn.apply(xb.clone().requires_grad_(True), blk.norm1.weight, blk.norm1.bias, blk.norm2.weight,
+                                     blk.norm2.bias, blk.linear.linear1.weight, blk.linear.linear1.bias,
+                                     blk.linear.linear2.weight, blk.linear.linear2.bias, att.earth_specific_bias,
+                                     att.linear1.weight, att.linear1.bias, att.linear2.weight, att.linear2.bias,
+                                     (st["Z"], st["H"], 24, st["heads"], roll), 1.0, 1.0, None, shd).detach()
     with torch.no_grad():
         yb_inf = fused_bf16._block(blk, shd, xb, st["Z"], st["H"], 24, roll)
     l2 = lambda a: ((a.double() - y32[0].double()).norm() / y32[0].double().norm()).item()
