@@ -387,6 +387,22 @@ int pangu_weighted_l1_loss_bwd(pangu_stream_t stream, const float* out, const fl
                                int levels, int target_levels_reversed, const float* t_mean_upper, const float* t_std_upper,
                                const float* t_mean_surface, const float* t_std_surface);
 
+/* Multi-step (rollout) fine-tuning: the gradient that enters the model's output at step k of a K-step chain, in ONE pass:
+ *   d_out = [what pangu_weighted_l1_loss_bwd writes] + d_next * std[var][level]
+ * d_next / d_next_surface (both or neither): d loss / d (physical input fields of step k+1), [B][Vu][plane_u] / [B][Vs][plane_s] in the
+ * MODEL's level order (never reversed); the multiply by std is the adjoint of `normBackData` (out * std + mean,
+ * era5_data/utils_data.py:324-330), which the forward's last kernel folds in (pangu_patch_recover_scatter_denorm).  The product
+ * is rounded to fp32 before the add (what the two torch ops give).  std_upper [Vu][levels] (logical level order), std_surface [Vs]:
+ * required when d_next is given.  d_out / d_out_surface MAY be the very buffers d_next / d_next_surface (elementwise, same index).
+ * grad: device scalar, lead-time weight x upstream gradient.  d_next == NULL (the last step): bit-identical to
+ * pangu_weighted_l1_loss_bwd.  Every other argument as there. */
+int pangu_rollout_l1_seed_bwd(pangu_stream_t stream, const float* out, const float* target, const float* out_surface,
+                              const float* target_surface, const float* w_upper, const float* w_surface, const float* grad,
+                              const float* d_next, const float* d_next_surface, const float* std_upper, const float* std_surface,
+                              float* d_out, float* d_out_surface, int B, int Vu, long long plane_u, int Vs, long long plane_s,
+                              int levels, int target_levels_reversed, const float* t_mean_upper, const float* t_std_upper,
+                              const float* t_mean_surface, const float* t_std_surface);
+
 /* Host side of the input pipeline (the idea of reference era5_data/utils_data.py:16-51 and the four
  * `.to(device)` of models/pangu_sample.py:41-43): copy `bytes` from the loader's pageable memory into a page-locked staging
  * buffer with up to `threads` host threads (each one contiguous 4 KB-aligned span; < 4 MB per thread is not split).  Pure

@@ -55,6 +55,7 @@ SIGNATURES = {
     "pangu_weighted_l1_loss_blocks": [_I, _I, _c.c_longlong, _I, _c.c_longlong, _I],
     "pangu_weighted_l1_loss_fwd": [_P] * 9 + [_I, _I, _c.c_longlong, _I, _c.c_longlong, _I, _I] + [_P] * 4,
     "pangu_weighted_l1_loss_bwd": [_P] * 10 + [_I, _I, _c.c_longlong, _I, _c.c_longlong, _I, _I] + [_P] * 4,
+    "pangu_rollout_l1_seed_bwd": [_P] * 14 + [_I, _I, _c.c_longlong, _I, _c.c_longlong, _I, _I] + [_P] * 4,
     "pangu_host_copy": [_P, _P, _c.c_longlong, _I],
     "pangu_window_attn_bwd_bf16": [_P] * 10 + [_I] * 6,
     "pangu_ln_residual_bwd_bf16": [_P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _F],

@@ -158,6 +158,71 @@ __global__ __launch_bounds__(256) void l1_loss_bwd_kernel(const float* __restric
   }
 }
 
+// Step k of a K-step rollout fine-tune: the gradient that enters the model's output is the step's own loss gradient (exactly what
+// l1_loss_bwd_kernel writes) PLUS the gradient the next step's physical input fields received, taken back through `normBackData`
+// (out * std + mean: a multiply by std[var][lev]).  As torch ops that is the loss backward, a broadcast multiply and autograd's
+// accumulate add: three passes and two temporaries of 286 MB; here one pass: read out, target, d_next, write d_out.
+// dn / dns live in the MODEL's level order like out (base, never base_t); d may BE dn (each thread reads the elements it writes:
+// same index, read before write), hence no __restrict__ on those four.
+__global__ __launch_bounds__(256) void rollout_l1_seed_bwd_kernel(const float* __restrict__ o, const float* __restrict__ t,
+                                                                  const float* __restrict__ os, const float* __restrict__ ts,
+                                                                  const float* __restrict__ wu, const float* __restrict__ ws,
+                                                                  const float* __restrict__ grad, const float* dn, const float* dns,
+                                                                  const float* __restrict__ fstd_u, const float* __restrict__ fstd_s,
+                                                                  float* d_o, float* d_os, LossGeom g, TargetStats st, float inv_nu,
+                                                                  float inv_ns) {
+  bool surface; int var, stat; long long begin, end, base, base_t;
+  locate(g, blockIdx.x, surface, var, begin, end, base, base_t, stat);
+  const float* __restrict__ a = (surface ? os : o) + base;
+  const float* __restrict__ b = (surface ? ts : t) + base_t;
+  const float* n = (surface ? dns : dn) + base;
+  float* d = (surface ? d_os : d_o) + base;
+  const bool nrm = st.mean_u != nullptr;
+  const float mn = nrm ? (surface ? st.mean_s[stat] : st.mean_u[stat]) : 0.f;
+  const float sd = nrm ? (surface ? st.std_s[stat] : st.std_u[stat]) : 1.f;
+  const float fsd = surface ? fstd_s[stat] : fstd_u[stat];
+  auto tgt = [nrm, mn, sd](float y) { return nrm ? (y - mn) / sd : y; };
+  const float gr = grad[0];
+  float c = surface ? ((gr * 0.25f) * inv_ns) : (gr * inv_nu);
+  asm volatile("" : "+v"(c));                       // as in l1_loss_bwd_kernel: the two multiplies stay apart
+  c = c * (surface ? ws[var] : wu[var]);
+  auto seed = [c, fsd](float x, float dnext) {
+    const float l = x > 0.f ? c : (x < 0.f ? -c : c * 0.f);
+    float p = dnext * fsd;
+    asm volatile("" : "+v"(p));                     // the product is rounded before the add (torch: one multiply, one add), no FMA
+    return l + p;
+  };
+  const bool vec = ((base | base_t | begin) & 3) == 0;
+  if (vec) {
+    // d may alias n, so the compiler keeps every load of n behind the stores before it: all loads of the chunk are issued first,
+    // by hand (24 x 16 B in flight per thread), then the stores
+    constexpr int U = LOSS_CHUNK / 1024;
+    f32x4 X[U] = {}, Y[U] = {}, Z[U] = {};
+#pragma unroll
+    for (int k = 0; k < U; ++k) {
+      const long long i = begin + k * 1024 + threadIdx.x * 4;
+      if (i + 4 <= end) {
+        X[k] = *reinterpret_cast<const f32x4*>(a + i);
+        Y[k] = *reinterpret_cast<const f32x4*>(b + i);
+        Z[k] = *reinterpret_cast<const f32x4*>(n + i);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < U; ++k) {
+      const long long i = begin + k * 1024 + threadIdx.x * 4;
+      if (i + 4 <= end) {
+        const f32x4 x = X[k], y = Y[k], z = Z[k];
+        *reinterpret_cast<f32x4*>(d + i) = f32x4{seed(x[0] - tgt(y[0]), z[0]), seed(x[1] - tgt(y[1]), z[1]),
+                                                 seed(x[2] - tgt(y[2]), z[2]), seed(x[3] - tgt(y[3]), z[3])};
+      } else {
+        for (long long j = i; j < end; ++j) d[j] = seed(a[j] - tgt(b[j]), n[j]);
+      }
+    }
+  } else {
+    for (long long i = begin + threadIdx.x; i < end; i += 256) d[i] = seed(a[i] - tgt(b[i]), n[i]);
+  }
+}
+
 bool make_loss_geom(LossGeom& g, int B, int Vu, long long plane_u, int Vs, long long plane_s, int levels, int t_rev) {
   if (B <= 0 || Vu <= 0 || Vs <= 0 || plane_u <= 0 || plane_s <= 0 || levels <= 0 || plane_u % levels) return false;
   g.plane_u = plane_u / levels; g.plane_s = plane_s;
@@ -217,5 +282,31 @@ extern "C" int pangu_weighted_l1_loss_bwd(pangu_stream_t stream, const float* ou
   const float inv_nu = 1.0f / (float)((double)B * Vu * (double)plane_u), inv_ns = 1.0f / (float)((double)g.planes_s * (double)plane_s);
   hipLaunchKernelGGL(l1_loss_bwd_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, out, target, out_surface, target_surface,
                      w_upper, w_surface, grad, d_out, d_out_surface, g, st, inv_nu, inv_ns);
+  return pangu_launch_status();
+}
+
+extern "C" int pangu_rollout_l1_seed_bwd(pangu_stream_t stream, const float* out, const float* target, const float* out_surface,
+                                         const float* target_surface, const float* w_upper, const float* w_surface,
+                                         const float* grad, const float* d_next, const float* d_next_surface,
+                                         const float* std_upper, const float* std_surface, float* d_out, float* d_out_surface,
+                                         int B, int Vu, long long plane_u, int Vs, long long plane_s, int levels,
+                                         int target_levels_reversed, const float* t_mean_upper, const float* t_std_upper,
+                                         const float* t_mean_surface, const float* t_std_surface) {
+  if (!out || !target || !out_surface || !target_surface || !w_upper || !w_surface || !grad || !d_out || !d_out_surface) return PANGU_E_NULL;
+  if ((d_next != nullptr) != (d_next_surface != nullptr)) return PANGU_E_NULL;      // both or neither
+  if (d_next && (!std_upper || !std_surface)) return PANGU_E_NULL;
+  LossGeom g;
+  TargetStats st;
+  if (!make_loss_geom(g, B, Vu, plane_u, Vs, plane_s, levels, target_levels_reversed)) return PANGU_E_SHAPE;
+  if (!make_stats(st, t_mean_upper, t_std_upper, t_mean_surface, t_std_surface)) return PANGU_E_NULL;
+  const int nb = g.planes_u * g.chunks_u + g.planes_s * g.chunks_s;
+  const float inv_nu = 1.0f / (float)((double)B * Vu * (double)plane_u), inv_ns = 1.0f / (float)((double)g.planes_s * (double)plane_s);
+  if (!d_next)          // the last step of a chain: the loss gradient alone, by the very kernel of pangu_weighted_l1_loss_bwd
+    hipLaunchKernelGGL(l1_loss_bwd_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, out, target, out_surface, target_surface,
+                       w_upper, w_surface, grad, d_out, d_out_surface, g, st, inv_nu, inv_ns);
+  else
+    hipLaunchKernelGGL(rollout_l1_seed_bwd_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, out, target, out_surface,
+                       target_surface, w_upper, w_surface, grad, d_next, d_next_surface, std_upper, std_surface, d_out,
+                       d_out_surface, g, st, inv_nu, inv_ns);
   return pangu_launch_status();
 }

@@ -64,6 +64,8 @@ class DevicePrefetcher:
     flip_levels   the reader delivers ascending levels: reverse the pressure-level axis (dim -3) of input / target.
     fuse_flip     with flip_levels: do NOT move any data; batches are yielded in file order and `self.levels_reversed` is True --
                   pass it on (`train_step(..., levels_reversed=pf.levels_reversed)`).  False: a device-side `flip` per field.
+                  The device-side flip touches batch elements 0 and 2 only, so a multi-target feed (train.rollout_train_step:
+                  target_2, target_3, ... ride in `*rest`) uses fuse_flip=True, which reverses every target by addressing.
     depth         batches staged ahead of the consumer (>= 1; 2 hides the copy behind a per-step host sync).
     threaded      False: stage on the consumer's thread (the pre-round-6 behaviour; for debugging / comparison).
     copy_threads  host threads of one staging copy (default_copy_threads()).

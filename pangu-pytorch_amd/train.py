@@ -340,6 +340,24 @@ def _owns_dropped_branches(grad_sync):
     return isinstance(getattr(grad_sync, "__self__", None), FlatGradSync)
 
 
+def _optimizer_tail(optimizer, grad_sync):
+    """What follows the backward in train_step / rollout_train_step: the gradient sync, then the optimizer step in which parameters
+    without a gradient (DropPath-dropped branches) get the reference's zero-gradient update."""
+    if grad_sync is not None:
+        grad_sync()
+        optimizer.step()
+    elif isinstance(optimizer, HipAdam):
+        # a DropPath-dropped branch is not computed here, so its parameters come back without a gradient; the reference
+        # computes the branch, multiplies by zero and hands Adam ZERO gradients (moments decay, weight decay applies)
+        optimizer.step(missing_as_zero=True)
+    else:
+        for group in optimizer.param_groups:
+            for p in group["params"]:
+                if p.requires_grad and p.grad is None:
+                    p.grad = torch.zeros_like(p)
+        optimizer.step()
+
+
 def train_step(model, optimizer, batch, statistics, maps, const_h, stats_last=None, grad_sync=None, levels_reversed=False):
     """One optimisation step (reference pangu_sample.py:45-77). batch = (input, input_surface, target, target_surface).
     `grad_sync` (optional callable) runs between backward and optimizer.step(): the data-parallel gradient
@@ -362,17 +380,223 @@ def train_step(model, optimizer, batch, statistics, maps, const_h, stats_last=No
     lean = grad_sync is None or _owns_dropped_branches(grad_sync)
     with ops.dropped_branch_grads("none" if lean else "zeros"):
         loss.backward()
-    if grad_sync is not None:
-        grad_sync()
-        optimizer.step()
-    elif isinstance(optimizer, HipAdam):
-        # a DropPath-dropped branch is not computed here, so its parameters come back without a gradient; the reference
-        # computes the branch, multiplies by zero and hands Adam ZERO gradients (moments decay, weight decay applies)
-        optimizer.step(missing_as_zero=True)
-    else:
-        for group in optimizer.param_groups:
-            for p in group["params"]:
-                if p.requires_grad and p.grad is None:
-                    p.grad = torch.zeros_like(p)
-        optimizer.step()
+    _optimizer_tail(optimizer, grad_sync)
     return loss.detach()
+
+
+# ---- multi-step (rollout) fine-tuning ---------------------------------------------------------------------------------------
+
+
+def _rollout_seed_torch(output, output_surface, target, target_surface, grad, d_next, d_next_surface, stats_last,
+                        target_levels_reversed=False):
+    """Torch form of `pangu_rollout_l1_seed_bwd` (what RolloutStepFn falls back to for tensors the HIP loss does not take): the
+    gradient entering the model's output at one step of a chain = autograd's gradient of grad * weighted_l1_loss PLUS the next
+    step's input gradient taken back through `rollout.norm_back` (out * std + mean: a multiply by std; one rounding, then the add)."""
+    o, o_s = output.detach().requires_grad_(True), output_surface.detach().requires_grad_(True)
+    with torch.enable_grad():
+        loss = _weighted_l1_loss_torch(o, o_s, target, target_surface, target_levels_reversed, stats_last)
+    d_o, d_os = torch.autograd.grad(loss, (o, o_s), grad.to(loss.dtype))
+    if d_next is not None:
+        _, s_std, _, u_std = stats_last
+        d_o, d_os = d_o + d_next * u_std, d_os + d_next_surface * s_std
+    return d_o, d_os
+
+
+class RolloutStepFn(torch.autograd.Function):
+    """One lead time of a K-step fine-tune, after the model: (out, out_surface) -> (loss_k, next_upper, next_surface).
+    next_upper / next_surface are the PHYSICAL fields the forward's last kernel wrote under `ops.scatter_denorm` (the next step's
+    input; None at the last step); they enter as plain buffers and leave as outputs of this node, so that the gradient the next
+    step's input receives arrives HERE.  The backward is one launch (csrc/loss.hip `pangu_rollout_l1_seed_bwd`):
+    d_out = d loss_k + d_next * std, written over the incoming d_next buffer.  The last step gets d_next = None
+    (`set_materialize_grads(False)`) and runs the loss backward's own kernel."""
+
+    @staticmethod
+    def forward(ctx, output, output_surface, target, target_surface, next_upper, next_surface, target_levels_reversed, stats_last):
+        ctx.set_materialize_grads(False)
+        if stats_last is None:
+            raise ValueError("RolloutStepFn: stats_last is required (the fed-back fields are de-normalised with it)")
+        rev = bool(target_levels_reversed)
+        nxt = (None, None) if next_upper is None else (next_upper.detach(), next_surface.detach())
+        ctx.hip = _hip_loss_ok(output, output_surface, target, target_surface)
+        if not ctx.hip:
+            ctx.save_for_backward(output, output_surface, target, target_surface)
+            ctx.rev, ctx.stats_last = rev, stats_last
+            return (_weighted_l1_loss_torch(output, output_surface, target, target_surface, rev, stats_last),) + nxt
+        from . import _lib
+        wu, ws = _weights_on(output.device, torch.float32)
+        with torch.cuda.device(output.device):
+            loss = WeightedL1LossFn._forward(ctx, _lib.load(), wu, ws, output, output_surface, target, target_surface, rev, stats_last)
+        return (loss,) + nxt
+
+    @staticmethod
+    def backward(ctx, g, d_next, d_next_surface):
+        if not ctx.hip:
+            output, output_surface, target, target_surface = ctx.saved_tensors
+        else:
+            output, output_surface, target, target_surface, u_mean, u_std, s_mean, s_std = ctx.saved_tensors
+        if g is None:
+            g = torch.zeros((), dtype=torch.float32, device=output.device)
+        if (d_next is None) != (d_next_surface is None):        # one field of the next step's input was never read
+            if d_next is None:
+                d_next = torch.zeros_like(output)
+            else:
+                d_next_surface = torch.zeros_like(output_surface)
+        if not ctx.hip:
+            return _rollout_seed_torch(output, output_surface, target, target_surface, g, d_next, d_next_surface, ctx.stats_last,
+                                       ctx.rev) + (None,) * 6
+        from . import _lib
+        from .ops import _stream
+        wu, ws = _weights_on(output.device, torch.float32)
+        g = g.to(torch.float32).contiguous()
+        if d_next is None:
+            d_o, d_os = torch.empty_like(output), torch.empty_like(output_surface)
+            np_ = (None, None)
+        else:
+            # in place: the incoming buffers are this node's alone (the gradient of a tensor only the next step's model read)
+            d_o, d_os = (t if t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0
+                         else t.to(torch.float32).clone(memory_format=torch.contiguous_format) for t in (d_next, d_next_surface))
+            if d_o.shape != output.shape or d_os.shape != output_surface.shape:
+                raise RuntimeError(f"rollout step: next-step input gradients {tuple(d_o.shape)} / {tuple(d_os.shape)} for outputs "
+                                   f"{tuple(output.shape)} / {tuple(output_surface.shape)}")
+            np_ = (d_o.data_ptr(), d_os.data_ptr())
+        with torch.cuda.device(output.device):
+            _lib.check(_lib.load().pangu_rollout_l1_seed_bwd(
+                _stream(output), output.data_ptr(), target.data_ptr(), output_surface.data_ptr(), target_surface.data_ptr(),
+                wu.data_ptr(), ws.data_ptr(), g.data_ptr(), *np_, u_std.data_ptr(), s_std.data_ptr(), d_o.data_ptr(), d_os.data_ptr(),
+                *ctx.geom, int(ctx.rev), u_mean.data_ptr(), u_std.data_ptr(), s_mean.data_ptr(), s_std.data_ptr()),
+                "rollout_l1_seed_bwd")
+        return d_o, d_os, None, None, None, None, None, None
+
+
+def _check_rollout_batch(batch, stats_last, lead_weights):
+    batch = tuple(batch)
+    if len(batch) < 4 or len(batch) % 2:
+        raise ValueError("rollout_train_step: batch = (input, input_surface, target_1, target_surface_1, ..., target_K, "
+                         f"target_surface_K): got {len(batch)} tensors (the target list is empty or odd)")
+    K = len(batch) // 2 - 1
+    if stats_last is None or len(stats_last) != 4:
+        raise ValueError("rollout_train_step: stats_last = (s_mean, s_std, u_mean, u_std) is required: the fed-back fields are "
+                         "de-normalised with it, and the targets are in physical units")
+    lam = [1.0 / K] * K if lead_weights is None else [float(w) for w in lead_weights]
+    if len(lam) != K:
+        raise ValueError(f"rollout_train_step: {len(lam)} lead_weights for K = {K} lead times")
+    inp, inp_s = batch[0], batch[1]
+    if inp.dim() != 5 or inp_s.dim() != 4 or inp_s.shape[0] != inp.shape[0] or inp_s.shape[-2:] != inp.shape[-2:]:
+        raise ValueError(f"rollout_train_step: input {tuple(inp.shape)} / input_surface {tuple(inp_s.shape)}: expected "
+                         "(1, 5, 13, LAT, LON) / (1, 4, LAT, LON)")
+    if inp.shape[0] != 1:
+        raise ValueError(f"rollout_train_step: the per-rank batch is one sample (as in the reference), got B = {inp.shape[0]}")
+    for k in range(K):
+        t, t_s = batch[2 + 2 * k], batch[3 + 2 * k]
+        if t.shape != inp.shape or t_s.shape != inp_s.shape:
+            raise ValueError(f"rollout_train_step: target {k + 1} is {tuple(t.shape)} / {tuple(t_s.shape)}, the fields are "
+                             f"{tuple(inp.shape)} / {tuple(inp_s.shape)}")
+    if not all(t.is_cuda for t in batch):
+        raise RuntimeError("rollout_train_step: the batch must live on the model's HIP device (got CPU tensors); there is no CPU "
+                           "fallback")
+    if any(t.device != inp.device for t in batch):
+        raise RuntimeError("rollout_train_step: the batch tensors are on different devices")
+    return batch, K, lam
+
+
+def _weighted_total(losses, lam):
+    total = losses[0] * lam[0]
+    for l, w in zip(losses[1:], lam[1:]):
+        total = total + l * w
+    return total
+
+
+def rollout_train_step(model, optimizer, batch, statistics, maps, const_h, stats_last, *, lead_weights=None, checkpoint=False,
+                       grad_sync=None, levels_reversed=False):
+    """One optimisation step on a loss summed over K autoregressive 24 h steps, gradients flowing back through the fed-back state.
+    batch = (input, input_surface, target_1, target_surface_1, ..., target_K, target_surface_K), targets in PHYSICAL units, one
+    sample (what data.DevicePrefetcher yields with extra `*rest` tensors; K = 1 is train_step's batch and train_step's result).
+    total = sum_k lead_weights[k] * loss_k (default 1/K each).  Returns (total, per_step): detached device tensors of shape () and
+    (K,); nothing in here waits for the device.
+
+    Step k runs the model inside `ops.scatter_denorm`, so its last kernel also writes the physical fields of step k+1 (the two
+    roundings of rollout.norm_back, no extra pass); the loss is `pangu_weighted_l1_loss_fwd`; and the backward of each step starts
+    with ONE launch that forms d loss_k + (gradient of step k+1's input) * std (RolloutStepFn).
+    `levels_reversed` applies to step 0's input and to every target; fed-back fields are in the model's level order.
+
+    checkpoint=False: one autograd graph over all K steps, one backward (memory grows by one step's activations per lead time);
+    works with a dist.FlatGradSync method as `grad_sync` (its hooks fire once per parameter).
+    checkpoint=True: pass 1 runs the K forwards keeping only each step's two input fields (0.6 GB per lead time) and the host RNG
+    state in front of it; then, last step first, each step is re-run with gradients under that RNG state (the same DropPath draws),
+    its loss and backward run with the d_next of the step after it, and its input gradient is kept for the step before it.  Peak
+    memory is one step's.  The host RNG ends where pass 1 left it, as with checkpoint=False.  The DropPath counters (`n_dropped`,
+    `n_dropped_branch`) count the recomputed forwards too: the branches of every step but the last are counted twice.  Not with a FlatGradSync method
+    (its per-parameter hooks would fire K times): RuntimeError; any other `grad_sync` callable runs after the last backward.
+
+    Dropped-branch contract and optimizer tail: train_step's; a parameter is without a gradient only if its branch was dropped in
+    all K steps."""
+    batch, K, lam = _check_rollout_batch(batch, stats_last, lead_weights)
+    if checkpoint and grad_sync is not None and _owns_dropped_branches(grad_sync):
+        raise RuntimeError("rollout_train_step(checkpoint=True) runs K backward passes, and a dist.FlatGradSync's per-parameter hooks "
+                           "would fire (and launch its buckets) K times: use checkpoint=False with FlatGradSync, or another grad_sync")
+    from . import ops
+    inp, inp_s = batch[0], batch[1]
+    targets = [(batch[2 + 2 * k], batch[3 + 2 * k]) for k in range(K)]
+    consts = (statistics, maps, const_h)
+    lean = grad_sync is None or _owns_dropped_branches(grad_sync)
+    policy = "none" if lean else "zeros"
+    optimizer.zero_grad(set_to_none=True)
+
+    def forward_step(k, cur, cur_s, feed):
+        """(out, out_surface, next_upper, next_surface): the model on step k's input; with `feed`, its last kernel also writes the
+        next step's physical input fields."""
+        rev = levels_reversed and k == 0
+        if not feed:
+            return model(cur, cur_s, *consts, levels_reversed=rev) + (None, None)
+        nxt, nxt_s = torch.empty_like(inp), torch.empty_like(inp_s)
+        with ops.scatter_denorm(nxt, nxt_s, stats_last):
+            return model(cur, cur_s, *consts, levels_reversed=rev) + (nxt, nxt_s)
+
+    if not checkpoint:
+        cur, cur_s, losses = inp, inp_s, []
+        for k in range(K):
+            out, out_s, nxt, nxt_s = forward_step(k, cur, cur_s, k + 1 < K)
+            loss_k, cur, cur_s = RolloutStepFn.apply(out, out_s, *targets[k], nxt, nxt_s, levels_reversed, stats_last)
+            losses.append(loss_k)
+        total = _weighted_total(losses, lam)
+        with ops.dropped_branch_grads(policy):
+            total.backward()
+        _optimizer_tail(optimizer, grad_sync)
+        return total.detach(), torch.stack([l.detach() for l in losses])
+
+    # pass 1: the same forwards (same kernels: the fed-back fields and every out_k are those of the other mode, bit for bit); each
+    # step's graph dies with its outputs, only the step's input fields and the RNG state in front of it are kept
+    fields, rng = [(inp, inp_s)], []
+    for k in range(K - 1):
+        rng.append(torch.get_rng_state())
+        out, out_s, nxt, nxt_s = forward_step(k, *fields[k], True)
+        del out, out_s
+        fields.append((nxt, nxt_s))
+    rng.append(torch.get_rng_state())
+    losses, d_next, rng_end = [None] * K, (None, None), None
+    for k in range(K - 1, -1, -1):
+        if k < K - 1:
+            torch.set_rng_state(rng[k])
+        cur, cur_s = fields[k]
+        if k > 0:                                     # a fed-back state: its gradient is the d_next of the step before
+            cur.requires_grad_(True)
+            cur_s.requires_grad_(True)
+        out, out_s, _, _ = forward_step(k, cur, cur_s, False)
+        if k == K - 1:
+            rng_end = torch.get_rng_state()           # where one pass over all K steps leaves the generator
+        nxt, nxt_s = fields[k + 1] if k + 1 < K else (None, None)
+        loss_k, nxt, nxt_s = RolloutStepFn.apply(out, out_s, *targets[k], nxt, nxt_s, levels_reversed, stats_last)
+        losses[k] = loss_k.detach()
+        roots, seeds = [loss_k], [torch.full((), lam[k], dtype=loss_k.dtype, device=loss_k.device)]
+        if d_next[0] is not None:
+            roots += [nxt, nxt_s]
+            seeds += list(d_next)
+        del out, out_s
+        with ops.dropped_branch_grads(policy):
+            torch.autograd.backward(roots, seeds)
+        d_next = (cur.grad, cur_s.grad) if k > 0 else (None, None)
+        if k + 1 < K:
+            fields[k + 1] = None
+    torch.set_rng_state(rng_end)
+    _optimizer_tail(optimizer, grad_sync)
+    return _weighted_total(losses, lam), torch.stack(losses)
