@@ -1,7 +1,8 @@
-"""Forward compositions of the HIP kernels for each reference layer (inference path, no autograd graph).
+"""Compositions of the HIP kernels for each reference layer, and the whole-model training forward of both precisions.
 
-Token tensors are (B, N, C); B is folded into rows for projections / LayerNorm and looped for the
-geometry-dependent kernels (the reference itself is B=1 only, models/layers.py:219,227).
+The functions behind the modules of layers.py take token tensors (B, N, C); B is folded into rows for projections / LayerNorm and
+looped for the geometry-dependent kernels (the reference itself is B=1 only, models/layers.py:219,227).  Their autograd arm and the
+training driver `forward_train` share the `sample_*` functions on 2-D (N, C) rows: the one call site of each layer Function.
 """
 import torch
 
@@ -76,30 +77,11 @@ def mlp(m, x2d):
     return ops.linear(h, _layers.eff_weight(m.linear2), m.linear2.bias)
 
 
-def earth_block(blk, x, Z, H, W, roll, out=None):
-    """x (B,N,C) -> (B,N,C).  reference layers.py:183-253 as 5 kernel launches per sample (qkv, attention core, proj+LN+residual, MLP-up+GELU, MLP-down+LN+residual)."""
-    B, N, C = x.shape
+def _block_rows(blk, x2, B, Z, H, W, roll, out=None):
+    """The inference composition of a block on the 2-D rows x2 (B*N, C) of B samples -> (B*N, C), written into the 2-D `out` if
+    given: 5 kernel launches per sample (qkv, attention core, proj+LN+residual, MLP-up+GELU, MLP-down+LN+residual)."""
+    N, C = x2.shape[0] // B, x2.shape[1]
     att = blk.attention
-    if _train_path(blk, x):
-        outs = []
-        # out as a 2-D (N, C) row-strided tensor (B = 1): the block function writes its result there (a half of the
-        # skip-concat buffer, PanguModel._forward_f32) -- no copy
-        direct = out is not None and out.dim() == 2 and B == 1
-        extra = ((out,) if direct else None, None) + _layers.lora_args(blk.linear.linear1, blk.linear.linear2, att.linear1, att.linear2)
-        for xb in _samples(x):
-            s1, s2 = drop_path_scales(blk)
-            outs.append(EarthBlockFn.apply(
-                xb, blk.norm1.weight, blk.norm1.bias, blk.norm2.weight, blk.norm2.bias,
-                _layers.eff_weight(blk.linear.linear1), blk.linear.linear1.bias,
-                _layers.eff_weight(blk.linear.linear2), blk.linear.linear2.bias, att.earth_specific_bias,
-                _layers.eff_weight(att.linear1), att.linear1.bias, _layers.eff_weight(att.linear2), att.linear2.bias,
-                (Z, H, W, att.head_number, bool(roll)), s1, s2, *extra))
-        y = _stack(outs, B)
-        if out is not None and not direct:
-            out.copy_(y)
-            return out
-        return y
-    x2 = _tok2d(x)
     s1, s2 = drop_path_scales(blk)
     if s1 != 0.0:
         qkv = ops.linear(x2, _layers.eff_weight(att.linear1), att.linear1.bias)      # (B*N, 3C)
@@ -122,85 +104,143 @@ def earth_block(blk, x, Z, H, W, roll, out=None):
             x1 = ops.ln_residual(y, x2, blk.norm1.weight, blk.norm1.bias, branch_scale=s1)
     else:
         x1 = x2
-    # out may be the 2-D (N, C) row-strided half of the skip-concat buffer that PanguModel._forward_f32 hands to the LAST block
-    # of layer 0 / 3 on the autograd path; a partially frozen fine-tune (nothing upstream of this block trains) lands here
-    o2 = None if out is None else (out if out.dim() == 2 else _tok2d(out))
-    if s2 != 0.0:
-        if C in (192, 384):
-            h = ops.linear(x1, _layers.eff_weight(blk.linear.linear1), blk.linear.linear1.bias, act=ops.ACT_GELU)
-            x2o = ops.linear_ln_residual(h, _layers.eff_weight(blk.linear.linear2), blk.linear.linear2.bias, x1,
-                                         blk.norm2.weight, blk.norm2.bias, out=o2, branch_scale=s2)
-        else:
-            m = mlp(blk.linear, x1)
-            x2o = ops.ln_residual(m, x1, blk.norm2.weight, blk.norm2.bias, out=o2, branch_scale=s2)
-    else:
-        x2o = x1
-        if out is not None:
-            o2.copy_(x1)
-            x2o = o2
-    if out is not None:
-        return out.unsqueeze(0) if out.dim() == 2 else out
-    return x2o.view(B, N, C)
+    if s2 == 0.0:
+        return x1 if out is None else out.copy_(x1)
+    if C in (192, 384):
+        h = ops.linear(x1, _layers.eff_weight(blk.linear.linear1), blk.linear.linear1.bias, act=ops.ACT_GELU)
+        return ops.linear_ln_residual(h, _layers.eff_weight(blk.linear.linear2), blk.linear.linear2.bias, x1,
+                                      blk.norm2.weight, blk.norm2.bias, out=out, branch_scale=s2)
+    return ops.ln_residual(mlp(blk.linear, x1), x1, blk.norm2.weight, blk.norm2.bias, out=out, branch_scale=s2)
+
+
+# ---- one sample, one layer, on 2-D rows (N, C): THE call site of each layer Function.  sh: None for fp32, the model's
+# fused_bf16.WeightShadow for bf16.  A frozen fp32 layer (no trainable parameter, no gradient arriving: _train_path false) takes the
+# fp32 inference composition instead of its Function; a bf16 layer always runs the Function.
+def sample_block(blk, x, Z, H, W, roll, out=None, sh=None):
+    """reference layers.py:183-253 for one sample, x (N, C) -> (N, C).  out: the 2-D (N, C) row-strided tensor the block writes its
+    result into (a half of the skip-concat buffer, concat_halves) -- no copy."""
+    if sh is None and not _train_path(blk, x):
+        return _block_rows(blk, x, 1, Z, H, W, roll, out)
+    att = blk.attention
+    s1, s2 = drop_path_scales(blk)
+    return EarthBlockFn.apply(
+        x, blk.norm1.weight, blk.norm1.bias, blk.norm2.weight, blk.norm2.bias,
+        _layers.eff_weight(blk.linear.linear1), blk.linear.linear1.bias,
+        _layers.eff_weight(blk.linear.linear2), blk.linear.linear2.bias, att.earth_specific_bias,
+        _layers.eff_weight(att.linear1), att.linear1.bias, _layers.eff_weight(att.linear2), att.linear2.bias,
+        (Z, H, W, att.head_number, bool(roll)), s1, s2, None if out is None else (out,), sh,
+        *_layers.lora_args(blk.linear.linear1, blk.linear.linear2, att.linear1, att.linear2))
+
+
+def _embed_rows(m, inp, inp_surface, consts, levels_reversed, out):
+    a_s, a_u = ops.patch_embed_gather(inp, inp_surface, *consts, levels_reversed)
+    n_s = a_s.shape[0]
+    ops.linear(a_s, m.conv_surface.weight, m.conv_surface.bias, out=out[:n_s])
+    ops.linear(a_u, m.conv.weight, m.conv.bias, out=out[n_s:])
+    return out
+
+
+def sample_embed(m, inp, inp_surface, consts, levels_reversed=False, sh=None):
+    """reference layers.py:40-93 for one sample: contiguous inp (5, 13, LAT, LON), inp_surface (4, LAT, LON); consts: embed_constants."""
+    if sh is None and not _train_path(m, inp, inp_surface):
+        LAT, LON = inp.shape[-2], inp.shape[-1]
+        x = torch.empty((8 * ((LAT + 3) // 4) * (LON // 4), m.conv.weight.shape[0]), dtype=torch.float32, device=inp.device)
+        return _embed_rows(m, inp, inp_surface, consts, levels_reversed, x)
+    return PatchEmbedFn.apply(m.conv.weight, m.conv.bias, m.conv_surface.weight, m.conv_surface.bias, inp, inp_surface, *consts,
+                              levels_reversed, sh)
+
+
+def sample_down(m, x, Z, H, W, skip_grad=None, sh=None):
+    """reference layers.py:432-459 for one sample.  skip_grad: the slot shared with PatchRecoverHalvesFn (see DownSampleFn)."""
+    if sh is None and not _train_path(m, x):
+        return ops.linear(ops.downsample_ln(x, m.norm.weight, m.norm.bias, Z, H, W), _layers.eff_weight(m.linear))
+    return DownSampleFn.apply(x, _layers.eff_weight(m.linear), m.norm.weight, m.norm.bias, (Z, H, W), skip_grad, sh,
+                              *_layers.lora_args(m.linear))
+
+
+def _up_rows(m, x2, B, Z, H2, W2, H):
+    y = ops.linear(x2, _layers.eff_weight(m.linear1))          # (B*N, 4Co)
+    N, Co, Nf = x2.shape[0] // B, y.shape[1] // 4, Z * H * 2 * W2
+    out = torch.empty((B * Nf, Co), dtype=torch.float32, device=x2.device)
+    for b in range(B):
+        g = ops.upsample_ln(y[b * N:(b + 1) * N], m.norm.weight, m.norm.bias, Z, H2, W2, H)
+        ops.linear(g, _layers.eff_weight(m.linear2), out=out[b * Nf:(b + 1) * Nf])
+    return out
+
+
+def sample_up(m, x, Z, H2, W2, H, sh=None):
+    """reference layers.py:474-499 for one sample."""
+    if sh is None and not _train_path(m, x):
+        return _up_rows(m, x, 1, Z, H2, W2, H)
+    return UpSampleFn.apply(x, _layers.eff_weight(m.linear1), _layers.eff_weight(m.linear2), m.norm.weight, m.norm.bias,
+                            (Z, H2, W2, H), sh, *_layers.lora_args(m.linear1, m.linear2))
+
+
+def forward_train(model, inp, inp_surface, statistics, maps, const_h, levels_reversed=False, sh=None):
+    """The autograd-enabled forward of the whole model (reference pangu_model.py:50-87), sample by sample on the per-sample
+    layers above: bf16 (sh = the model's WeightShadow, any B) and fp32 (sh None, B = 1: PanguModel._forward_dispatch)."""
+    B, LAT, LON = inp.shape[0], inp.shape[-2], inp.shape[-1]
+    H4, W4 = (LAT + 3) // 4, LON // 4
+    H2, W2 = (H4 + 1) // 2, W4 // 2
+    consts = embed_constants(statistics, maps, const_h, LAT, LON, inp.device)
+    rec = model._output_layer
+
+    def run_layer(layer, x, H, W, out=None):
+        last = len(layer.blocks) - 1
+        for i, blk in enumerate(layer.blocks):
+            x = sample_block(blk, x, 8, H, W, i % 2 == 1, out if i == last else None, sh)
+        return x
+
+    res = []
+    for b in range(B):
+        x = sample_embed(model._input_layer, inp[b].contiguous(), inp_surface[b].contiguous(), consts, levels_reversed, sh)
+        halves = concat_halves(x)                 # layer 0 / layer 3 write straight into them
+        skip = run_layer(model.layers[0], x, H4, W4, halves[0])
+        skip_grad = [None, False]                 # [the concat path's gradient of `skip`, armed]: see DownSampleFn
+        x = sample_down(model.downsample, skip, 8, H4, W4, skip_grad, sh)
+        x = run_layer(model.layers[1], x, H2, W2)
+        x = run_layer(model.layers[2], x, H2, W2)
+        x = sample_up(model.upsample, x, 8, H2, W2, H4, sh)
+        x = run_layer(model.layers[3], x, H4, W4, halves[1])
+        res.append(PatchRecoverHalvesFn.apply(skip, x, rec.conv.weight, rec.conv.bias, rec.conv_surface.weight,
+                                              rec.conv_surface.bias, (H4 * W4, LAT, LON), skip_grad, sh))
+    return tuple(_stack(t, B) for t in zip(*res))
+
+
+# ---- the batched (B, N, C) functions behind the modules of layers.py, usable and differentiable on their own
+def earth_block(blk, x, Z, H, W, roll, out=None):
+    """x (B,N,C) -> (B,N,C), into the (B,N,C) `out` if given (a half of the inference concat buffer)."""
+    B, N, C = x.shape
+    if _train_path(blk, x):
+        y = _stack([sample_block(blk, xb, Z, H, W, roll) for xb in _samples(x)], B)
+        return y if out is None else out.copy_(y)
+    y = _block_rows(blk, _tok2d(x), B, Z, H, W, roll, None if out is None else _tok2d(out))
+    return y.view(B, N, C) if out is None else out
 
 
 def patch_embed(m, inp, inp_surface, statistics, maps, const_h, levels_reversed=False):
     """reference layers.py:40-93 -> (B, 8*181*360, 192)."""
-    B = inp.shape[0]
-    LAT, LON = inp.shape[-2], inp.shape[-1]
-    H4, W4 = (LAT + 3) // 4, LON // 4
-    n_s, n_u = H4 * W4, 7 * H4 * W4
-    dim = m.conv.weight.shape[0]
-    x = torch.empty((B, n_s + n_u, dim), dtype=torch.float32, device=inp.device)
+    B, LAT, LON = inp.shape[0], inp.shape[-2], inp.shape[-1]
     consts = embed_constants(statistics, maps, const_h, LAT, LON, inp.device)
     if _train_path(m, inp, inp_surface):
-        return _stack([PatchEmbedFn.apply(m.conv.weight, m.conv.bias, m.conv_surface.weight, m.conv_surface.bias,
-                                          inp[b].contiguous(), inp_surface[b].contiguous(), *consts, levels_reversed)
-                       for b in range(B)], B)
+        return _stack([sample_embed(m, inp[b].contiguous(), inp_surface[b].contiguous(), consts, levels_reversed) for b in range(B)], B)
+    x = torch.empty((B, 8 * ((LAT + 3) // 4) * (LON // 4), m.conv.weight.shape[0]), dtype=torch.float32, device=inp.device)
     for b in range(B):
-        a_s, a_u = ops.patch_embed_gather(inp[b].contiguous(), inp_surface[b].contiguous(), *consts, levels_reversed)
-        ops.linear(a_s, m.conv_surface.weight, m.conv_surface.bias, out=x[b, :n_s])
-        ops.linear(a_u, m.conv.weight, m.conv.bias, out=x[b, n_s:])
+        _embed_rows(m, inp[b].contiguous(), inp_surface[b].contiguous(), consts, levels_reversed, x[b])
     return x
 
 
-def down_sample(m, x, Z, H, W, skip_grad=None):
-    B, N, C = x.shape
+def down_sample(m, x, Z, H, W):
+    B = x.shape[0]
+    rows = _samples(x) if _train_path(m, x) else [_tok2d(x[b:b + 1]) for b in range(B)]
+    return _stack([sample_down(m, xb, Z, H, W) for xb in rows], B)
+
+
+def up_sample(m, x, Z, H2, W2, H):
+    B = x.shape[0]
     if _train_path(m, x):
-        return _stack([DownSampleFn.apply(xb, _layers.eff_weight(m.linear), m.norm.weight, m.norm.bias, (Z, H, W),
-                                          skip_grad if B == 1 else None, None, *_layers.lora_args(m.linear)) for xb in _samples(x)], B)
-    outs = []
-    for b in range(B):
-        g = ops.downsample_ln(_tok2d(x[b:b + 1]), m.norm.weight, m.norm.bias, Z, H, W)
-        outs.append(ops.linear(g, _layers.eff_weight(m.linear)))
-    return torch.stack(outs, 0) if B > 1 else outs[0].unsqueeze(0)
-
-
-def up_sample(m, x, Z, H2, W2, H, out=None):
-    B, N, C2 = x.shape
-    if _train_path(m, x):
-        y = _stack([UpSampleFn.apply(xb, _layers.eff_weight(m.linear1), _layers.eff_weight(m.linear2), m.norm.weight, m.norm.bias,
-                                     (Z, H2, W2, H), None, *_layers.lora_args(m.linear1, m.linear2)) for xb in _samples(x)], B)
-        if out is not None:
-            out.copy_(y)
-            return out
-        return y
-    y = ops.linear(_tok2d(x), _layers.eff_weight(m.linear1))          # (B*N, 4Co)
-    Co = y.shape[1] // 4
-    Nf = Z * H * 2 * W2
-    if out is None:
-        out = torch.empty((B, Nf, Co), dtype=torch.float32, device=x.device)
-    for b in range(B):
-        g = ops.upsample_ln(y[b * N:(b + 1) * N], m.norm.weight, m.norm.bias, Z, H2, W2, H)
-        ops.linear(g, _layers.eff_weight(m.linear2), out=_tok2d(out[b:b + 1]))
-    return out
-
-
-def patch_recover_halves(m, skip, x, Z, H, W, LAT=721, LON=1440, skip_grad=None):
-    """Training path, B = 1: reference layers.py:511-545 on cat(skip, x) where skip / x (1, N, C) are the two halves of one
-    (N, 2C) buffer (PanguModel._forward_f32)."""
-    o, os_ = PatchRecoverHalvesFn.apply(skip[0], x[0], m.conv.weight, m.conv.bias, m.conv_surface.weight, m.conv_surface.bias,
-                                        (H * W, LAT, LON), skip_grad)
-    return o.unsqueeze(0), os_.unsqueeze(0)
+        return _stack([sample_up(m, xb, Z, H2, W2, H) for xb in _samples(x)], B)
+    return _up_rows(m, _tok2d(x), B, Z, H2, W2, H).view(B, Z * H * 2 * W2, -1)
 
 
 def patch_recover(m, x, Z, H, W, LAT=721, LON=1440):

@@ -1,11 +1,10 @@
-"""bf16 forward of the whole model (BASELINE configs[2]/[4]): bf16 activations + bf16 weight shadows, fp32 LayerNorm /
-softmax / accumulation, fp32 output fields.  `forward` is the inference path (same launch sequence as the fp32 one),
-`forward_train` the autograd path on the layer Functions of autograd.py."""
+"""bf16 precision of the whole model (BASELINE configs[2]/[4]): bf16 activations + bf16 weight shadows, fp32 LayerNorm /
+softmax / accumulation, fp32 output fields.  `WeightShadow` keeps the bf16 images of the fp32 parameters, `forward` is the
+inference path (same launch sequence as the fp32 one); training runs the driver of fused.py with the model's WeightShadow."""
 import torch
 
 from . import ops, ops_bf16 as ob
-from .autograd import DownSampleFn, EarthBlockFn, PatchEmbedFn, PatchRecoverHalvesFn, UpSampleFn
-from .fused import concat_halves, drop_path_scales, embed_constants
+from .fused import drop_path_scales, embed_constants
 
 
 def _stamp(p):
@@ -271,48 +270,5 @@ def forward(model, inp, inp_surface, statistics, maps, const_h, levels_reversed=
         outs.append(o)
         outs_s.append(os_)
     if B == 1:                                   # no 286 MB stack copy for the usual single sample
-        return outs[0].unsqueeze(0), outs_s[0].unsqueeze(0)
-    return torch.stack(outs, 0), torch.stack(outs_s, 0)
-
-
-def forward_train(model, inp, inp_surface, statistics, maps, const_h, levels_reversed=False):
-    """Autograd-enabled bf16 forward of the whole model (B looped; the reference is B = 1 per rank)."""
-    sh = model._shadow
-    B = inp.shape[0]
-    LAT, LON = inp.shape[-2], inp.shape[-1]
-    H4, W4 = (LAT + 3) // 4, LON // 4
-    H2, W2 = (H4 + 1) // 2, W4 // 2
-    consts = embed_constants(statistics, maps, const_h, LAT, LON, inp.device)
-    emb, rec, dn, up = model._input_layer, model._output_layer, model.downsample, model.upsample
-
-    def run_layer(layer, x, Z, H, W, out=None):
-        last = len(layer.blocks) - 1
-        for i, blk in enumerate(layer.blocks):
-            att = blk.attention
-            s1, s2 = drop_path_scales(blk)
-            x = EarthBlockFn.apply(
-                x, blk.norm1.weight, blk.norm1.bias, blk.norm2.weight, blk.norm2.bias, blk.linear.linear1.weight,
-                blk.linear.linear1.bias, blk.linear.linear2.weight, blk.linear.linear2.bias, att.earth_specific_bias,
-                att.linear1.weight, att.linear1.bias, att.linear2.weight, att.linear2.bias,
-                (Z, H, W, att.head_number, i % 2 == 1), s1, s2, (out,) if out is not None and i == last else None, sh)
-        return x
-
-    outs, outs_s = [], []
-    for b in range(B):
-        x = PatchEmbedFn.apply(emb.conv.weight, emb.conv.bias, emb.conv_surface.weight, emb.conv_surface.bias,
-                               inp[b].contiguous(), inp_surface[b].contiguous(), *consts, levels_reversed, sh)
-        halves = concat_halves(x)
-        skip = run_layer(model.layers[0], x, 8, H4, W4, out=halves[0])
-        skip_grad = [None, False]                 # [the concat path's gradient of `skip`, armed]: see DownSampleFn
-        x = DownSampleFn.apply(skip, dn.linear.weight, dn.norm.weight, dn.norm.bias, (8, H4, W4), skip_grad, sh)
-        x = run_layer(model.layers[1], x, 8, H2, W2)
-        x = run_layer(model.layers[2], x, 8, H2, W2)
-        x = UpSampleFn.apply(x, up.linear1.weight, up.linear2.weight, up.norm.weight, up.norm.bias, (8, H2, W2, H4), sh)
-        x = run_layer(model.layers[3], x, 8, H4, W4, out=halves[1])
-        o, os_ = PatchRecoverHalvesFn.apply(skip, x, rec.conv.weight, rec.conv.bias, rec.conv_surface.weight,
-                                            rec.conv_surface.bias, (H4 * W4, LAT, LON), skip_grad, sh)
-        outs.append(o)
-        outs_s.append(os_)
-    if B == 1:
         return outs[0].unsqueeze(0), outs_s[0].unsqueeze(0)
     return torch.stack(outs, 0), torch.stack(outs_s, 0)

@@ -7,6 +7,7 @@ reference's op chain: every forward calls hand-written gfx950 kernels through th
 all view/pad/roll/permute/crop steps folded into kernel address arithmetic.  nn.Linear / nn.Conv1d /
 nn.LayerNorm sub-modules are parameter containers only.
 """
+import math
 from collections import OrderedDict
 
 import torch
@@ -67,7 +68,6 @@ class LoraLinear(nn.Linear):
         self._init_lora(r, alpha)
 
     def _init_lora(self, r, alpha):
-        import math
         self.r, self.lora_alpha = int(r), alpha
         self.scaling = alpha / r
         w = self.weight
@@ -340,8 +340,8 @@ class DownSample(nn.Module):
         self.linear = nn.Linear(in_features=4 * dim, out_features=2 * dim, bias=False)
         self.norm = nn.LayerNorm(4 * dim)
 
-    def forward(self, x, Z, H, W, skip_grad=None):
-        return fused.down_sample(self, x, Z, H, W, skip_grad=skip_grad)
+    def forward(self, x, Z, H, W):
+        return fused.down_sample(self, x, Z, H, W)
 
 
 class UpSample(nn.Module):
@@ -353,8 +353,13 @@ class UpSample(nn.Module):
         self.linear2 = nn.Linear(output_dim, output_dim, bias=False)
         self.norm = nn.LayerNorm(output_dim)
 
-    def forward(self, x, Z=8, H2=91, W2=180, H=181, out=None):
-        return fused.up_sample(self, x, Z, H2, W2, H, out=out)
+    def forward(self, x, Z=8, H2=None, W2=None, H=None):
+        if H2 is None:       # the reference's forward(x): on its grid, W2 = 2 (H2 - 1) less one latitude row (layers.py:480-489)
+            H2 = (1 + math.isqrt(1 + 2 * (x.shape[1] // Z))) // 2
+            W2, H = 2 * (H2 - 1), 2 * H2 - 1
+        if Z * H2 * W2 != x.shape[1]:
+            raise RuntimeError(f"UpSample: {x.shape[1]} tokens are not a ({Z}, {H2}, {W2}) grid; pass Z, H2, W2, H")
+        return fused.up_sample(self, x, Z, H2, W2, H)
 
 
 class PatchRecovery_pretrain(nn.Module):

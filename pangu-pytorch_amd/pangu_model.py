@@ -11,7 +11,7 @@ from collections import OrderedDict
 import torch
 from torch import nn
 
-from . import ops
+from . import fused, ops
 from .layers import (DownSample, EarthSpecificLayer, PatchEmbedding_pretrain, PatchRecovery_pretrain, UpSample,
                      _trunc_normal_)
 
@@ -307,48 +307,43 @@ class PanguModel(nn.Module):
         return self._forward_dispatch(input, input_surface, statistics, maps, const_h, want_bf16, grad_path, rev)
 
     def _forward_dispatch(self, input, input_surface, statistics, maps, const_h, want_bf16, grad_path, levels_reversed=False):
+        args = (self, input, input_surface, statistics, maps, const_h, levels_reversed)
         if want_bf16:
             from . import fused_bf16
             if self._shadow is None:
                 self._shadow = fused_bf16.WeightShadow()
             if grad_path:
-                return fused_bf16.forward_train(self, input, input_surface, statistics, maps, const_h, levels_reversed)
-            return fused_bf16.forward(self, input, input_surface, statistics, maps, const_h, levels_reversed)
+                return fused.forward_train(*args, sh=self._shadow)
+            return fused_bf16.forward(*args)
+        if grad_path and input.shape[0] == 1:
+            return fused.forward_train(*args)
         if self._compact_bias and not grad_path:
             self._build_compact_bias()            # no-op while the tables exist (dropped with the weight shadows)
         return self._forward_f32(input, input_surface, statistics, maps, const_h, grad_path, levels_reversed)
 
-    def _forward_f32(self, input, input_surface, statistics, maps, const_h, grad_path, levels_reversed=False):
-        B = input.shape[0]
+    def _forward_f32(self, input, input_surface, statistics, maps, const_h, grad_path, levels_reversed=False):      # through the modules
+        B, LAT, LON = input.shape[0], input.shape[-2], input.shape[-1]
+        H4, W4 = (LAT + 3) // 4, LON // 4
+        H2, W2 = (H4 + 1) // 2, W4 // 2
         x = self._input_layer(input, input_surface, statistics, maps, const_h, levels_reversed)             # (B,521280,192)
         N, C = x.shape[1], x.shape[2]
+        if grad_path:
+            # plain concat.  Not on fused.forward_train: this arm is block-major (each block loops over the samples), the driver
+            # sample-major, so under train() the DropPath factors would be drawn from the host RNG in another order
+            skip = self.layers[0](x, 8, H4, W4)
+            x = self.downsample(skip, 8, H4, W4)
+            x = self.layers[1](x, 8, H2, W2)
+            x = self.layers[2](x, 8, H2, W2)
+            x = self.upsample(x, 8, H2, W2, H4)
+            x = self.layers[3](x, 8, H4, W4)
+            return self._output_layer(torch.cat((skip, x), dim=-1), 8, H4, W4)
         # skip connection: layer 0 writes its result into the left half, layer 3 into the right half of one
         # (B,N,2C) buffer, so the channel concat of reference pangu_model.py:81 costs no copy
-        if grad_path and B == 1:
-            # autograd path, one sample: layer 0 / layer 3 write straight into the two halves of one (N, 2C) buffer
-            from . import fused
-            halves = fused.concat_halves(x)
-            skip = self.layers[0](x, 8, 181, 360, out=halves[0])
-            skip_grad = [None, False]         # the skip connection's concat-path gradient, summed inside the down-sampling backward
-            x = self.downsample(skip, 8, 181, 360, skip_grad=skip_grad)
-            x = self.layers[1](x, 8, 91, 180)
-            x = self.layers[2](x, 8, 91, 180)
-            x = self.upsample(x)
-            x = self.layers[3](x, 8, 181, 360, out=halves[1])
-            return fused.patch_recover_halves(self._output_layer, skip, x, 8, 181, 360, skip_grad=skip_grad)
-        if grad_path:
-            skip = self.layers[0](x, 8, 181, 360)                 # autograd path, B > 1: plain concat
-            x = self.downsample(skip, 8, 181, 360)
-            x = self.layers[1](x, 8, 91, 180)
-            x = self.layers[2](x, 8, 91, 180)
-            x = self.upsample(x)
-            x = self.layers[3](x, 8, 181, 360)
-            return self._output_layer(torch.cat((skip, x), dim=-1), 8, 181, 360)
         cat = torch.empty((B, N, 2 * C), dtype=x.dtype, device=x.device)
-        skip = self.layers[0](x, 8, 181, 360, out=cat[:, :, :C])
-        x = self.downsample(skip, 8, 181, 360)
-        x = self.layers[1](x, 8, 91, 180)
-        x = self.layers[2](x, 8, 91, 180)
-        x = self.upsample(x)
-        self.layers[3](x, 8, 181, 360, out=cat[:, :, C:])
-        return self._output_layer(cat, 8, 181, 360)
+        skip = self.layers[0](x, 8, H4, W4, out=cat[:, :, :C])
+        x = self.downsample(skip, 8, H4, W4)
+        x = self.layers[1](x, 8, H2, W2)
+        x = self.layers[2](x, 8, H2, W2)
+        x = self.upsample(x, 8, H2, W2, H4)
+        self.layers[3](x, 8, H4, W4, out=cat[:, :, C:])
+        return self._output_layer(cat, 8, H4, W4)

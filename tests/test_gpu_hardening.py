@@ -240,6 +240,40 @@ def test_partially_frozen_finetune_f32(P, trainable):
             assert p.grad is None, k
 
 
+def test_frozen_block_rule_of_the_per_sample_block(P):
+    """fused.sample_block, the one call site of EarthBlockFn, with grad mode on and a 2-D row-strided half of a concat_halves
+    buffer as `out`: a frozen fp32 block whose input carries no gradient runs the inference kernels (bit-equal to the batched
+    block under no_grad), a frozen bf16 block runs the Function (bit-equal to the trainable block), and a gradient arriving at
+    the frozen fp32 block's input puts it on the Function too.  Every result is written into `out`."""
+    from pangu_pytorch_amd import fused, fused_bf16
+    C, roll, W = 192, True, 12
+    st = cases.STAGES[C]
+    geom = (st["Z"], st["H"], W, roll)
+    blk = P.layers.EarthSpecificBlock(C, 0.0, st["heads"], device="cuda").cuda().eval()
+    pre = cases.block_prefix(C, roll)
+    blk.load_state_dict({k: synth.synth_param(pre + k, s, "cuda") for k, s in cases.block_param_shapes(C).items()})
+    x = cases.block_input(C, W, "cuda")[0]
+
+    def run(x, sh, trainable, which):
+        blk.requires_grad_(trainable)
+        half = fused.concat_halves(x)[which]
+        half.zero_()
+        assert half.stride() == (2 * C, 1)
+        y = fused.sample_block(blk, x, *geom, out=half, sh=sh)
+        assert y.data_ptr() == half.data_ptr() and y.stride() == half.stride() and bool(half.abs().sum() > 0)
+        return y
+
+    assert torch.is_grad_enabled()
+    y = run(x, None, False, 0)
+    with torch.no_grad():
+        ref = blk(x.unsqueeze(0), *geom)[0]
+    assert y.grad_fn is None and torch.equal(y, ref)
+    xb, sh = x.to(BF), fused_bf16.WeightShadow()
+    yb, yb_train = run(xb, sh, False, 1), run(xb, sh, True, 1)
+    assert yb.dtype == BF and yb_train.grad_fn is not None and torch.equal(yb, yb_train.detach())
+    assert run(x.clone().requires_grad_(True), None, False, 0).grad_fn is not None
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_eval_forward_with_grad_is_the_inference_forward_and_recomputes_for_backward(P, dtype):
     """The reference's `test()` calls the model in eval() WITHOUT no_grad (models/pangu_sample.py:197-202).  Default
