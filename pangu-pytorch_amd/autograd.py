@@ -399,7 +399,8 @@ class PatchRecoverFn(torch.autograd.Function):
 class PatchRecoverHalvesFn(torch.autograd.Function):
     """The same layer on the channel concat of reference pangu_model.py:81 given as its two (N, C) halves, which are the two
     halves of ONE (N, 2C) buffer (layer 0 / layer 3 wrote them in place): no concat copy in the forward, and each half gets
-    its own DENSE gradient in the backward (two N = C products instead of row-strided views of one N = 2C product)."""
+    its own DENSE gradient in the backward (two N = C products instead of row-strided views of one N = 2C product).  The last
+    layer of the whole-model driver in training and inference: without a graph its forward is the inference recovery."""
 
     @staticmethod
     def forward(ctx, skip, x, cw, cb, sw, sb, geom, skip_grad=None, sh=None):

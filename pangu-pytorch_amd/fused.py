@@ -1,12 +1,13 @@
-"""Compositions of the HIP kernels for each reference layer, and the whole-model training forward of both precisions.
+"""Compositions of the HIP kernels for each reference layer, and the whole-model forward of both precisions, training and inference.
 
 The functions behind the modules of layers.py take token tensors (B, N, C); B is folded into rows for projections / LayerNorm and
 looped for the geometry-dependent kernels (the reference itself is B=1 only, models/layers.py:219,227).  Their autograd arm and the
-training driver `forward_train` share the `sample_*` functions on 2-D (N, C) rows: the one call site of each layer Function.
+whole-model driver `forward_model` share the `sample_*` functions on 2-D (N, C) rows: the one call site of each layer Function and
+of each layer's per-sample inference composition.
 """
 import torch
 
-from . import ops
+from . import ops, ops_bf16 as ob
 from .autograd import DownSampleFn, EarthBlockFn, MlpFn, PatchEmbedFn, PatchRecoverFn, PatchRecoverHalvesFn, UpSampleFn
 from . import layers as _layers      # (layers imports this module: attribute access at call time)
 
@@ -58,7 +59,7 @@ def embed_constants(statistics, maps, const_h, LAT, LON, dev):
 
 
 def concat_halves(x):
-    """The skip-concat buffer of reference pangu_model.py:81 for the autograd path, as its two (N, C) halves: layer 0 / layer 3
+    """The skip-concat buffer of reference pangu_model.py:81 of the whole-model driver, as its two (N, C) halves: layer 0 / layer 3
     write their results straight into them, so the concat costs no copy.  The halves SHARE the storage of one (N, 2C) buffer
     without being autograd views of it (a view returned by a custom Function whose base is written again -- the other half -- is
     refused by autograd).  x: (N, C) or (1, N, C), giving shape, dtype and device."""
@@ -113,14 +114,58 @@ def _block_rows(blk, x2, B, Z, H, W, roll, out=None):
     return ops.ln_residual(mlp(blk.linear, x1), x1, blk.norm2.weight, blk.norm2.bias, out=out, branch_scale=s2)
 
 
-# ---- one sample, one layer, on 2-D rows (N, C): THE call site of each layer Function.  sh: None for fp32, the model's
-# fused_bf16.WeightShadow for bf16.  A frozen fp32 layer (no trainable parameter, no gradient arriving: _train_path false) takes the
-# fp32 inference composition instead of its Function; a bf16 layer always runs the Function.
-def sample_block(blk, x, Z, H, W, roll, out=None, sh=None):
+def _block_rows_bf16(blk, sh, x, Z, H, W, roll, out=None):
+    """The bf16 inference composition of a block: x (N,C) bf16 -> (N,C) bf16.  DropPath (reference layers.py:250-251) is the
+    identity in eval(); in train() mode under no_grad each branch draws its per-sample keep factor like the fp32 path (a dropped
+    branch is not computed)."""
+    att = blk.attention
+    s1, s2 = drop_path_scales(blk)
+    C = x.shape[1]
+    # attention projection + post-norm residual in one launch (the branch never round-trips HBM; -1.2 % on the forward at C = 384)
+    fuse_proj = x.is_contiguous() and s1 == 1.0 and s2 == 1.0 and C in (192, 384)
+    if s1 != 0.0:
+        if C in (192, 384):
+            # QKV projection inside the attention kernel: the (N, 3C) qkv tensor never reaches HBM
+            o = ob.window_attention_qkv(x, sh.get_lin(att.linear1), att.linear1.bias, sh.get(att.earth_specific_bias),
+                                        Z, H, W, att.head_number, roll)
+        else:
+            qkv = ob.linear(x, sh.get_lin(att.linear1), att.linear1.bias)
+            o = ob.window_attention(qkv, sh.get(att.linear1.bias), sh.get(att.earth_specific_bias), Z, H, W,
+                                    att.head_number, roll)
+        if fuse_proj:
+            x1 = ob.linear_ln_residual(o, sh.get_lin(att.linear2), att.linear2.bias, x, blk.norm1.weight, blk.norm1.bias)
+        else:
+            y = ob.linear(o, sh.get_lin(att.linear2), att.linear2.bias)
+            x1 = ob.ln_residual(y, x, blk.norm1.weight, blk.norm1.bias, branch_scale=s1)
+    else:
+        x1 = x
+    if s2 == 0.0:
+        return x1 if out is None else out.copy_(x1)
+    if C in (192, 384):
+        # whole MLP branch + LayerNorm + residual in one launch: the (N, 4C) hidden activation never reaches HBM
+        return ob.mlp_ln_residual(x1, sh.get_mlp_lin(blk.linear.linear1, blk.linear.linear2),
+                                  blk.linear.linear1.bias, blk.linear.linear2.bias, blk.norm2.weight, blk.norm2.bias,
+                                  out=out, branch_scale=s2)
+    h = ob.linear(x1, sh.get_lin(blk.linear.linear1), blk.linear.linear1.bias, act=ob.ACT_GELU)
+    m = ob.linear(h, sh.get_lin(blk.linear.linear2), blk.linear.linear2.bias)
+    return ob.ln_residual(m, x1, blk.norm2.weight, blk.norm2.bias, out=out, branch_scale=s2)
+
+
+# ---- one sample, one layer, on 2-D rows (N, C): THE call site of each layer Function and of its inference composition.
+# sh: None for fp32, the model's fused_bf16.WeightShadow for bf16.  infer: nothing in the whole model asks for a gradient (`not
+# grad_path` of PanguModel.forward); the default is a layer called on its own.
+def _infer_arm(layer, sh, infer, *tensors):
+    """Which arm a layer takes.  fp32: the inference composition iff the layer is frozen and no gradient arrives (_train_path
+    false), whatever `infer` says.  bf16: `infer` and nothing else -- on the model's autograd path a frozen bf16 layer runs its
+    Function too, and a fully frozen bf16 model run with grad mode on takes the inference kernels (grad mode alone cannot tell)."""
+    return infer if sh is not None else not _train_path(layer, *tensors)
+
+
+def sample_block(blk, x, Z, H, W, roll, out=None, sh=None, infer=False):
     """reference layers.py:183-253 for one sample, x (N, C) -> (N, C).  out: the 2-D (N, C) row-strided tensor the block writes its
     result into (a half of the skip-concat buffer, concat_halves) -- no copy."""
-    if sh is None and not _train_path(blk, x):
-        return _block_rows(blk, x, 1, Z, H, W, roll, out)
+    if _infer_arm(blk, sh, infer, x):
+        return _block_rows(blk, x, 1, Z, H, W, roll, out) if sh is None else _block_rows_bf16(blk, sh, x, Z, H, W, roll, out)
     att = blk.attention
     s1, s2 = drop_path_scales(blk)
     return EarthBlockFn.apply(
@@ -141,7 +186,9 @@ def _embed_rows(m, inp, inp_surface, consts, levels_reversed, out):
 
 
 def sample_embed(m, inp, inp_surface, consts, levels_reversed=False, sh=None):
-    """reference layers.py:40-93 for one sample: contiguous inp (5, 13, LAT, LON), inp_surface (4, LAT, LON); consts: embed_constants."""
+    """reference layers.py:40-93 for one sample: contiguous inp (5, 13, LAT, LON), inp_surface (4, LAT, LON); consts: embed_constants.
+    (bf16 has no inference arm: the conv weights are never adapted, and without a graph PatchEmbedFn's forward IS the inference
+    composition, launch for launch.)"""
     if sh is None and not _train_path(m, inp, inp_surface):
         LAT, LON = inp.shape[-2], inp.shape[-1]
         x = torch.empty((8 * ((LAT + 3) // 4) * (LON // 4), m.conv.weight.shape[0]), dtype=torch.float32, device=inp.device)
@@ -150,9 +197,11 @@ def sample_embed(m, inp, inp_surface, consts, levels_reversed=False, sh=None):
                               levels_reversed, sh)
 
 
-def sample_down(m, x, Z, H, W, skip_grad=None, sh=None):
+def sample_down(m, x, Z, H, W, skip_grad=None, sh=None, infer=False):
     """reference layers.py:432-459 for one sample.  skip_grad: the slot shared with PatchRecoverHalvesFn (see DownSampleFn)."""
-    if sh is None and not _train_path(m, x):
+    if _infer_arm(m, sh, infer, x):
+        if sh is not None:        # (get_lin: the bf16 image of W_eff where the projection carries adapters)
+            return ob.linear(ob.downsample_ln(x, m.norm.weight, m.norm.bias, Z, H, W), sh.get_lin(m.linear))
         return ops.linear(ops.downsample_ln(x, m.norm.weight, m.norm.bias, Z, H, W), _layers.eff_weight(m.linear))
     return DownSampleFn.apply(x, _layers.eff_weight(m.linear), m.norm.weight, m.norm.bias, (Z, H, W), skip_grad, sh,
                               *_layers.lora_args(m.linear))
@@ -168,27 +217,31 @@ def _up_rows(m, x2, B, Z, H2, W2, H):
     return out
 
 
-def sample_up(m, x, Z, H2, W2, H, sh=None):
+def sample_up(m, x, Z, H2, W2, H, sh=None, infer=False):
     """reference layers.py:474-499 for one sample."""
-    if sh is None and not _train_path(m, x):
+    if _infer_arm(m, sh, infer, x):
+        if sh is not None:
+            g = ob.upsample_ln(ob.linear(x, sh.get_lin(m.linear1)), m.norm.weight, m.norm.bias, Z, H2, W2, H)
+            return ob.linear(g, sh.get_lin(m.linear2))
         return _up_rows(m, x, 1, Z, H2, W2, H)
     return UpSampleFn.apply(x, _layers.eff_weight(m.linear1), _layers.eff_weight(m.linear2), m.norm.weight, m.norm.bias,
                             (Z, H2, W2, H), sh, *_layers.lora_args(m.linear1, m.linear2))
 
 
-def forward_train(model, inp, inp_surface, statistics, maps, const_h, levels_reversed=False, sh=None):
-    """The autograd-enabled forward of the whole model (reference pangu_model.py:50-87), sample by sample on the per-sample
-    layers above: bf16 (sh = the model's WeightShadow, any B) and fp32 (sh None, B = 1: PanguModel._forward_dispatch)."""
+def forward_model(model, inp, inp_surface, statistics, maps, const_h, levels_reversed=False, sh=None, grad_path=True):
+    """The forward of the whole model (reference pangu_model.py:50-87), sample by sample on the per-sample layers above: bf16
+    (sh = the model's WeightShadow, any B) and fp32 (sh None, B = 1: PanguModel._forward_dispatch).  grad_path: the model-level
+    decision of PanguModel.forward; without it every layer takes its inference arm and no Function records a graph."""
     B, LAT, LON = inp.shape[0], inp.shape[-2], inp.shape[-1]
     H4, W4 = (LAT + 3) // 4, LON // 4
     H2, W2 = (H4 + 1) // 2, W4 // 2
     consts = embed_constants(statistics, maps, const_h, LAT, LON, inp.device)
-    rec = model._output_layer
+    rec, infer = model._output_layer, not grad_path
 
     def run_layer(layer, x, H, W, out=None):
         last = len(layer.blocks) - 1
         for i, blk in enumerate(layer.blocks):
-            x = sample_block(blk, x, 8, H, W, i % 2 == 1, out if i == last else None, sh)
+            x = sample_block(blk, x, 8, H, W, i % 2 == 1, out if i == last else None, sh, infer)
         return x
 
     res = []
@@ -197,14 +250,14 @@ def forward_train(model, inp, inp_surface, statistics, maps, const_h, levels_rev
         halves = concat_halves(x)                 # layer 0 / layer 3 write straight into them
         skip = run_layer(model.layers[0], x, H4, W4, halves[0])
         skip_grad = [None, False]                 # [the concat path's gradient of `skip`, armed]: see DownSampleFn
-        x = sample_down(model.downsample, skip, 8, H4, W4, skip_grad, sh)
+        x = sample_down(model.downsample, skip, 8, H4, W4, skip_grad, sh, infer)
         x = run_layer(model.layers[1], x, H2, W2)
         x = run_layer(model.layers[2], x, H2, W2)
-        x = sample_up(model.upsample, x, 8, H2, W2, H4, sh)
+        x = sample_up(model.upsample, x, 8, H2, W2, H4, sh, infer)
         x = run_layer(model.layers[3], x, H4, W4, halves[1])
         res.append(PatchRecoverHalvesFn.apply(skip, x, rec.conv.weight, rec.conv.bias, rec.conv_surface.weight,
                                               rec.conv_surface.bias, (H4 * W4, LAT, LON), skip_grad, sh))
-    return tuple(_stack(t, B) for t in zip(*res))
+    return tuple(_stack(t, B) for t in zip(*res))       # (B = 1: a view, no 286 MB stack copy)
 
 
 # ---- the batched (B, N, C) functions behind the modules of layers.py, usable and differentiable on their own

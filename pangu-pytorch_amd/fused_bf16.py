@@ -1,15 +1,9 @@
 """bf16 precision of the whole model (BASELINE configs[2]/[4]): bf16 activations + bf16 weight shadows, fp32 LayerNorm /
-softmax / accumulation, fp32 output fields.  `WeightShadow` keeps the bf16 images of the fp32 parameters, `forward` is the
-inference path (same launch sequence as the fp32 one); training runs the driver of fused.py with the model's WeightShadow."""
+softmax / accumulation, fp32 output fields.  `WeightShadow` keeps the bf16 images of the fp32 parameters; the forward, training
+and inference, is the driver of fused.py run with the model's WeightShadow."""
 import torch
 
 from . import ops, ops_bf16 as ob
-from .fused import drop_path_scales, embed_constants
-
-
-def _stamp(p):
-    """ops.param_stamp: (optimizer epoch, _version, data_ptr, shape, device)."""
-    return ops.param_stamp(p)
 
 
 class WeightShadow:
@@ -111,7 +105,7 @@ class WeightShadow:
         if keys:
             _lib.check(_lib.load().pangu_shadow_refresh_bf16(ob._stream(table), table.data_ptr(), len(keys), total), "shadow_refresh_bf16")
         for key in list(keys) + list(skip):
-            self.cache[key] = (tuple(_stamp(p) for p in self.jobs[key][1]), self.jobs[key][2])
+            self.cache[key] = (tuple(ops.param_stamp(p) for p in self.jobs[key][1]), self.jobs[key][2])
 
     def _lookup(self, key, params, make, mode=None, idx=None):
         ep = ops._weights_epoch[0]
@@ -119,7 +113,7 @@ class WeightShadow:
             self.bulk_epoch = ep
             if self.jobs:
                 self._bulk_refresh()
-        stamp = tuple(_stamp(p) for p in params)
+        stamp = tuple(ops.param_stamp(p) for p in params)
         hit = self.cache.get(key)
         if hit is not None and hit[0] == stamp:
             return hit[1]
@@ -149,7 +143,7 @@ class WeightShadow:
                 if hit is None or key in self.jobs:
                     continue
                 hit[1].copy_(make())
-                self.cache[key] = (tuple(_stamp(p) for p in params), hit[1])
+                self.cache[key] = (tuple(ops.param_stamp(p) for p in params), hit[1])
 
     def get(self, p, pad_k=None):
         def make():
@@ -188,87 +182,3 @@ class WeightShadow:
         """Packed chunk image of an Mlp's two weights for the fused MLP kernel (ops_bf16.pack_mlp_weights)."""
         return self._lookup(("mlp", id(w1), id(w2)), (w1, w2), lambda: ob.pack_mlp_weights(w1.detach(), w2.detach()),
                             mode=2, idx=lambda: ob.mlp_pack_index32(w1.shape[1], w1.device))
-
-
-def _block(blk, sh, x, Z, H, W, roll, out=None):
-    """x (N,C) bf16 -> (N,C) bf16.  DropPath (reference layers.py:250-251) is the identity in eval(); in train() mode under
-    no_grad each branch draws its per-sample keep factor like the fp32 path (a dropped branch is not computed)."""
-    att = blk.attention
-    s1, s2 = drop_path_scales(blk)
-    C = x.shape[1]
-    # attention projection + post-norm residual in one launch (the branch never round-trips HBM; -1.2 % on the forward at C = 384)
-    fuse_proj = x.is_contiguous() and s1 == 1.0 and s2 == 1.0 and C in (192, 384)
-    if s1 != 0.0:
-        if C in (192, 384):
-            # QKV projection inside the attention kernel: the (N, 3C) qkv tensor never reaches HBM
-            o = ob.window_attention_qkv(x, sh.get_lin(att.linear1), att.linear1.bias, sh.get(att.earth_specific_bias),
-                                        Z, H, W, att.head_number, roll)
-        else:
-            qkv = ob.linear(x, sh.get_lin(att.linear1), att.linear1.bias)
-            o = ob.window_attention(qkv, sh.get(att.linear1.bias), sh.get(att.earth_specific_bias), Z, H, W,
-                                    att.head_number, roll)
-        if fuse_proj:
-            x1 = ob.linear_ln_residual(o, sh.get_lin(att.linear2), att.linear2.bias, x, blk.norm1.weight, blk.norm1.bias)
-        else:
-            y = ob.linear(o, sh.get_lin(att.linear2), att.linear2.bias)
-            x1 = ob.ln_residual(y, x, blk.norm1.weight, blk.norm1.bias, branch_scale=s1)
-    else:
-        x1 = x
-    if s2 == 0.0:
-        if out is not None:
-            out.copy_(x1)
-            return out
-        return x1
-    if C in (192, 384):
-        # whole MLP branch + LayerNorm + residual in one launch: the (N, 4C) hidden activation never reaches HBM
-        return ob.mlp_ln_residual(x1, sh.get_mlp_lin(blk.linear.linear1, blk.linear.linear2),
-                                  blk.linear.linear1.bias, blk.linear.linear2.bias, blk.norm2.weight, blk.norm2.bias,
-                                  out=out, branch_scale=s2)
-    h = ob.linear(x1, sh.get_lin(blk.linear.linear1), blk.linear.linear1.bias, act=ob.ACT_GELU)
-    m = ob.linear(h, sh.get_lin(blk.linear.linear2), blk.linear.linear2.bias)
-    return ob.ln_residual(m, x1, blk.norm2.weight, blk.norm2.bias, out=out, branch_scale=s2)
-
-
-def _layer(layer, sh, x, Z, H, W, out=None):
-    n = len(layer.blocks)
-    for i, blk in enumerate(layer.blocks):
-        x = _block(blk, sh, x, Z, H, W, i % 2 == 1, out=out if i == n - 1 else None)
-    return x
-
-
-def forward(model, inp, inp_surface, statistics, maps, const_h, levels_reversed=False):
-    sh = model._shadow
-    B = inp.shape[0]
-    LAT, LON = inp.shape[-2], inp.shape[-1]
-    H4, W4 = (LAT + 3) // 4, LON // 4
-    dev = inp.device
-    consts = embed_constants(statistics, maps, const_h, LAT, LON, dev)
-    emb, rec = model._input_layer, model._output_layer
-    outs, outs_s = [], []
-    n_s = H4 * W4
-    N = 8 * n_s
-    C = emb.conv.weight.shape[0]
-    for b in range(B):
-        a_s, a_u = ob.patch_embed_gather(inp[b].contiguous(), inp_surface[b].contiguous(), *consts, levels_reversed)
-        x = torch.empty((N, C), dtype=torch.bfloat16, device=dev)
-        ob.linear(a_s, sh.get(emb.conv_surface.weight, pad_k=128), emb.conv_surface.bias, out=x[:n_s])
-        ob.linear(a_u, sh.get(emb.conv.weight), emb.conv.bias, out=x[n_s:])
-        cat = torch.empty((N, 2 * C), dtype=torch.bfloat16, device=dev)
-        skip = _layer(model.layers[0], sh, x, 8, H4, W4, out=cat[:, :C])
-        g = ob.downsample_ln(skip, model.downsample.norm.weight, model.downsample.norm.bias, 8, H4, W4)
-        x = ob.linear(g, sh.get_lin(model.downsample.linear))
-        H2, W2 = (H4 + 1) // 2, W4 // 2
-        x = _layer(model.layers[1], sh, x, 8, H2, W2)
-        x = _layer(model.layers[2], sh, x, 8, H2, W2)
-        y = ob.linear(x, sh.get_lin(model.upsample.linear1))
-        g = ob.upsample_ln(y, model.upsample.norm.weight, model.upsample.norm.bias, 8, H2, W2, H4)
-        x = ob.linear(g, sh.get_lin(model.upsample.linear2))
-        _layer(model.layers[3], sh, x, 8, H4, W4, out=cat[:, C:])
-        y_s = ob.linear(cat[:n_s], sh.get(rec.conv_surface.weight), rec.conv_surface.bias, out_dtype=torch.float32)
-        y_u = ob.linear(cat[n_s:], sh.get(rec.conv.weight), rec.conv.bias, out_dtype=torch.float32)
-        o, os_ = ops.patch_recover_scatter(y_u, y_s, LAT, LON)
-        outs.append(o)
-        outs_s.append(os_)
-    if B == 1:                                   # no 286 MB stack copy for the usual single sample
-        return outs[0].unsqueeze(0), outs_s[0].unsqueeze(0)
-    return torch.stack(outs, 0), torch.stack(outs_s, 0)

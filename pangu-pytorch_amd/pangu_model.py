@@ -16,11 +16,6 @@ from .layers import (DownSample, EarthSpecificLayer, PatchEmbedding_pretrain, Pa
                      _trunc_normal_)
 
 
-def compact_bias_stamp(p):
-    """What a compact bias table was derived from (ops.param_stamp: optimizer epoch, `_version`, storage, shape, device)."""
-    return ops.param_stamp(p)
-
-
 class _EvalRecomputeFn(torch.autograd.Function):
     """`model.eval()` called WITH gradients enabled -- the reference's own `test()` does exactly that (models/pangu_sample.py:197-202:
     no `torch.no_grad()`), and nothing ever calls backward there.  The forward runs the INFERENCE kernels under no_grad and keeps
@@ -136,7 +131,7 @@ class PanguModel(nn.Module):
             p = getattr(m, "earth_specific_bias", None)
             if p is None:
                 continue
-            stamp = compact_bias_stamp(p)
+            stamp = ops.param_stamp(p)
             if getattr(m, "_esb_compact", None) is not None and getattr(m, "_esb_compact_stamp", None) == stamp:
                 continue
             m._esb_compact = None
@@ -307,29 +302,28 @@ class PanguModel(nn.Module):
         return self._forward_dispatch(input, input_surface, statistics, maps, const_h, want_bf16, grad_path, rev)
 
     def _forward_dispatch(self, input, input_surface, statistics, maps, const_h, want_bf16, grad_path, levels_reversed=False):
-        args = (self, input, input_surface, statistics, maps, const_h, levels_reversed)
-        if want_bf16:
+        if want_bf16 and self._shadow is None:
             from . import fused_bf16
-            if self._shadow is None:
-                self._shadow = fused_bf16.WeightShadow()
-            if grad_path:
-                return fused.forward_train(*args, sh=self._shadow)
-            return fused_bf16.forward(*args)
-        if grad_path and input.shape[0] == 1:
-            return fused.forward_train(*args)
-        if self._compact_bias and not grad_path:
+            self._shadow = fused_bf16.WeightShadow()
+        if not want_bf16 and self._compact_bias and not grad_path:
             self._build_compact_bias()            # no-op while the tables exist (dropped with the weight shadows)
+        if want_bf16 or input.shape[0] == 1:
+            return fused.forward_model(self, input, input_surface, statistics, maps, const_h, levels_reversed,
+                                       sh=self._shadow if want_bf16 else None, grad_path=grad_path)
         return self._forward_f32(input, input_surface, statistics, maps, const_h, grad_path, levels_reversed)
 
-    def _forward_f32(self, input, input_surface, statistics, maps, const_h, grad_path, levels_reversed=False):      # through the modules
+    def _forward_f32(self, input, input_surface, statistics, maps, const_h, grad_path, levels_reversed=False):
+        # through the modules: fp32 at B > 1 only.  Batched and block-major -- each block takes the whole batch (a loop over the
+        # samples with a graph; B folded into the GEMM rows and ONE pair of DropPath factors per block without) -- where
+        # fused.forward_model is sample-major: on the driver a train() forward would draw its DropPath factors from the host RNG in
+        # another order, and inference would run other launch sizes
         B, LAT, LON = input.shape[0], input.shape[-2], input.shape[-1]
         H4, W4 = (LAT + 3) // 4, LON // 4
         H2, W2 = (H4 + 1) // 2, W4 // 2
         x = self._input_layer(input, input_surface, statistics, maps, const_h, levels_reversed)             # (B,521280,192)
         N, C = x.shape[1], x.shape[2]
         if grad_path:
-            # plain concat.  Not on fused.forward_train: this arm is block-major (each block loops over the samples), the driver
-            # sample-major, so under train() the DropPath factors would be drawn from the host RNG in another order
+            # plain concat
             skip = self.layers[0](x, 8, H4, W4)
             x = self.downsample(skip, 8, H4, W4)
             x = self.layers[1](x, 8, H2, W2)

@@ -733,7 +733,7 @@ def test_block_bf16_drift_within_2x_of_reference_autocast(P, golden_dir, C, roll
     models/pangu_model.py:41-48; synth.param_spec_refinit) the HIP bf16 block -- training forward and no-grad forward -- drifts
     from fp32 by no more than 2x what the reference's own CPU autocast(bfloat16) block does on the same input
     (tests/golden/refinit.npz: 4.2e-3 rel-L2, recorded by oracle/gen_golden.py refinit)."""
-    from pangu_pytorch_amd import autograd as AB, fused_bf16
+    from pangu_pytorch_amd import autograd as AB, fused, fused_bf16
     g = np.load(os.path.join(golden_dir, "refinit.npz"))
     tag = f"refinit_block_{C}_{int(roll)}"
     st = cases.STAGES[C]
@@ -756,7 +756,7 @@ def test_block_bf16_drift_within_2x_of_reference_autocast(P, golden_dir, C, roll
                                      att.linear1.weight, att.linear1.bias, att.linear2.weight, att.linear2.bias,
                                      (st["Z"], st["H"], 24, st["heads"], roll), 1.0, 1.0, None, shd).detach()
     with torch.no_grad():
-        yb_inf = fused_bf16._block(blk, shd, xb, st["Z"], st["H"], 24, roll)
+        yb_inf = fused.sample_block(blk, xb, st["Z"], st["H"], 24, roll, sh=shd, infer=True)
     l2 = lambda a: ((a.double() - y32[0].double()).norm() / y32[0].double().norm()).item()
     d_train, d_inf = l2(yb_train.float()), l2(yb_inf.float())
     print(f"{tag}: bf16 drift vs fp32: training forward {d_train:.2e}, inference forward {d_inf:.2e}; reference autocast {ref_drift:.2e}")
@@ -826,7 +826,7 @@ def test_full_backward_smooth_bf16_refinit_vs_reference(P, golden_dir):
 def test_block_bf16_nograd_droppath(P, s1, s2):
     """bf16 inference block in train() mode under no_grad: DropPath factors per branch like the fp32 path (a dropped
     branch is skipped); (1,1) takes the fused projection+LN launches.  Compared with the fp32 oracle expression."""
-    from pangu_pytorch_amd import fused_bf16
+    from pangu_pytorch_amd import fused, fused_bf16
     C, roll, W = 192, True, 12
     st = cases.STAGES[C]
     blk = P.layers.EarthSpecificBlock(C, 0.2, st["heads"], device="cuda").cuda().train()
@@ -836,7 +836,7 @@ def test_block_bf16_nograd_droppath(P, s1, s2):
     blk.drop_path.sample_scale = lambda training: next(seq)
     x = cases.block_input(C, W)
     with torch.no_grad():
-        y = fused_bf16._block(blk, fused_bf16.WeightShadow(), x[0].cuda().to(BF).contiguous(), st["Z"], st["H"], W, roll)
+        y = fused.sample_block(blk, x[0].cuda().to(BF).contiguous(), st["Z"], st["H"], W, roll, sh=fused_bf16.WeightShadow(), infer=True)
         p = cases.block_params(C, roll)
         g = lambda k: p[pre + k]
         xr = x.to(BF).float()

@@ -244,7 +244,9 @@ def test_frozen_block_rule_of_the_per_sample_block(P):
     """fused.sample_block, the one call site of EarthBlockFn, with grad mode on and a 2-D row-strided half of a concat_halves
     buffer as `out`: a frozen fp32 block whose input carries no gradient runs the inference kernels (bit-equal to the batched
     block under no_grad), a frozen bf16 block runs the Function (bit-equal to the trainable block), and a gradient arriving at
-    the frozen fp32 block's input puts it on the Function too.  Every result is written into `out`."""
+    the frozen fp32 block's input puts it on the Function too.  With the inference flag -- what the whole-model driver passes when
+    nothing in the model asks for a gradient -- the bf16 block runs the inference kernels, grad mode on or off (bit-equal, no
+    graph).  Every result is written into `out`."""
     from pangu_pytorch_amd import fused, fused_bf16
     C, roll, W = 192, True, 12
     st = cases.STAGES[C]
@@ -254,12 +256,12 @@ def test_frozen_block_rule_of_the_per_sample_block(P):
     blk.load_state_dict({k: synth.synth_param(pre + k, s, "cuda") for k, s in cases.block_param_shapes(C).items()})
     x = cases.block_input(C, W, "cuda")[0]
 
-    def run(x, sh, trainable, which):
+    def run(x, sh, trainable, which, **kw):
         blk.requires_grad_(trainable)
         half = fused.concat_halves(x)[which]
         half.zero_()
         assert half.stride() == (2 * C, 1)
-        y = fused.sample_block(blk, x, *geom, out=half, sh=sh)
+        y = fused.sample_block(blk, x, *geom, out=half, sh=sh, **kw)
         assert y.data_ptr() == half.data_ptr() and y.stride() == half.stride() and bool(half.abs().sum() > 0)
         return y
 
@@ -271,6 +273,10 @@ def test_frozen_block_rule_of_the_per_sample_block(P):
     xb, sh = x.to(BF), fused_bf16.WeightShadow()
     yb, yb_train = run(xb, sh, False, 1), run(xb, sh, True, 1)
     assert yb.dtype == BF and yb_train.grad_fn is not None and torch.equal(yb, yb_train.detach())
+    yb_inf = run(xb, sh, False, 1, infer=True)
+    with torch.no_grad():
+        yb_ref = run(xb, sh, False, 1, infer=True)
+    assert yb_inf.dtype == BF and yb_inf.grad_fn is None and torch.equal(yb_inf, yb_ref)
     assert run(x.clone().requires_grad_(True), None, False, 0).grad_fn is not None
 
 
