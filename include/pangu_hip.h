@@ -419,6 +419,28 @@ int pangu_host_copy(void* dst, const void* src, long long bytes, int threads);
 int pangu_adam_step_multi(pangu_stream_t stream, const void* jobs, int n_jobs, long long total_blocks, double lr, double beta1,
                           double beta2, double weight_decay, double eps, float bias_correction1, float bias_correction2_sqrt);
 
+/* Global-norm gradient clipping, an accumulation scale and a non-finite-step guard for the Adam above, over the SAME job table and
+ * without touching the gradients or waiting on the host.  Three launches replace the one:
+ *   1. pangu_grad_sumsq_multi, once per table: partials[b] = sum of grad^2 over table block b, accumulated in double in a fixed
+ *      order (no atomics: bit-identical from run to run); a row with grad = 0 contributes 0.  `partials`: total_blocks doubles.
+ *   2. pangu_grad_clip_state, once: adds `n_partials` doubles (the partials of every table, written next to each other) and writes
+ *      the 24-byte device record `state`:
+ *        +0  float  norm           = fl32(grad_scale * sqrt(sumsq)), the norm of the scaled gradient before clipping
+ *        +4  float  multiplier     = fl32(grad_scale) * min(1.0f, fl32(max_norm) / (norm + 1e-6f)) with `clip` (the fp32 arithmetic
+ *                                    of torch.nn.utils.clip_grad_norm_; a NaN stays a NaN), else fl32(grad_scale)
+ *        +8  int    skip           = 1 when `skip_nonfinite` and sumsq is NaN or Inf, else 0
+ *        +16 int64  skipped_total += skip (the record must be zeroed once by its owner)
+ *   3. pangu_adam_step_multi_scaled, once per table: pangu_adam_step_multi on grad * multiplier (the product rounded to float, as
+ *      if the gradient had been scaled in place).  With skip = 1 neither the parameters nor the moments are written; a row's bf16
+ *      image [4] is still written, from the unchanged parameter.
+ * max_norm must be > 0 when `clip`, grad_scale finite and > 0 (PANGU_E_ARG otherwise); counts as for pangu_adam_step_multi. */
+int pangu_grad_sumsq_multi(pangu_stream_t stream, const void* jobs, int n_jobs, long long total_blocks, void* partials);
+int pangu_grad_clip_state(pangu_stream_t stream, const void* partials, long long n_partials, void* state, int clip, double max_norm,
+                          double grad_scale, int skip_nonfinite);
+int pangu_adam_step_multi_scaled(pangu_stream_t stream, const void* jobs, int n_jobs, long long total_blocks, double lr, double beta1,
+                                 double beta2, double weight_decay, double eps, float bias_correction1, float bias_correction2_sqrt,
+                                 const void* state);
+
 /* Rehearsal tool (not on the product path): copy `bytes` (multiple of 16, 16-B aligned pointers) device to device with a grid of
  * exactly `workgroups` 256-thread workgroups -- the HBM traffic / CU footprint of a collective on its own stream, for measuring how
  * much a bucketed gradient all-reduce (reference era5_data/utils_dist.py:125-134 semantics) slows the backward kernels it overlaps. */

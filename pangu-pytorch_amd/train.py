@@ -143,13 +143,76 @@ class HipAdam(torch.optim.Optimizer):
     torch.optim.Adam's (`step`, `exp_avg`, `exp_avg_sq`; lr / betas / eps / weight_decay per group), so schedulers work unchanged.
     Optimizer steps advance ops' weights epoch through the global post-step hook like any torch optimizer."""
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, shadow_of=None):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, shadow_of=None, max_grad_norm=None,
+                 skip_nonfinite=False):
+        """max_grad_norm: clip the global gradient norm (over every group) to it, as torch.nn.utils.clip_grad_norm_ in front of
+        the step would -- without writing the gradients.  skip_nonfinite: a step whose gradients hold a NaN or an Inf leaves
+        parameters and moments alone (what torch's GradScaler does through fused Adam's `found_inf`).  Either, or
+        `step(grad_scale=)`, turns the one launch per group into: one sum-of-squares pass per group (csrc/adam.hip, double partials
+        in a fixed order), one launch that forms the device record (norm, multiplier, skip, skips so far), and one scaled Adam launch
+        per group that reads the record.  Nothing waits for the device: see `last_grad_norm`, `last_grad_multiplier`,
+        `skipped_steps`, `reconcile_skips`."""
+        if max_grad_norm is not None and not float(max_grad_norm) > 0:
+            raise ValueError(f"HipAdam: max_grad_norm must be > 0 (got {max_grad_norm})")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self._tables = {}        # group index -> (signature, device table, n_jobs, total blocks)
         # shadow_of: a PanguModel whose bf16 weight shadows (fused_bf16.WeightShadow) this optimizer keeps current for the plain
         # casts -- the Earth-specific bias tables, 94 % of the bytes: the kernel writes the bf16 image next to the updated fp32
         # value instead of the refresh launch re-reading 1.04 GB
         self._shadow_of = shadow_of
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._init_clip()
+
+    def _init_clip(self):
+        self._clip_state = None      # (device, the 24-byte record as 6 int32) -- allocated by the first clipped / scaled / guarded step
+        self._partials = None        # (total blocks of all groups, double tensor): one partial sum of squares per table block
+        self._skips_seen = 0         # `skipped_steps` at the last reconcile_skips()
+        self._guarded = {}           # parameter -> guarded steps it took part in since the last reconcile_skips()
+
+    def _record(self, lo, hi, dtype):
+        return None if self._clip_state is None else self._clip_state[1][lo:hi].view(dtype)[0]
+
+    @property
+    def last_grad_norm(self):
+        """fp32 device scalar: the global norm of grad_scale * gradients in the last clipped / scaled / guarded step, before
+        clipping (None before the first such step).  Reading it is the caller's synchronisation, not the optimizer's."""
+        return self._record(0, 1, torch.float32)
+
+    @property
+    def last_grad_multiplier(self):
+        """fp32 device scalar: what that step multiplied every gradient by, grad_scale * min(1, max_grad_norm / (norm + 1e-6))."""
+        return self._record(1, 2, torch.float32)
+
+    @property
+    def skipped_steps(self):
+        """int64 device scalar: steps skipped so far for non-finite gradients (skip_nonfinite=True)."""
+        return self._record(4, 6, torch.int64)
+
+    def reconcile_skips(self):
+        """Take the skipped steps out of the host step counters: reads `skipped_steps` (ONE host synchronisation; call it every
+        so often, not every step) and rewinds state[p]["step"] of every parameter stepped under skip_nonfinite since the last
+        call by the number of steps skipped since then.  Returns that number.
+
+        Why it exists: the bias corrections are host scalars computed from state[p]["step"], and `step()` cannot know whether the
+        kernel skipped, so the counter advances through a skipped step.  Until this is called the following steps use the bias
+        corrections of a step count that is too high by the number of skips (parameters and moments are untouched by the skip
+        itself); once it has been called, the trajectory is that of torch's fused Adam with `found_inf`, which does not advance
+        `step` on a skipped step.  Exact when every guarded step since the last call stepped the same parameters (what
+        train_step / rollout_train_step / accumulated_train_step do); a parameter that took part in fewer guarded steps than
+        were skipped is rewound by the steps it took part in."""
+        if self._clip_state is None:
+            return 0
+        total = int(self.skipped_steps.item())
+        new, self._skips_seen = total - self._skips_seen, total
+        if new > 0:
+            for p, k in self._guarded.items():
+                st = self.state.get(p)
+                if st:
+                    st["step"] = max(0, int(st["step"]) - min(new, k))
+            self._tables = {}        # per-row bias corrections (tensors at different step counts) are part of the tables
+        self._guarded = {}
+        return new
 
     # the device job tables hold raw pointers into the optimizer state: anything that can replace state tensors drops them
     def load_state_dict(self, state_dict):
@@ -159,16 +222,22 @@ class HipAdam(torch.optim.Optimizer):
     def __setstate__(self, state):
         super().__setstate__(state)
         self._tables = {}
+        self.__dict__.setdefault("max_grad_norm", None)
+        self.__dict__.setdefault("skip_nonfinite", False)
+        if "_clip_state" not in self.__dict__:
+            self._init_clip()
 
     def add_param_group(self, param_group):
         self._tables = {}
         return super().add_param_group(param_group)
 
     @torch.no_grad()
-    def step(self, closure=None, missing_as_zero=False):
+    def step(self, closure=None, missing_as_zero=False, grad_scale=1.0):
         """missing_as_zero: parameters without a gradient are stepped with a ZERO gradient (moments decay, weight decay applies)
         instead of being skipped -- what the reference's DropPath-dropped branches get (the branch is computed and multiplied by
-        zero there) -- without materialising the zeros."""
+        zero there) -- without materialising the zeros.
+        grad_scale: the update uses grad_scale * gradient (1/n after n accumulated backward passes); the norm that is clipped
+        and reported is that of the scaled gradient.  The gradients themselves are not written."""
         import math
         import struct
 
@@ -179,6 +248,11 @@ class HipAdam(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         lib = _lib.load()
+        grad_scale = float(grad_scale)
+        if not (math.isfinite(grad_scale) and grad_scale > 0):
+            raise ValueError(f"HipAdam.step: grad_scale must be finite and > 0 (got {grad_scale})")
+        fused = self.max_grad_norm is not None or self.skip_nonfinite or grad_scale != 1.0
+        work = []                # per group with rows: (group, device table, n_jobs, blocks, bias corrections, imaged parameters, shadows)
         for gi, group in enumerate(self.param_groups):
             rows, first, dev = [], 0, None
             beta1, beta2 = group["betas"]
@@ -201,6 +275,8 @@ class HipAdam(torch.optim.Optimizer):
                 if torch.is_tensor(st["step"]):          # a state_dict written by torch.optim.Adam keeps `step` as a tensor
                     st["step"] = int(st["step"].item())
                 st["step"] += 1
+                if self.skip_nonfinite:
+                    self._guarded[p] = self._guarded.get(p, 0) + 1
                 n = p.numel()
                 if n == 0:
                     continue
@@ -243,22 +319,63 @@ class HipAdam(torch.optim.Optimizer):
                     tab.append([pp, gp, mp, vp, sp, n, bits, fb])
                 tab.append([0, 0, 0, 0, 0, 0, 0, first])
                 hit = self._tables[gi] = (sig, torch.tensor(tab, dtype=torch.int64).pin_memory().to(dev, non_blocking=True), len(rows), first)
-            b1, b2 = bias(rows[0][6])
-            with torch.cuda.device(dev):      # the launch goes to the parameters' device whatever the caller's current device is
-                _lib.check(lib.pangu_adam_step_multi(_stream(hit[1]), hit[1].data_ptr(), hit[2], hit[3], float(group["lr"]), float(beta1),
-                                                     float(beta2), float(group["weight_decay"]), float(group["eps"]), b1, b2), "adam_step_multi")
-            for p in imaged:
+            work.append((group, hit[1], hit[2], hit[3], bias(rows[0][6]), imaged, ws))
+        if fused and work:
+            self._clip_record(lib, work, grad_scale)
+        for group, table, n_jobs, blocks, (b1, b2), imaged, ws in work:
+            beta1, beta2 = group["betas"]
+            with torch.cuda.device(table.device):      # the launch goes to the parameters' device whatever the caller's current device is
+                args = (_stream(table), table.data_ptr(), n_jobs, blocks, float(group["lr"]), float(beta1), float(beta2),
+                        float(group["weight_decay"]), float(group["eps"]), b1, b2)
+                if fused:
+                    _lib.check(lib.pangu_adam_step_multi_scaled(*args, self._clip_state[1].data_ptr()), "adam_step_multi_scaled")
+                else:
+                    _lib.check(lib.pangu_adam_step_multi(*args), "adam_step_multi")
+            for p in imaged:       # (a skipped step re-wrote the image from the unchanged parameter: fresh either way)
                 ws.mark_fresh(p)
         return loss
 
+    def _clip_record(self, lib, work, grad_scale):
+        """The launches in front of a clipped / scaled / guarded step: the sum of squares of every group's gradients into one
+        partial buffer, then the device record (csrc/adam.hip ClipState) the scaled Adam launches read."""
+        from . import _lib
+        from .ops import _stream
+        dev = work[0][1].device
+        if any(w[1].device != dev for w in work):
+            raise RuntimeError("HipAdam: max_grad_norm / skip_nonfinite / grad_scale take ONE norm over all groups: every group must "
+                               "live on one device")
+        if self._clip_state is None or self._clip_state[0] != dev:
+            self._clip_state = (dev, torch.zeros(6, dtype=torch.int32, device=dev))
+            self._skips_seen = 0
+        total = sum(w[3] for w in work)
+        if self._partials is None or self._partials[0] != total or self._partials[1].device != dev:
+            self._partials = (total, torch.empty(total, dtype=torch.float64, device=dev))
+        partials, state = self._partials[1], self._clip_state[1]
+        with torch.cuda.device(dev):
+            stream, first = _stream(partials), 0
+            for _, table, n_jobs, blocks, _, _, _ in work:
+                _lib.check(lib.pangu_grad_sumsq_multi(stream, table.data_ptr(), n_jobs, blocks, partials.data_ptr() + 8 * first),
+                           "grad_sumsq_multi")
+                first += blocks
+            clip = self.max_grad_norm is not None
+            _lib.check(lib.pangu_grad_clip_state(stream, partials.data_ptr(), total, state.data_ptr(), int(clip),
+                                                 self.max_grad_norm if clip else 0.0, grad_scale, int(self.skip_nonfinite)),
+                       "grad_clip_state")
 
-def make_optimizer(model, lr=5e-6, weight_decay=3e-6):
+
+def make_optimizer(model, lr=5e-6, weight_decay=3e-6, max_grad_norm=None, skip_nonfinite=False):
     """The reference's optimiser (finetune_fully.py:121: Adam(lr=5e-6, weight_decay=3e-6)).  Parameters on a HIP device: the
-    one-launch HipAdam above (bit-identical to torch's fused Adam); CPU parameters (host-side tests): torch.optim.Adam."""
+    one-launch HipAdam above (bit-identical to torch's fused Adam); CPU parameters (host-side tests): torch.optim.Adam.
+    max_grad_norm / skip_nonfinite: HipAdam's fused global-norm clipping and non-finite-step guard; torch's Adam has neither, so
+    asking for them where HipAdam cannot be used is a ValueError."""
     params = [p for p in model.parameters() if p.requires_grad]
     on_gpu = all(p.is_cuda for p in params)
     if on_gpu and all(p.dtype == torch.float32 and p.is_contiguous() for p in params):
-        return HipAdam(params, lr=lr, weight_decay=weight_decay, shadow_of=model)
+        return HipAdam(params, lr=lr, weight_decay=weight_decay, shadow_of=model, max_grad_norm=max_grad_norm,
+                       skip_nonfinite=skip_nonfinite)
+    if max_grad_norm is not None or skip_nonfinite:
+        raise ValueError("make_optimizer: max_grad_norm / skip_nonfinite are HipAdam's (contiguous fp32 parameters on a HIP device); "
+                         "these parameters get torch.optim.Adam, which would ignore them")
     return torch.optim.Adam(params, lr=lr, weight_decay=weight_decay, fused=on_gpu)
 
 
@@ -340,22 +457,34 @@ def _owns_dropped_branches(grad_sync):
     return isinstance(getattr(grad_sync, "__self__", None), FlatGradSync)
 
 
-def _optimizer_tail(optimizer, grad_sync):
+def _optimizer_tail(optimizer, grad_sync, grad_scale=1.0):
     """What follows the backward in train_step / rollout_train_step: the gradient sync, then the optimizer step in which parameters
-    without a gradient (DropPath-dropped branches) get the reference's zero-gradient update."""
+    without a gradient (DropPath-dropped branches) get the reference's zero-gradient update.  grad_scale != 1 (accumulated
+    backward passes): HipAdam scales inside its kernel; any other optimizer gets its gradients scaled with torch ops first."""
+    hip = isinstance(optimizer, HipAdam)
+    kw = {"grad_scale": grad_scale} if hip and grad_scale != 1.0 else {}
     if grad_sync is not None:
         grad_sync()
-        optimizer.step()
-    elif isinstance(optimizer, HipAdam):
+        _scale_grads(optimizer, 1.0 if hip else grad_scale)
+        optimizer.step(**kw)
+    elif hip:
         # a DropPath-dropped branch is not computed here, so its parameters come back without a gradient; the reference
         # computes the branch, multiplies by zero and hands Adam ZERO gradients (moments decay, weight decay applies)
-        optimizer.step(missing_as_zero=True)
+        optimizer.step(missing_as_zero=True, **kw)
     else:
         for group in optimizer.param_groups:
             for p in group["params"]:
                 if p.requires_grad and p.grad is None:
                     p.grad = torch.zeros_like(p)
+        _scale_grads(optimizer, grad_scale)
         optimizer.step()
+
+
+def _scale_grads(optimizer, grad_scale):
+    if grad_scale != 1.0:
+        grads = [p.grad for group in optimizer.param_groups for p in group["params"] if p.grad is not None]
+        if grads:
+            torch._foreach_mul_(grads, grad_scale)
 
 
 def train_step(model, optimizer, batch, statistics, maps, const_h, stats_last=None, grad_sync=None, levels_reversed=False):
@@ -382,6 +511,39 @@ def train_step(model, optimizer, batch, statistics, maps, const_h, stats_last=No
         loss.backward()
     _optimizer_tail(optimizer, grad_sync)
     return loss.detach()
+
+
+def accumulated_train_step(model, optimizer, batches, statistics, maps, const_h, stats_last=None, grad_sync=None,
+                           levels_reversed=False):
+    """One optimisation step on the MEAN gradient of n batches (gradient accumulation: the per-rank batch is one sample, as in the
+    reference, so this is how one GPU reaches the reference's effective batch of 8).  batches: a sequence of n train_step batches.
+    zero_grad once; n forward / loss / backward passes under train_step's dropped-branch policy, autograd accumulating; `grad_sync`
+    once, after the last backward; then train_step's optimizer tail with grad_scale = 1/n -- inside HipAdam's kernel (the
+    gradients are not rewritten; a `max_grad_norm` clips the norm of the mean gradient), with torch ops for any other optimizer.
+    A parameter is without a gradient only if its branch was dropped in all n passes.  Returns the mean of the n detached losses;
+    nothing in here waits for the device.  n = 1 is train_step, bit for bit.
+    Not with a dist.FlatGradSync method and n > 1 (its per-parameter hooks would fire, and launch its buckets, n times):
+    RuntimeError, as rollout_train_step(checkpoint=True)."""
+    batches = list(batches)
+    n = len(batches)
+    if n == 0:
+        raise ValueError("accumulated_train_step: `batches` is empty")
+    if n > 1 and grad_sync is not None and _owns_dropped_branches(grad_sync):
+        raise RuntimeError(f"accumulated_train_step runs {n} backward passes, and a dist.FlatGradSync's per-parameter hooks would fire "
+                           "(and launch its buckets) once per pass: use another grad_sync, or one batch per step")
+    from . import ops
+    lean = grad_sync is None or _owns_dropped_branches(grad_sync)
+    optimizer.zero_grad(set_to_none=True)
+    total = None
+    for inp, inp_s, tgt, tgt_s in batches:
+        out, out_s = model(inp, inp_s, statistics, maps, const_h, levels_reversed=levels_reversed)
+        loss = weighted_l1_loss(out, out_s, tgt, tgt_s, target_levels_reversed=levels_reversed, stats_last=stats_last)
+        with ops.dropped_branch_grads("none" if lean else "zeros"):
+            loss.backward()
+        total = loss.detach() if total is None else total + loss.detach()
+        del out, out_s, loss
+    _optimizer_tail(optimizer, grad_sync, 1.0 / n)
+    return total if n == 1 else total / n
 
 
 # ---- multi-step (rollout) fine-tuning ---------------------------------------------------------------------------------------
