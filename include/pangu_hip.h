@@ -403,6 +403,34 @@ int pangu_rollout_l1_seed_bwd(pangu_stream_t stream, const float* out, const flo
                               int levels, int target_levels_reversed, const float* t_mean_upper, const float* t_std_upper,
                               const float* t_mean_surface, const float* t_std_surface);
 
+/* Fair-CRPS training loss over E ensemble members (2 <= E <= 16), one pass per direction (csrc/crps_loss.hip).  Per grid point,
+ * x_e the members' normalised outputs, t the normalised target:
+ *   c = (1/E) sum_e |x_e - t| - 1/(2E(E-1)) sum_e sum_f |x_e - x_f|
+ *   loss = mean(w_upper[var] * a[h] * c) + 0.25 * mean(w_surface[var] * a[h] * c_surface)
+ * members / members_surface: HOST arrays of E device pointers, member e's fields [B][Vu][levels][H][W] / [B][Vs][H][W] fp32 (the
+ * outputs of E forwards; the entry copies the addresses into the kernel arguments).  target / target_surface, w_upper / w_surface,
+ * target_levels_reversed and the four statistics: as for pangu_weighted_l1_loss_fwd.  lat_weight: H device floats, the weight a[h]
+ * of latitude row h, or NULL for a = 1.  fwd: `partial` = scratch of pangu_fair_crps_loss_blocks(..) floats; loss[0] = the loss,
+ * loss[1] / loss[2] = the two means; fp32 block partials summed by one fixed-order fp64 launch (no atomics: the same bits every
+ * run).  bwd: grad = device scalar (d loss), k = 1/n_upper or 0.25/n_surface, sign(0) = 0:
+ *   d_members[e] = grad * k * w[var] * a[h] * (sign(x_e - t)/E - sum_f sign(x_e - x_f) / (E(E-1)))
+ * d_members / d_members_surface: HOST arrays of E device pointers; d_members[e] MAY be members[e] itself (every thread reads all E
+ * values of an element before its first store).  A 16-byte vector path runs when W % 4 == 0 and every field is 16-byte aligned,
+ * a scalar path otherwise.  PANGU_E_NULL: a NULL pointer (array entries included; statistics not all four or none), PANGU_E_ARG:
+ * E outside 2..16, PANGU_E_SHAPE: a non-positive size, H * W or the block count out of range. */
+long long pangu_fair_crps_loss_blocks(int E, int B, int Vu, int levels, int Vs, int H, int W);
+int pangu_fair_crps_loss_fwd(pangu_stream_t stream, const float* const* members, const float* const* members_surface, int E,
+                             const float* target, const float* target_surface, const float* w_upper, const float* w_surface,
+                             const float* lat_weight, float* partial, float* loss, int B, int Vu, int levels, int Vs, int H, int W,
+                             int target_levels_reversed, const float* t_mean_upper, const float* t_std_upper,
+                             const float* t_mean_surface, const float* t_std_surface);
+int pangu_fair_crps_loss_bwd(pangu_stream_t stream, const float* const* members, const float* const* members_surface, int E,
+                             const float* target, const float* target_surface, const float* w_upper, const float* w_surface,
+                             const float* lat_weight, const float* grad, float* const* d_members, float* const* d_members_surface,
+                             int B, int Vu, int levels, int Vs, int H, int W, int target_levels_reversed,
+                             const float* t_mean_upper, const float* t_std_upper, const float* t_mean_surface,
+                             const float* t_std_surface);
+
 /* Host side of the input pipeline (the idea of reference era5_data/utils_data.py:16-51 and the four
  * `.to(device)` of models/pangu_sample.py:41-43): copy `bytes` from the loader's pageable memory into a page-locked staging
  * buffer with up to `threads` host threads (each one contiguous 4 KB-aligned span; < 4 MB per thread is not split).  Pure

@@ -59,6 +59,9 @@ SIGNATURES = {
     "pangu_weighted_l1_loss_fwd": [_P] * 9 + [_I, _I, _c.c_longlong, _I, _c.c_longlong, _I, _I] + [_P] * 4,
     "pangu_weighted_l1_loss_bwd": [_P] * 10 + [_I, _I, _c.c_longlong, _I, _c.c_longlong, _I, _I] + [_P] * 4,
     "pangu_rollout_l1_seed_bwd": [_P] * 14 + [_I, _I, _c.c_longlong, _I, _c.c_longlong, _I, _I] + [_P] * 4,
+    "pangu_fair_crps_loss_blocks": [_I] * 7,
+    "pangu_fair_crps_loss_fwd": [_P, _P, _P, _I] + [_P] * 7 + [_I] * 7 + [_P] * 4,
+    "pangu_fair_crps_loss_bwd": [_P, _P, _P, _I] + [_P] * 8 + [_I] * 7 + [_P] * 4,
     "pangu_host_copy": [_P, _P, _c.c_longlong, _I],
     "pangu_window_attn_bwd_bf16": [_P] * 10 + [_I] * 6,
     "pangu_ln_residual_bwd_bf16": [_P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _F],
@@ -79,7 +82,8 @@ SIGNATURES = {
     "pangu_patch_recover_scatter_denorm": [_P] * 11 + [_I, _I],
     "pangu_traffic_copy": [_P, _P, _P, _c.c_longlong, _I],
 }
-_RESTYPES = {"pangu_error_string": _c.c_char_p, "pangu_weighted_l1_loss_blocks": _c.c_longlong}
+_RESTYPES = {"pangu_error_string": _c.c_char_p, "pangu_weighted_l1_loss_blocks": _c.c_longlong,
+             "pangu_fair_crps_loss_blocks": _c.c_longlong}
 
 _lib = None
 

@@ -12,6 +12,7 @@
 //     era5_data/utils_data.py:117 is an address: logical level lev lives in plane L-1-lev.  Statistics are indexed by LOGICAL level.
 // Blocks never straddle a (sample, variable, level) plane, so weight, statistics and the target's plane are block-uniform.
 #include "common.h"
+#include "loss_target.h"
 
 namespace {
 
@@ -23,11 +24,6 @@ struct LossGeom {
   int planes_u, planes_s;             // B * Vu * L, B * Vs
   int Vu, Vs, L;
   int t_rev;                          // the target's level axis is stored reversed
-};
-
-struct TargetStats {                  // null = the target is already normalised
-  const float* mean_u; const float* std_u;      // [Vu][L], logical level order
-  const float* mean_s; const float* std_s;      // [Vs]
 };
 
 // block b -> which field, which variable, [begin, end) inside the plane, the plane's offset in out (base) and in target (base_t),
@@ -232,12 +228,6 @@ bool make_loss_geom(LossGeom& g, int B, int Vu, long long plane_u, int Vs, long 
   g.Vu = Vu; g.Vs = Vs; g.L = levels; g.t_rev = t_rev != 0;
   const long long blocks = (long long)g.planes_u * g.chunks_u + (long long)g.planes_s * g.chunks_s;
   return blocks > 0 && blocks < (1ll << 30);
-}
-
-bool make_stats(TargetStats& st, const float* mu, const float* su, const float* ms, const float* ss) {
-  st = TargetStats{mu, su, ms, ss};
-  const int n = (mu != nullptr) + (su != nullptr) + (ms != nullptr) + (ss != nullptr);
-  return n == 0 || n == 4;            // all four or none
 }
 
 }  // namespace

@@ -45,6 +45,21 @@ def _amplitude9(amplitude):
     return vals
 
 
+_amp_on = {}      # (device, the 9 amplitudes) -> the fp32 device tensor
+
+
+def _amplitudes_on(device, amp):
+    """Uploaded once per (device, values): torch.tensor(list, device=cuda) is a synchronous host-to-device copy (it waits for
+    whatever the stream holds), which a training step that perturbs every step must not pay (train.ensemble_train_step)."""
+    key = (str(device), tuple(amp))
+    t = _amp_on.get(key)
+    if t is None:
+        if len(_amp_on) > 8:
+            _amp_on.clear()
+        t = _amp_on[key] = torch.tensor(amp, dtype=torch.float32).to(device)
+    return t
+
+
 def perturb_(upper, surface, stats_last, amplitude, seed, octaves=3, period=12, persistence=0.5, first_member=0, control=True):
     """Add amplitude[var] * std[plane] * Perlin noise, in place, to member states upper (E,5,13,H,W) and surface (E,4,H,W)
     (fp32, physical units, on the device); std comes from stats_last = (s_mean, s_std, u_mean, u_std).
@@ -71,7 +86,7 @@ def perturb_(upper, surface, stats_last, amplitude, seed, octaves=3, period=12, 
     _, s_std, _, u_std = stats_last
     dev = upper.device
     f = lambda t: t.to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
-    amp_t = torch.tensor(amp, dtype=torch.float32, device=dev)
+    amp_t = _amplitudes_on(dev, amp)
     us, ss = f(u_std), f(s_std)
     if us.numel() != 65 or ss.numel() != 4:
         raise ValueError("perturb_: stats_last must be (s_mean (1,4,1,1), s_std, u_mean (1,5,13,1,1), u_std)")

@@ -762,3 +762,254 @@ def rollout_train_step(model, optimizer, batch, statistics, maps, const_h, stats
     torch.set_rng_state(rng_end)
     _optimizer_tail(optimizer, grad_sync)
     return _weighted_total(losses, lam), torch.stack(losses)
+
+
+# ---- fair-CRPS ensemble fine-tuning -------------------------------------------------------------------------------------------
+
+CRPS_MIN_MEMBERS, CRPS_MAX_MEMBERS = 2, 16      # csrc/crps_loss.hip keeps the E values of an element in registers
+
+_crps_lat = {}      # (H, device) -> max(score.latitude_weights(H), 0), fp32 on the device
+
+
+def _crps_lat_weights(H, device):
+    """The latitude weights of the fair-CRPS loss: score.latitude_weights clamped at zero (see fair_crps_loss)."""
+    key = (int(H), str(device))
+    a = _crps_lat.get(key)
+    if a is None:
+        from . import score
+        a = _crps_lat[key] = score.latitude_weights(H, device).clamp_min(0.0).contiguous()
+    return a
+
+
+def _check_member_count(E, who):
+    if not CRPS_MIN_MEMBERS <= E <= CRPS_MAX_MEMBERS:
+        raise ValueError(f"{who}: {CRPS_MIN_MEMBERS} <= members <= {CRPS_MAX_MEMBERS}, got {E}")
+
+
+def _fair_crps_loss_torch(outputs, outputs_surface, target, target_surface, target_levels_reversed=False, stats_last=None,
+                          lat_weighted=True):
+    """The definition of fair_crps_loss as torch ops (any device, any floating dtype; the reference of the tests): O(E^2) passes
+    over the fields."""
+    E = len(outputs)
+    if target_levels_reversed:
+        target = target.flip(-3)
+    if stats_last is not None:
+        target, target_surface = norm_data(target, target_surface, stats_last)
+    dev, dt = outputs[0].device, outputs[0].dtype
+    wu, ws = _weights_on(dev, dt)
+    a = _crps_lat_weights(outputs[0].shape[-2], dev).to(dt).view(-1, 1) if lat_weighted else None
+
+    def mean_crps(xs, t, w):
+        s1 = sum((x - t).abs() for x in xs)
+        s2 = sum((xs[e] - xs[f]).abs() for e in range(1, E) for f in range(e))       # every pair once: 2 / (2E(E-1))
+        c = (s1 / E - s2 / (E * (E - 1))) * w
+        return torch.mean(c if a is None else c * a)
+
+    return mean_crps(outputs, target, wu) + mean_crps(outputs_surface, target_surface, ws) * 0.25
+
+
+def _crps_geom(upper, surface):
+    return (upper.shape[0], upper.shape[1], upper.shape[2], surface.shape[1], upper.shape[-2], upper.shape[-1])
+
+
+def _crps_pointers(tensors):
+    import ctypes
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def _fair_crps_launch_fwd(outputs, outputs_surface, target, target_surface, rev, st, lat):
+    """The forward launch pair on contiguous fp32 device fields -> loss (3,) = (total, upper mean, surface mean)."""
+    from . import _lib
+    from .ops import _stream
+    lib = _lib.load()
+    E, o = len(outputs), outputs[0]
+    geom = _crps_geom(o, outputs_surface[0])
+    nblk = lib.pangu_fair_crps_loss_blocks(E, *geom)
+    if nblk <= 0:
+        raise RuntimeError(f"fair_crps_loss: unsupported shapes {tuple(o.shape)} {tuple(outputs_surface[0].shape)} x {E} members")
+    wu, ws = _weights_on(o.device, torch.float32)
+    sp = tuple(t.data_ptr() for t in st) if st else (None,) * 4
+    partial = torch.empty((nblk,), dtype=torch.float32, device=o.device)
+    loss = torch.empty((3,), dtype=torch.float32, device=o.device)
+    with torch.cuda.device(o.device):
+        _lib.check(lib.pangu_fair_crps_loss_fwd(
+            _stream(o), _crps_pointers(outputs), _crps_pointers(outputs_surface), E, target.data_ptr(), target_surface.data_ptr(),
+            wu.data_ptr(), ws.data_ptr(), None if lat is None else lat.data_ptr(), partial.data_ptr(), loss.data_ptr(), *geom,
+            int(rev), *sp), "fair_crps_loss_fwd")
+    return loss
+
+
+def _fair_crps_launch_bwd(outputs, outputs_surface, target, target_surface, rev, st, lat, g, d_outputs, d_outputs_surface):
+    """The backward launch: d_outputs[e] / d_outputs_surface[e] may be outputs[e] / outputs_surface[e] themselves."""
+    from . import _lib
+    from .ops import _stream
+    E, o = len(outputs), outputs[0]
+    wu, ws = _weights_on(o.device, torch.float32)
+    sp = tuple(t.data_ptr() for t in st) if st else (None,) * 4
+    with torch.cuda.device(o.device):
+        _lib.check(_lib.load().pangu_fair_crps_loss_bwd(
+            _stream(o), _crps_pointers(outputs), _crps_pointers(outputs_surface), E, target.data_ptr(), target_surface.data_ptr(),
+            wu.data_ptr(), ws.data_ptr(), None if lat is None else lat.data_ptr(), g.data_ptr(), _crps_pointers(d_outputs),
+            _crps_pointers(d_outputs_surface), *_crps_geom(o, outputs_surface[0]), int(rev), *sp), "fair_crps_loss_bwd")
+
+
+class FairCrpsLossFn(torch.autograd.Function):
+    """fair_crps_loss on the device: one forward launch pair (block partials, fp64 final sum) and one backward launch that writes
+    all 2E gradient fields (csrc/crps_loss.hip).  apply(target, target_surface, target_levels_reversed, stats_last, lat_weighted,
+    *outputs, *outputs_surface)."""
+
+    @staticmethod
+    def forward(ctx, target, target_surface, target_levels_reversed, stats_last, lat_weighted, *fields):
+        E = len(fields) // 2
+        outputs, outputs_surface = fields[:E], fields[E:]
+        o = outputs[0]
+        st = _flat_stats(stats_last, o.device, o.shape[1], o.shape[2], outputs_surface[0].shape[1]) if stats_last is not None else ()
+        lat = _crps_lat_weights(o.shape[-2], o.device) if lat_weighted else None
+        loss = _fair_crps_launch_fwd(outputs, outputs_surface, target, target_surface, target_levels_reversed, st, lat)
+        ctx.save_for_backward(target, target_surface, *fields, *st)
+        ctx.E, ctx.rev, ctx.lat = E, bool(target_levels_reversed), lat
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        E = ctx.E
+        target, target_surface, *rest = ctx.saved_tensors
+        outputs, outputs_surface, st = rest[:E], rest[E:2 * E], rest[2 * E:]
+        d_o, d_os = [torch.empty_like(t) for t in outputs], [torch.empty_like(t) for t in outputs_surface]
+        _fair_crps_launch_bwd(outputs, outputs_surface, target, target_surface, ctx.rev, st, ctx.lat,
+                              g.to(torch.float32).contiguous(), d_o, d_os)
+        return (None,) * 5 + tuple(d_o) + tuple(d_os)
+
+
+def _hip_crps_ok(outputs, outputs_surface, target, target_surface):
+    o, o_s = outputs[0], outputs_surface[0]
+    return (all(_hip_loss_ok(x, x_s, target, target_surface) for x, x_s in zip(outputs, outputs_surface))
+            and all(x.device == o.device and x.shape == o.shape for x in outputs)
+            and all(x.shape == o_s.shape for x in outputs_surface) and o.shape[-2:] == o_s.shape[-2:])
+
+
+def fair_crps_loss(outputs, outputs_surface, target, target_surface, target_levels_reversed=False, stats_last=None,
+                   lat_weighted=True):
+    """The fair (unbiased-in-E) CRPS of E member forecasts against one target, in weighted_l1_loss's shape -- the score
+    score.ensemble_scores reports, as a differentiable training loss.  outputs / outputs_surface: sequences of E (2..16) member
+    fields, normalised, (1,5,13,H,W) / (1,4,H,W); target / target_surface, target_levels_reversed, stats_last: as weighted_l1_loss.
+    Per grid point
+        c = (1/E) sum_e |x_e - t|  -  1/(2E(E-1)) sum_e sum_f |x_e - x_f|
+        loss = mean(w_upper[var] * a[h] * c) + 0.25 * mean(w_surface[var] * a[h] * c_surface)
+    lat_weighted: a[h] = max(score.latitude_weights(H)[h], 0), else a = 1.  The clamp: the reference's `3.1416` literal for pi makes
+    the weight of the last latitude row -7.5e-6, and a loss must not reward error there; the effect on the value is about 1e-8
+    relative.  With identical members and lat_weighted=False this is weighted_l1_loss.
+    Contiguous fp32 fields on one HIP device take the HIP form (FairCrpsLossFn: the fields are read once per direction, where the
+    torch expression makes O(E^2) passes); anything else (other dtypes, CPU tensors, targets that need gradients) the torch
+    expression `_fair_crps_loss_torch`."""
+    outputs, outputs_surface = tuple(outputs), tuple(outputs_surface)
+    _check_member_count(len(outputs), "fair_crps_loss")
+    if len(outputs_surface) != len(outputs):
+        raise ValueError(f"fair_crps_loss: {len(outputs)} upper-air and {len(outputs_surface)} surface member fields")
+    if _hip_crps_ok(outputs, outputs_surface, target, target_surface):
+        return FairCrpsLossFn.apply(target, target_surface, bool(target_levels_reversed), stats_last, bool(lat_weighted),
+                                    *outputs, *outputs_surface)
+    return _fair_crps_loss_torch(outputs, outputs_surface, target, target_surface, target_levels_reversed, stats_last, lat_weighted)
+
+
+def _check_ensemble_batch(batch, stats_last, members, amplitude, octaves, period):
+    from . import ensemble
+    if not isinstance(members, int) or isinstance(members, bool):
+        raise ValueError(f"ensemble_train_step: members must be an int, got {members!r}")
+    _check_member_count(members, "ensemble_train_step")
+    ensemble._amplitude9(amplitude)
+    batch = tuple(batch)
+    if len(batch) != 4:
+        raise ValueError(f"ensemble_train_step: batch = (input, input_surface, target, target_surface): got {len(batch)} tensors")
+    if stats_last is None or len(stats_last) != 4:
+        raise ValueError("ensemble_train_step: stats_last = (s_mean, s_std, u_mean, u_std) is required: the perturbations are scaled "
+                         "with it, and the targets are in physical units")
+    inp, inp_s, tgt, tgt_s = batch
+    if inp.dim() != 5 or inp_s.dim() != 4 or inp_s.shape[0] != inp.shape[0] or inp_s.shape[-2:] != inp.shape[-2:]:
+        raise ValueError(f"ensemble_train_step: input {tuple(inp.shape)} / input_surface {tuple(inp_s.shape)}: expected "
+                         "(1, 5, 13, LAT, LON) / (1, 4, LAT, LON)")
+    if inp.shape[0] != 1:
+        raise ValueError(f"ensemble_train_step: the per-rank batch is one sample (as in the reference), got B = {inp.shape[0]}")
+    if tgt.shape != inp.shape or tgt_s.shape != inp_s.shape:
+        raise ValueError(f"ensemble_train_step: the target is {tuple(tgt.shape)} / {tuple(tgt_s.shape)}, the fields are "
+                         f"{tuple(inp.shape)} / {tuple(inp_s.shape)}")
+    ensemble._check_lattice(inp.shape[-1], octaves, period)
+    return batch
+
+
+def ensemble_train_step(model, optimizer, batch, statistics, maps, const_h, stats_last, *, members, amplitude, seed,
+                        checkpoint=True, lat_weighted=True, grad_sync=None, octaves=3, period=12, persistence=0.5, control=True):
+    """One optimisation step on the fair CRPS (fair_crps_loss) of `members` perturbed forecasts of one sample: the model is
+    fine-tuned on the score its ensembles are judged by (score.ensemble_scores).  batch = train_step's (input, input_surface,
+    target, target_surface): one sample in the model's level order, targets in PHYSICAL units, on the device.  The member inputs
+    are the sample under ensemble.perturb_(amplitude, seed, octaves, period, persistence, control) -- amplitude is required, the
+    project has no calibrated default.  Returns the detached loss; nothing in here waits for the device.
+
+    checkpoint=True: pass 1 runs the E forwards keeping only each member's two output fields (0.3 GB) and the host RNG state in
+    front of it -- with the kernels of the training forward, so that the recomputed outputs are the ones the loss saw, bit for
+    bit; one loss forward and one loss backward launch then write every member's output gradient over the kept outputs; then each
+    member is re-run with gradients under its RNG state (the same DropPath draws) and back-propagated from those gradients,
+    parameter gradients accumulating over the members.  Peak memory is one step's activations plus the member fields.  The host
+    RNG ends where pass 1 left it; the DropPath counters count every forward twice.  Not with a dist.FlatGradSync method (its
+    per-parameter hooks would fire E times): RuntimeError, as rollout_train_step(checkpoint=True); any other `grad_sync` callable
+    runs after the last backward.
+    checkpoint=False: one autograd graph over the E forwards and FairCrpsLossFn, one backward (memory grows by one step's
+    activations per member); works with a dist.FlatGradSync method.
+
+    zero_grad once; dropped-branch contract and optimizer tail: train_step's; a parameter is without a gradient only if its branch
+    was dropped in all E forwards."""
+    inp, inp_s, tgt, tgt_s = _check_ensemble_batch(batch, stats_last, members, amplitude, octaves, period)
+    if checkpoint and grad_sync is not None and _owns_dropped_branches(grad_sync):
+        raise RuntimeError("ensemble_train_step(checkpoint=True) runs E backward passes, and a dist.FlatGradSync's per-parameter hooks "
+                           "would fire (and launch its buckets) E times: use checkpoint=False with FlatGradSync, or another grad_sync")
+    if not all(t.is_cuda for t in (inp, inp_s, tgt, tgt_s)):
+        raise RuntimeError("ensemble_train_step: the batch must live on the model's HIP device (got CPU tensors); there is no CPU "
+                           "fallback")
+    if any(t.device != inp.device for t in (inp_s, tgt, tgt_s)):
+        raise RuntimeError("ensemble_train_step: the batch tensors are on different devices")
+    from . import ensemble, ops
+    E = members
+    consts = (statistics, maps, const_h)
+    policy = "none" if grad_sync is None or _owns_dropped_branches(grad_sync) else "zeros"
+    up = inp.to(torch.float32).expand(E, *inp.shape[1:]).contiguous()
+    sf = inp_s.to(torch.float32).expand(E, *inp_s.shape[1:]).contiguous()
+    ensemble.perturb_(up, sf, stats_last, amplitude, seed, octaves=octaves, period=period, persistence=persistence, control=control)
+    optimizer.zero_grad(set_to_none=True)
+
+    if not checkpoint:
+        outs = [model(up[e:e + 1], sf[e:e + 1], *consts) for e in range(E)]
+        loss = fair_crps_loss([o for o, _ in outs], [o_s for _, o_s in outs], tgt, tgt_s, stats_last=stats_last,
+                              lat_weighted=lat_weighted)
+        del outs
+        with ops.dropped_branch_grads(policy):
+            loss.backward()
+        _optimizer_tail(optimizer, grad_sync)
+        return loss.detach()
+
+    # pass 1: each member's graph dies with its outputs; only the two output fields and the RNG state in front of the forward stay
+    rng, kept, kept_s = [], [], []
+    for e in range(E):
+        rng.append(torch.get_rng_state())
+        out, out_s = model(up[e:e + 1], sf[e:e + 1], *consts)
+        kept.append(out.detach())
+        kept_s.append(out_s.detach())
+        del out, out_s
+    rng_end = torch.get_rng_state()
+    if not _hip_crps_ok(kept, kept_s, tgt, tgt_s):
+        raise RuntimeError("ensemble_train_step: model outputs and targets must be contiguous float32 fields of one shape on one "
+                           "HIP device")
+    st = _flat_stats(stats_last, inp.device, kept[0].shape[1], kept[0].shape[2], kept_s[0].shape[1])
+    lat = _crps_lat_weights(kept[0].shape[-2], inp.device) if lat_weighted else None
+    loss = _fair_crps_launch_fwd(kept, kept_s, tgt, tgt_s, False, st, lat)[0]
+    one = torch.ones((), dtype=torch.float32, device=inp.device)
+    _fair_crps_launch_bwd(kept, kept_s, tgt, tgt_s, False, st, lat, one, kept, kept_s)       # in place: kept now holds d loss / d out
+    for e in range(E):
+        torch.set_rng_state(rng[e])
+        out, out_s = model(up[e:e + 1], sf[e:e + 1], *consts)
+        with ops.dropped_branch_grads(policy):
+            torch.autograd.backward([out, out_s], [kept[e], kept_s[e]])
+        del out, out_s
+        kept[e] = kept_s[e] = None
+    torch.set_rng_state(rng_end)
+    _optimizer_tail(optimizer, grad_sync)
+    return loss
