@@ -89,6 +89,13 @@ int pangu_linear_wgrad_ws(pangu_stream_t stream, const float* dC, int lddc, cons
 int pangu_lora_wgrad_f32(pangu_stream_t stream, const float* dY, int lddy, const float* X, int ldx, const float* A,
                          const float* B, float* dA, float* dB, int M, int N, int K, int r, float scaling, float* workspace,
                          long long workspace_bytes);
+/* The same gradients on the bf16 training path: X and dY are bf16 (row strides in elements, multiples of 8), A and B the fp32
+ * master parameters, rounded to nearest-even bf16 by the kernel; every product is bf16 MFMA with fp32 accumulation, U = X A^T and
+ * V = dY B are rounded to bf16 once; dA / dB are fp32, WRITTEN, scaled in fp32.  Same workspace / determinism contract and error
+ * codes as the fp32 entry; X, dY, A, B and the workspace 16-B aligned. */
+int pangu_lora_wgrad_bf16(pangu_stream_t stream, const void* dY, int lddy, const void* X, int ldx, const float* A, const float* B,
+                          float* dA, float* dB, int M, int N, int K, int r, float scaling, float* workspace,
+                          long long workspace_bytes);
 /* W_eff[N][K] = W + s * (B A), the rank sum in the fixed order 0..r-1 (dense fp32; r in {4, 8, 16, 32}); capturable. */
 int pangu_lora_merge_f32(pangu_stream_t stream, const float* W, const float* A, const float* B, float* W_eff, int N, int K,
                          int r, float scaling);

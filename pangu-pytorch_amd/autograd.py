@@ -40,14 +40,10 @@ class _BF16:
         self.w, self.wt, self.table = sh.get, sh.get_t, sh.get
 
 
-def _precision(sh, lora=None):
-    """What separates the two precisions of a layer Function outside its explicit branches: kernel module `k`, operand accessors
-    `w` / `wt` / `table`, activation `dtype`, `f32_out`."""
-    if sh is None:
-        return _F32
-    if lora is not None:
-        raise RuntimeError("bf16 layer Functions take no LoRA adapters (PanguModel.forward refuses bf16 training with adapters)")
-    return _BF16(sh)
+def _precision(sh):
+    """What separates the two precisions of a layer Function outside its explicit branches: kernel module `k` (linear_wgrad and
+    lora_wgrad included), operand accessors `w` / `wt` / `table`, activation `dtype`, `f32_out`."""
+    return _F32 if sh is None else _BF16(sh)
 
 
 def _adapters(ctx, ab, n):
@@ -62,7 +58,7 @@ def _adapters(ctx, ab, n):
 def _wgrad(ctx, dy, x, w, b=None, ad=None, db_into=None, shape=None):
     """Parameter gradients of one projection y = x @ W_eff^T (+ b), W_eff = W (+ s B A when adapted).  w / b: input positions of
     the base weight and bias (b None: no bias); ad: None or (s, A, B, input position of A), from _adapters.  linear_wgrad (of ctx.pr:
-    _precision) runs only if W or b asks for a gradient, ops.lora_wgrad only if A or B does
+    _precision) runs only if W or b asks for a gradient, its lora_wgrad only if A or B does
     -> (dW (in `shape` if given), db, dA, dB), None where not computed.  Both run at the same point of the backward, so an adapter
     keeps no activation gradient alive for longer."""
     need = ctx.needs_input_grad
@@ -72,7 +68,7 @@ def _wgrad(ctx, dy, x, w, b=None, ad=None, db_into=None, shape=None):
         if shape is not None:
             dw = dw.reshape(shape)
     if ad is not None and (need[ad[3]] or need[ad[3] + 1]):
-        da, dbb = ops.lora_wgrad(dy, x, ad[1], ad[2], ad[0])
+        da, dbb = ctx.pr.k.lora_wgrad(dy, x, ad[1], ad[2], ad[0])
     return dw, db, da, dbb
 
 
@@ -100,7 +96,7 @@ class EarthBlockFn(torch.autograd.Function):
         # without adapters (layers.lora_args); m1w / m2w / a1w / a2w are then the W_eff tensors and ab = (A, B) per linear
         out = dst[0] if dst else None
         Z, H, W, heads, shifted = geom
-        ctx.pr = pr = _precision(sh, lora)
+        ctx.pr = pr = _precision(sh)
         K = pr.k
         ctx.geom, ctx.s1, ctx.s2, ctx.lora = geom, s1, s2, lora
         saved = [x, n1w, n2w, m1w, m2w, esb, a1w, a1b, a2w, *ab]
@@ -166,11 +162,12 @@ class EarthBlockFn(torch.autograd.Function):
             if pr is _F32:
                 g["m2w"], g["m2b"], g["m2A"], g["m2B"] = _wgrad(ctx, dm, h, 7, 8, ad_m2)
             if ctx.mlp_mode == 1:          # h = GELU(pre) comes out of the data-gradient GEMM's epilogue (never stored by the forward)
-                dpre, h = ob.linear_gelu_bwd(dm, pr.wt(m2w), pre, want_h=need["m2w"] or need["m2b"])
+                dpre, h = ob.linear_gelu_bwd(dm, pr.wt(m2w), pre,
+                                             want_h=need["m2w"] or need["m2b"] or need.get("m2A", False) or need.get("m2B", False))
             else:
                 dpre = K.linear(dm, pr.wt(m2w), None, act=ops.ACT_GELU_BWD, aux=pre)
             if pr is not _F32:
-                g["m2w"], g["m2b"] = _wgrad(ctx, dm, h, 7, 8)[:2]
+                g["m2w"], g["m2b"], g["m2A"], g["m2B"] = _wgrad(ctx, dm, h, 7, 8, ad_m2)
             del dm, h
             g["m1w"], g["m1b"], g["m1A"], g["m1B"] = _wgrad(ctx, dpre, x1, 5, 6, ad_m1)
             if dout.is_contiguous():      # residual gradient added in the GEMM epilogue (no extra pass over N x C)
@@ -319,7 +316,7 @@ class DownSampleFn(torch.autograd.Function):
         # whose OTHER gradient (through the channel concat) that function leaves in the slot instead of handing it to autograd:
         # the backward below sums the two inside the down-sampling kernel (no elementwise add over the 200-400 MB)
         Z, H, W = geom
-        ctx.pr = pr = _precision(sh, lora)
+        ctx.pr = pr = _precision(sh)
         g = pr.k.downsample_ln(x, nw, nb, Z, H, W)
         ctx.save_for_backward(x, g, lw, nw, *ab)
         ctx.geom, ctx.skip_grad = geom, skip_grad
@@ -349,7 +346,7 @@ class UpSampleFn(torch.autograd.Function):
     def forward(ctx, x, l1w, l2w, nw, nb, geom, sh=None, lora=None, *ab):
         # lora: scalings of (linear1, linear2) (layers.lora_args), l1w / l2w then the W_eff tensors, ab = (A1, B1, A2, B2)
         Z, H2, W2, H = geom
-        ctx.pr = pr = _precision(sh, lora)
+        ctx.pr = pr = _precision(sh)
         y = pr.k.linear(x, pr.w(l1w))
         g = pr.k.upsample_ln(y, nw, nb, Z, H2, W2, H)
         ctx.save_for_backward(x, y, g, l1w, l2w, nw, *ab)

@@ -145,7 +145,28 @@ class WeightShadow:
                 hit[1].copy_(make())
                 self.cache[key] = (tuple(ops.param_stamp(p) for p in params), hit[1])
 
+    @staticmethod
+    def _lora_owner(p):
+        """The LoraLinear whose W_eff the tensor `p` is (layers.LoraLinear.effective_weight tags it with a weak reference), or None:
+        a parameter, or a W_eff whose module is gone."""
+        ref = getattr(p, "_lora_owner", None)
+        return ref() if ref is not None else None
+
+    def _lora_lookup(self, kind, lin, p, cast):
+        """The `kind` image of the adapted projection `lin`, asked for through its W_eff tensor `p` (the layer Functions of the
+        training path hold that tensor, not the module).  W_eff is a fresh tensor per refresh, so the image is keyed by the MODULE
+        and stamped by (W, A, B), like get_lin -- keyed by id(p), every optimizer step would leave a dead entry behind -- and made
+        lazily, never as a bulk-refresh job (those run before W_eff is current).  A `p` that its module has replaced since (a
+        backward that outlived an optimizer step) gets a one-off cast that is not cached."""
+        if p is not lin._w_eff or lin._w_eff_stamp != lin._stamp():
+            return cast(p.detach())
+        return self._lookup((kind, id(lin)), (lin.weight, lin.lora_A, lin.lora_B), lambda: cast(lin.effective_weight()))
+
     def get(self, p, pad_k=None):
+        lin = self._lora_owner(p)
+        if lin is not None:
+            return self._lora_lookup("lora", lin, p, lambda w: w.to(torch.bfloat16).contiguous())
+
         def make():
             w = p.detach().reshape(p.shape[0], -1) if p.dim() == 3 else p.detach()
             if p.dim() == 5:
@@ -159,26 +180,32 @@ class WeightShadow:
     def get_lin(self, lin):
         """bf16 shadow of a projection's weight: `get(lin.weight)` for a plain nn.Linear; for a LoraLinear the cast of its W_eff,
         keyed by the stamps of W, A and B (made lazily, never a bulk-refresh job: those run before W_eff is current)."""
-        from .layers import LoraLinear
-        if type(lin) is not LoraLinear:
-            return self.get(lin.weight)
-        return self._lookup(("lora", id(lin)), (lin.weight, lin.lora_A, lin.lora_B),
-                            lambda: lin.effective_weight().to(torch.bfloat16).contiguous())
+        from .layers import eff_weight
+        return self.get(eff_weight(lin))
 
     def get_mlp_lin(self, l1, l2):
         """`get_mlp` of an Mlp's two projections, on W_eff where they carry adapters."""
-        from .layers import LoraLinear, eff_weight
-        if type(l1) is not LoraLinear and type(l2) is not LoraLinear:
-            return self.get_mlp(l1.weight, l2.weight)
-        params = tuple(p for l in (l1, l2) for p in ((l.weight, l.lora_A, l.lora_B) if type(l) is LoraLinear else (l.weight,)))
-        return self._lookup(("mlp-lora", id(l1), id(l2)), params, lambda: ob.pack_mlp_weights(eff_weight(l1), eff_weight(l2)))
+        from .layers import eff_weight
+        return self.get_mlp(eff_weight(l1), eff_weight(l2))
 
     def get_t(self, p):
         """Transposed bf16 shadow (in, out): the `W` operand of the input-gradient GEMM dA = dC @ W."""
+        lin = self._lora_owner(p)
+        if lin is not None:
+            return self._lora_lookup("lora-t", lin, p, lambda w: w.t().to(torch.bfloat16).contiguous())
         return self._lookup(("t", id(p)), (p,),
                             lambda: p.detach().reshape(p.shape[0], -1).t().to(torch.bfloat16).contiguous(), mode=1)
 
     def get_mlp(self, w1, w2):
-        """Packed chunk image of an Mlp's two weights for the fused MLP kernel (ops_bf16.pack_mlp_weights)."""
-        return self._lookup(("mlp", id(w1), id(w2)), (w1, w2), lambda: ob.pack_mlp_weights(w1.detach(), w2.detach()),
-                            mode=2, idx=lambda: ob.mlp_pack_index32(w1.shape[1], w1.device))
+        """Packed chunk image of an Mlp's two weights for the fused MLP kernel (ops_bf16.pack_mlp_weights).  Where a weight is the
+        W_eff of an adapted projection the image is keyed by that module and stamped by its (W, A, B), as in _lora_lookup."""
+        lins = (self._lora_owner(w1), self._lora_owner(w2))
+        if lins[0] is None and lins[1] is None:
+            return self._lookup(("mlp", id(w1), id(w2)), (w1, w2), lambda: ob.pack_mlp_weights(w1.detach(), w2.detach()),
+                                mode=2, idx=lambda: ob.mlp_pack_index32(w1.shape[1], w1.device))
+        if any(l is not None and (w is not l._w_eff or l._w_eff_stamp != l._stamp()) for l, w in zip(lins, (w1, w2))):
+            return ob.pack_mlp_weights(w1.detach(), w2.detach())
+        src = tuple((lambda l=l: l.effective_weight()) if l is not None else (lambda w=w: w.detach()) for l, w in zip(lins, (w1, w2)))
+        params = tuple(q for l, w in zip(lins, (w1, w2)) for q in ((l.weight, l.lora_A, l.lora_B) if l is not None else (w,)))
+        return self._lookup(("mlp-lora",) + tuple(id(l) if l is not None else id(w) for l, w in zip(lins, (w1, w2))), params,
+                            lambda: ob.pack_mlp_weights(src[0](), src[1]()))

@@ -8,6 +8,7 @@ all view/pad/roll/permute/crop steps folded into kernel address arithmetic.  nn.
 nn.LayerNorm sub-modules are parameter containers only.
 """
 import math
+import weakref
 from collections import OrderedDict
 
 import torch
@@ -61,7 +62,7 @@ class LoraLinear(nn.Linear):
     The kernels never see A and B in the forward: they run on W_eff (`effective_weight()`), a derived tensor made by
     `pangu_lora_merge_f32` and re-made only when the stamp (ops.param_stamp) of W, A or B changes -- like the bf16 weight
     shadows, it is never pickled and is dropped by `.to()` / `invalidate_shadows`.  The adapter gradients come from
-    `pangu_lora_wgrad_f32` in the backward of the layer functions (autograd.py)."""
+    `pangu_lora_wgrad_f32` (`pangu_lora_wgrad_bf16` on the bf16 training path) in the backward of the layer functions (autograd.py)."""
 
     def __init__(self, in_features, out_features, bias=True, r=16, alpha=16, device=None, dtype=None):
         super().__init__(in_features, out_features, bias=bias, device=device, dtype=dtype)
@@ -114,6 +115,8 @@ class LoraLinear(nn.Linear):
                     w = ops.lora_merge(self.weight.detach(), self.lora_A.detach(), self.lora_B.detach(), self.scaling)
             else:
                 w = self.weight.detach() + self.scaling * (self.lora_B.detach() @ self.lora_A.detach())
+        # (the bf16 weight shadows key their images of W_eff by this module, not by the per-refresh tensor: WeightShadow._lora_owner)
+        w._lora_owner = weakref.ref(self)
         self._w_eff, self._w_eff_stamp = w, stamp
         return w
 

@@ -300,6 +300,29 @@ def linear_wgrad(dc, a, want_bias=True, db_into=None):
     return dw, db
 
 
+def lora_wgrad(dy, x, A, B, scaling):
+    """ops.lora_wgrad on the bf16 path: (dA (r, K), dB (N, r)) fp32 from the bf16 row-strided x (M, K) and dy (M, N) and the fp32
+    master adapters A, B (rounded to bf16 by the kernel); one pass, deterministic, through the stream's weight-gradient workspace."""
+    lib = _lib.load()
+    dp, lddy = _rows(dy, "lora_wgrad.dy")
+    xp, ldx = _rows(x, "lora_wgrad.x")
+    M, N = dy.shape
+    K = x.shape[1]
+    r = A.shape[0]
+    if (x.shape[0] != M or tuple(A.shape) != (r, K) or tuple(B.shape) != (N, r) or dy.dtype != torch.bfloat16
+            or x.dtype != torch.bfloat16):
+        raise RuntimeError(f"lora_wgrad: dy {tuple(dy.shape)} {dy.dtype} x {tuple(x.shape)} {x.dtype} A {tuple(A.shape)} "
+                           f"B {tuple(B.shape)}")
+    ws = _wgrad_workspace(dy.device)
+    dA = torch.empty((r, K), dtype=torch.float32, device=dy.device)
+    dB = torch.empty((N, r), dtype=torch.float32, device=dy.device)
+    with _timed("lora_wgrad", 2.0 * M * (K + N)):          # bytes: the pass is HBM-bound (DESIGN.md, LoRA section)
+        _lib.check(lib.pangu_lora_wgrad_bf16(_stream(dy), dp, lddy, xp, ldx, _p(A, "lora_A", torch.float32),
+                                             _p(B, "lora_B", torch.float32), dA.data_ptr(), dB.data_ptr(), M, N, K, r,
+                                             float(scaling), ws.data_ptr(), _WGRAD_WS_BYTES), "lora_wgrad_bf16")
+    return dA, dB
+
+
 def window_attention_bwd(qkv, qkv_bias, esb, out, lse, dout, Z, H, W, heads, shifted, desb_out=None):
     lib = _lib.load()
     N, C3 = qkv.shape

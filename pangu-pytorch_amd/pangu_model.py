@@ -168,11 +168,14 @@ class PanguModel(nn.Module):
     # modules_to_save=["_output_layer.conv", "_output_layer.conv_surface"])) ------------------------------------------------
 
     def enable_lora(self, r=16, alpha=16, target_modules=None, train_also=("_output_layer.conv", "_output_layer.conv_surface"),
-                    dropout=0.0):
+                    dropout=0.0, bf16_training=False):
         """Replace each targeted nn.Linear IN PLACE by a layers.LoraLinear holding the same base Parameters (default: all 67, as
         the reference does), and freeze everything except the adapters and the modules named in `train_also` (trained in full,
         peft's `modules_to_save`).  target_modules: None, or names / name suffixes ("linear1", "attention.linear2", ...) as peft
-        matches them.  Returns the list of adapted module names."""
+        matches them.  bf16_training: allow the adapted model to TRAIN in bf16 mixed precision (`set_compute_dtype(torch.bfloat16)`
+        or bf16 autocast): fp32 master adapters and adapter gradients, bf16 images of W_eff, adapter gradients from
+        `pangu_lora_wgrad_bf16`; without it a bf16 training forward of an adapted model is refused.  Returns the list of adapted
+        module names."""
         from .layers import LoraLinear
         from .ops import LORA_RANKS
         if r not in LORA_RANKS:
@@ -209,6 +212,7 @@ class PanguModel(nn.Module):
             for p in mods[t].parameters():
                 p.requires_grad_(True)
         self._lora_train_also = train_also
+        self._lora_bf16_training = bool(bf16_training)      # (a plain attribute: deepcopy and pickle keep it)
         self.invalidate_shadows()
         return adapted
 
@@ -224,6 +228,7 @@ class PanguModel(nn.Module):
                         child.weight.copy_(child.effective_weight().view_as(child.weight))
                         setattr(mod, cname, child.to_linear())
         self._lora_train_also = ()
+        self._lora_bf16_training = False
         self.invalidate_shadows()
         return self
 
@@ -293,10 +298,11 @@ class PanguModel(nn.Module):
         want_bf16 = self.compute_dtype == torch.bfloat16 or (
             torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16)
         rev = bool(levels_reversed)
-        if grad_path and want_bf16 and self.has_lora():
+        if grad_path and want_bf16 and not getattr(self, "_lora_bf16_training", False) and self.has_lora():
             raise RuntimeError("PanguModel: bf16 training with LoRA adapters is not implemented (the bf16 autograd path's fused "
                                "MLP / QKV kernels do not keep the operands the adapter gradients need); train in fp32, or "
-                               "run bf16 inference under torch.no_grad()")
+                               "run bf16 inference under torch.no_grad(); or opt in to bf16 adapter training with "
+                               "enable_lora(..., bf16_training=True)")
         if grad_path and not self.training and getattr(self, "eval_grad_mode", "save") == "recompute":
             return _EvalRecomputeFn.apply(self, (statistics, maps, const_h, want_bf16, rev), input, input_surface, *self.parameters())
         return self._forward_dispatch(input, input_surface, statistics, maps, const_h, want_bf16, grad_path, rev)

@@ -1,13 +1,18 @@
 #!/usr/bin/env python3
 """LoRA measurements (LoRA section):
 
-  python tools/bench_lora.py [--steps 5] [--warmup 2] [--rank 16] [--skip-train]
+  python tools/bench_lora.py [--dtype fp32|bf16] [--steps 5] [--warmup 2] [--rank 16] [--skip-train]
 
 1. `ops.lora_wgrad` per (K -> N) projection of the model at its real token count, against its roof
    max(bytes / 6.29 TB/s, FLOPs / 157.3 TF/s), bytes = 4 M (K + N), FLOPs = 4 M r (K + N).
 2. In one process, same seeded batch, DropPath off, alternating: the fp32 `train.train_step` of the full fine-tune against the
    LoRA fine-tune (enable_lora(r)), ms/step for both, their ratio, and the peak memory of each.
-Prints one JSON line per section."""
+Prints one JSON line per section.
+
+--dtype bf16: `ops_bf16.lora_wgrad` per shape against its roof 2 M (K + N) / 6.29 TB/s and against `ops_bf16.linear_wgrad` of the
+same shape (the launch a LoRA step skips); then, alternating in one process, the bf16 full fine-tune step, the bf16 LoRA step
+(enable_lora(r, bf16_training=True)) and the fp32 LoRA step: ms/step, ratios, peak memory, and the host + GPU time of re-making
+the 67 W_eff images after an optimizer step.  One JSON line, also written to profiles/lora_bf16.json."""
 import argparse
 import copy
 import json
@@ -51,6 +56,110 @@ def kernels(P, r, reps=20):
                      "frac_of_roof": round(roof_ms / ms, 3), "TBps": round(byt / ms / 1e9, 3)})
         del x, dy
     return rows
+
+
+def _time(fn, reps, warm=3):
+    for _ in range(warm):
+        fn()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def kernels_bf16(P, r, reps=20):
+    ob = P.ops_bf16
+    rows = []
+    for K, N, M in SHAPES:
+        g = torch.Generator(device="cuda").manual_seed(K + N)
+        x = torch.randn(M, K, device="cuda", generator=g).to(torch.bfloat16)
+        dy = torch.randn(M, N, device="cuda", generator=g).to(torch.bfloat16)
+        A = torch.randn(r, K, device="cuda", generator=g) * 0.1
+        B = torch.randn(N, r, device="cuda", generator=g) * 0.1
+        # alternately, twice each: both kernels see the same clocks
+        ms, wg = [], []
+        for _ in range(2):
+            ms.append(_time(lambda: ob.lora_wgrad(dy, x, A, B, 1.0), reps))
+            wg.append(_time(lambda: ob.linear_wgrad(dy, x, want_bias=False), reps))
+        ms, wg = min(ms), min(wg)
+        byt = 2.0 * M * (K + N)
+        roof_ms = byt / HBM * 1e3
+        rows.append({"K": K, "N": N, "M": M, "r": r, "ms": round(ms, 4), "roof_ms": round(roof_ms, 4),
+                     "frac_of_roof": round(roof_ms / ms, 3), "TBps": round(byt / ms / 1e9, 3),
+                     "linear_wgrad_ms": round(wg, 4), "vs_linear_wgrad": round(ms / wg, 3)})
+        del x, dy
+    return rows
+
+
+def train_compare_bf16(P, r, steps, warmup):
+    import time
+
+    import cases
+    import synth
+    from pangu_pytorch_amd import train
+    base = P.PanguModel(device="cuda").cuda()
+    base.load_state_dict(synth.fill_state_dict(cases.model_param_shapes(), "cuda"))
+    for m in base.modules():
+        if isinstance(m, P.layers.DropPath):
+            m.drop_prob = 0.0
+    inp, inp_s, stats, maps, const_h = cases.model_inputs("cuda")
+    tgt, tgt_s = cases.model_targets("cuda")
+    batch = (inp, inp_s, tgt, tgt_s)
+    full = copy.deepcopy(base).train()
+    full.set_compute_dtype(torch.bfloat16)
+    lora = copy.deepcopy(base).train()
+    lora.enable_lora(r=r, alpha=r, bf16_training=True)
+    lora.set_compute_dtype(torch.bfloat16)
+    lora32 = copy.deepcopy(base).train()
+    lora32.enable_lora(r=r, alpha=r)
+    del base
+    runs = {k: (m, train.make_optimizer(m)) for k, m in (("full_bf16", full), ("lora_bf16", lora), ("lora_fp32", lora32))}
+    times = {k: [] for k in runs}
+    peak = {}
+    for i in range(warmup + steps):
+        for k, (m, opt) in runs.items():            # alternating: all see the same clocks and thermal state
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            train.train_step(m, opt, batch, stats, maps, const_h)
+            b.record()
+            torch.cuda.synchronize()
+            if i >= warmup:
+                times[k].append(a.elapsed_time(b))
+            peak[k] = max(peak.get(k, 0), torch.cuda.max_memory_allocated())
+    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    # the per-step remake of the W_eff images (merge kernel + plain / transposed / packed casts of 67 projections), on its own:
+    # the state right after an optimizer step, then every image the training step asks for
+    sh = lora._shadow
+    lins = [m for m in lora.modules() if type(m) is P.layers.LoraLinear]
+    blocks = [m for m in lora.modules() if type(m) is P.layers.EarthSpecificBlock]
+    in_mlp = {id(l) for b in blocks for l in (b.linear.linear1, b.linear.linear2)}
+
+    def remake():
+        P.ops.bump_weights_epoch()
+        for b in blocks:
+            sh.get_mlp(P.layers.eff_weight(b.linear.linear1), P.layers.eff_weight(b.linear.linear2))
+        for l in lins:
+            w = l.effective_weight()
+            if id(l) not in in_mlp:          # (the MLP projections' forward image is the packed one above)
+                sh.get(w)
+            sh.get_t(w)
+    remake()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    gpu_ms = _time(remake, 5, warm=1)
+    host_ms = (time.perf_counter() - t0) * 1e3 / 6
+    return {"rank": r, "steps": steps, **{k + "_ms": round(v, 2) for k, v in med.items()},
+            "ratio_lora_bf16_to_full_bf16": round(med["lora_bf16"] / med["full_bf16"], 3),
+            "ratio_lora_bf16_to_lora_fp32": round(med["lora_bf16"] / med["lora_fp32"], 3),
+            **{k + "_peak_GB": round(v / 1e9, 2) for k, v in peak.items()},
+            "w_eff_remake_gpu_ms": round(gpu_ms, 3), "w_eff_remake_wall_ms": round(host_ms, 3),
+            "trainable_params": {k: sum(p.numel() for p in m.parameters() if p.requires_grad) for k, (m, _) in runs.items()}}
 
 
 def train_compare(P, r, steps, warmup):
@@ -98,9 +207,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rank", type=int, default=16)
     ap.add_argument("--skip-train", action="store_true")
+    ap.add_argument("--dtype", choices=("fp32", "bf16"), default="fp32")
     a = ap.parse_args()
     import pangu_pytorch_amd as P
     P._lib.load()
+    if a.dtype == "bf16":
+        res = {"lora_wgrad_bf16": kernels_bf16(P, a.rank)}
+        if not a.skip_train:
+            res["train_step_bf16"] = train_compare_bf16(P, a.rank, a.steps, a.warmup)
+        line = json.dumps(res)
+        print(line, flush=True)
+        with open(os.path.join(ROOT, "profiles", "lora_bf16.json"), "w") as f:
+            f.write(line + "\n")
+        return
     print(json.dumps({"lora_wgrad": kernels(P, a.rank)}), flush=True)
     if not a.skip_train:
         print(json.dumps({"train_step": train_compare(P, a.rank, a.steps, a.warmup)}), flush=True)
