@@ -100,6 +100,31 @@ int pangu_lora_wgrad_bf16(pangu_stream_t stream, const void* dY, int lddy, const
 int pangu_lora_merge_f32(pangu_stream_t stream, const float* W, const float* A, const float* B, float* W_eff, int N, int K,
                          int r, float scaling);
 
+/* ---- LoRA adapter dropout (peft's lora_dropout; fp32).  In training mode peft computes y = X W^T + b + s * drop(X) A^T B^T with
+ * drop(X) = keep * X / (1 - p).  The projection kernels run on W_eff, so with c = keep / (1 - p) - 1 the dropout is an additive
+ * correction after the projection's forward launch and after its input-gradient GEMM.  The keep mask is a pure function of
+ * (seed, row i of the [M][K] operand, column k) and is never stored:
+ *   keep(seed, i, k) = lowbias32(lowbias32(lowbias32(seed) ^ i) ^ k) >= T,   T = clamp(floor(p * 2^32 + 0.5), 1, 2^32 - 1),
+ *   lowbias32(x): x ^= x>>16; x *= 0x7feb352d; x ^= x>>15; x *= 0x846ca68b; x ^= x>>16   (uint32).
+ * Common contract: 0 < p < 1 (PANGU_E_ARG otherwise), r in {4, 8, 16, 32}, K and N multiples of 64 with K + N <= 1920, row strides
+ * multiples of 4 floats, every pointer 16-B aligned; no atomics, bit-identical from run to run; capturable. */
+
+/* Y[M][N] (row stride ldy) += s * ((c * X) A^T) B^T, in place, X [M][K] (row stride ldx).  act = PANGU_ACT_GELU: H[M][N] (row
+ * stride ldh) = gelu(Y) of the corrected Y is written as well (the MLP's first projection then runs its GEMM without the GELU
+ * epilogue); PANGU_ACT_NONE: H is not touched (may be NULL). */
+int pangu_lora_dropout_fwd_f32(pangu_stream_t stream, const float* X, int ldx, float* Y, int ldy, const float* A, const float* B,
+                               int M, int N, int K, int r, float scaling, double p, unsigned seed, int act, float* H, int ldh);
+/* pangu_lora_wgrad_f32 with drop(X) in place of X: dA = s * (dY B)^T drop(X), dB = s * dY^T (drop(X) A^T), and one more output,
+ * V[M][r] = s * dY B (dense), which pangu_lora_dropout_dx_f32 reads.  Workspace and error codes as pangu_lora_wgrad_f32. */
+int pangu_lora_wgrad_dropout_f32(pangu_stream_t stream, const float* dY, int lddy, const float* X, int ldx, const float* A,
+                                 const float* B, float* dA, float* dB, float* V, int M, int N, int K, int r, float scaling, double p,
+                                 unsigned seed, float* workspace, long long workspace_bytes);
+/* dX[M][K] (row stride lddx) += c * (V A), in place, V [M][r] from the entry above.  pre (optional, [M][K], row stride ldpre):
+ * the projection's input is gelu(pre) and dX already holds the gradient of pre (PANGU_ACT_GELU_BWD epilogue of the dX GEMM); the
+ * correction is multiplied by gelu'(pre) as well. */
+int pangu_lora_dropout_dx_f32(pangu_stream_t stream, float* dX, int lddx, const float* V, const float* A, int M, int K, int r,
+                              double p, unsigned seed, const float* pre, int ldpre);
+
 /* ---- Earth-specific window attention -------------------------------------------------------------- */
 
 /* Fused roll + window partition + (q*scale)k^T + earth_specific_bias + shift mask + softmax + .v +

@@ -55,10 +55,32 @@ def _adapters(ctx, ab, n):
     return tuple(None if s is None else (s, ab[2 * i], ab[2 * i + 1], p + 2 * i) for i, s in enumerate(ctx.lora))
 
 
+def _dropout_fwd(pr, lora, ab, i, x, y, act=ops.ACT_NONE, h=None):
+    """After the forward launch y = x W_eff^T (+ b) of a Function's projection i (its place in `lora`): the adapter-dropout
+    correction y += s ((c * x) A^T) B^T in place, when that projection's `lora` entry is (scaling, p, seed) -- layers.lora_args,
+    dropout active; nothing otherwise.  act=ACT_GELU: h = gelu(y) is produced as well -> whether it ran."""
+    e = lora[i] if lora is not None else None
+    if type(e) is not tuple:
+        return False
+    if pr is not _F32:
+        raise RuntimeError("LoRA adapter dropout in train() mode is fp32 only (no bf16 correction kernels)")
+    ops.lora_dropout_fwd(x, y, ab[2 * i], ab[2 * i + 1], *e, act=act, h=h)
+    return True
+
+
+def _dropout_dx(ctx, ad, dx, pre=None):
+    """After the input-gradient GEMM of the same projection: dx += c * (V A) in place on that GEMM's result `dx` (never the
+    incoming gradient), V kept by _wgrad.  pre: see ops.lora_dropout_dx (the projection behind a GELU) -> dx."""
+    if ad is not None and type(ad[0]) is tuple:
+        ops.lora_dropout_dx(dx, ctx.lora_V.pop(ad[3]), ad[1], ad[0][1], ad[0][2], pre=pre)
+    return dx
+
+
 def _wgrad(ctx, dy, x, w, b=None, ad=None, db_into=None, shape=None):
     """Parameter gradients of one projection y = x @ W_eff^T (+ b), W_eff = W (+ s B A when adapted).  w / b: input positions of
     the base weight and bias (b None: no bias); ad: None or (s, A, B, input position of A), from _adapters.  linear_wgrad (of ctx.pr:
-    _precision) runs only if W or b asks for a gradient, its lora_wgrad only if A or B does
+    _precision) runs only if W or b asks for a gradient, its lora_wgrad only if A or B does.  With active adapter dropout (s is
+    (scaling, p, seed)) the dropout variant runs instead, always: its third result V = s dy B stays on ctx for _dropout_dx
     -> (dW (in `shape` if given), db, dA, dB), None where not computed.  Both run at the same point of the backward, so an adapter
     keeps no activation gradient alive for longer."""
     need = ctx.needs_input_grad
@@ -67,7 +89,12 @@ def _wgrad(ctx, dy, x, w, b=None, ad=None, db_into=None, shape=None):
         dw, db = ctx.pr.k.linear_wgrad(dy, x, want_bias=b is not None, db_into=db_into)
         if shape is not None:
             dw = dw.reshape(shape)
-    if ad is not None and (need[ad[3]] or need[ad[3] + 1]):
+    if ad is not None and type(ad[0]) is tuple:
+        da, dbb, V = ops.lora_wgrad_dropout(dy, x, ad[1], ad[2], *ad[0])
+        if getattr(ctx, "lora_V", None) is None:
+            ctx.lora_V = {}
+        ctx.lora_V[ad[3]] = V
+    elif ad is not None and (need[ad[3]] or need[ad[3] + 1]):
         da, dbb = ctx.pr.k.lora_wgrad(dy, x, ad[1], ad[2], ad[0])
     return dw, db, da, dbb
 
@@ -93,7 +120,8 @@ class EarthBlockFn(torch.autograd.Function):
         # dst: optional 1-tuple holding the (N, C) row-strided tensor the block writes its result into (one half of the
         # skip-concat buffer of reference pangu_model.py:81); wrapped so that autograd does not see a tensor argument.
         # lora: scalings of (linear.linear1, linear.linear2, attention.linear1, attention.linear2), None where not adapted, or None
-        # without adapters (layers.lora_args); m1w / m2w / a1w / a2w are then the W_eff tensors and ab = (A, B) per linear
+        # without adapters (layers.lora_args); m1w / m2w / a1w / a2w are then the W_eff tensors and ab = (A, B) per linear.  Where
+        # an entry is (scaling, p, seed) the projection's adapter dropout is active: _dropout_fwd follows its launch
         out = dst[0] if dst else None
         Z, H, W, heads, shifted = geom
         ctx.pr = pr = _precision(sh)
@@ -103,8 +131,10 @@ class EarthBlockFn(torch.autograd.Function):
         x1 = x
         if s1 != 0.0:
             qkv = K.linear(x, pr.w(a1w), a1b)
+            _dropout_fwd(pr, lora, ab, 2, x, qkv)
             o, lse = K.window_attention(qkv, pr.table(a1b), pr.table(esb), Z, H, W, heads, shifted, want_lse=True)
             y = K.linear(o, pr.w(a2w), a2b)
+            _dropout_fwd(pr, lora, ab, 3, o, y)
             # (a dropped MLP branch -- s2 == 0 -- makes x1 the block's result: written straight into `out`, no copy afterwards)
             x1 = K.ln_residual(y, x, n1w, n1b, branch_scale=s1, out=out if s2 == 0.0 else None)
             saved += [qkv, o, lse, y]
@@ -116,13 +146,20 @@ class EarthBlockFn(torch.autograd.Function):
         # layers.py:115-119 -- measured +2.7 ms per step and was removed in round 4; so were the QKV-inside-attention training
         # forward, +0.3 ms, and weight gradients on a second stream, +0.5 ms.  DESIGN.md keeps the numbers.)
         ctx.mlp_mode = mode = 1 if (sh is not None and x.shape[1] in (192, 384) and x1.is_contiguous()) else 0
+        if sh is not None and lora is not None and any(type(e) is tuple for e in lora):
+            raise RuntimeError("LoRA adapter dropout in train() mode is fp32 only (no bf16 correction kernels)")
         if s2 != 0.0 and mode:
             x2, pre, m = ob.mlp_ln_residual_train(x1, sh.get_mlp(m1w, m2w), m1b, m2b, n2w, n2b, branch_scale=s2, out=out)
             saved += [x1, pre, m]
         elif s2 != 0.0:
             pre = torch.empty((x.shape[0], m1w.shape[0]), dtype=x.dtype, device=x.device)
-            h = K.linear(x1, pr.w(m1w), m1b, act=ops.ACT_GELU, aux=pre)
+            if lora is not None and type(lora[0]) is tuple:      # the GEMM without its GELU epilogue; the correction makes pre and h
+                h = torch.empty_like(pre)
+                _dropout_fwd(pr, lora, ab, 0, x1, K.linear(x1, pr.w(m1w), m1b, out=pre), act=ops.ACT_GELU, h=h)
+            else:
+                h = K.linear(x1, pr.w(m1w), m1b, act=ops.ACT_GELU, aux=pre)
             m = K.linear(h, pr.w(m2w), m2b)
+            _dropout_fwd(pr, lora, ab, 1, h, m)
             x2 = K.ln_residual(m, x1, n2w, n2b, out=out, branch_scale=s2)
             saved += [x1, pre, h, m]
         elif out is not None:
@@ -165,7 +202,7 @@ class EarthBlockFn(torch.autograd.Function):
                 dpre, h = ob.linear_gelu_bwd(dm, pr.wt(m2w), pre,
                                              want_h=need["m2w"] or need["m2b"] or need.get("m2A", False) or need.get("m2B", False))
             else:
-                dpre = K.linear(dm, pr.wt(m2w), None, act=ops.ACT_GELU_BWD, aux=pre)
+                dpre = _dropout_dx(ctx, ad_m2, K.linear(dm, pr.wt(m2w), None, act=ops.ACT_GELU_BWD, aux=pre), pre=pre)
             if pr is not _F32:
                 g["m2w"], g["m2b"], g["m2A"], g["m2B"] = _wgrad(ctx, dm, h, 7, 8, ad_m2)
             del dm, h
@@ -175,12 +212,13 @@ class EarthBlockFn(torch.autograd.Function):
             else:
                 dx1 = K.linear(dpre, pr.wt(m1w))
                 dx1 += dout
+            _dropout_dx(ctx, ad_m1, dx1)
             del dpre
         dx = dx1
         if s1 != 0.0:
             dy, g["n1w"], g["n1b"] = K.ln_residual_bwd(dx1, y, n1w, s1)
             g["a2w"], g["a2b"], g["a2A"], g["a2B"] = _wgrad(ctx, dy, o, 12, 13, ad_a2)
-            do = K.linear(dy, pr.wt(a2w))
+            do = _dropout_dx(ctx, ad_a2, K.linear(dy, pr.wt(a2w)))
             del dy
             # (the bias-table gradient goes straight into the DP flat buffer)
             dqkv, dqb_pad, desb = K.window_attention_bwd(qkv, pr.table(a1b), pr.table(esb), o, lse, do, Z, H, W, heads, shifted,
@@ -194,6 +232,7 @@ class EarthBlockFn(torch.autograd.Function):
             else:
                 dx = K.linear(dqkv, pr.wt(a1w))
                 dx += dx1
+            _dropout_dx(ctx, ad_a1, dx)
         elif not dx.is_contiguous():
             dx = dx.contiguous()
         g["x"] = dx
@@ -213,10 +252,13 @@ class AttentionWindowsFn(torch.autograd.Function):
         # lora: scalings of (linear1, linear2) (layers.lora_args), w1 / w2 then the W_eff tensors, ab = (A1, B1, A2, B2)
         n_lon, types, heads = geom
         qkv = ops.linear(xw, w1, b1)
+        _dropout_fwd(_F32, lora, ab, 0, xw, qkv)
         o = ops.attention_windows(qkv, esb[0], mask, n_lon, types, heads)
         ctx.save_for_backward(xw, qkv, o, w1, w2, esb, mask, *ab)
         ctx.geom, ctx.lora, ctx.pr = geom, lora, _F32
-        return ops.linear(o, w2, b2)
+        y = ops.linear(o, w2, b2)
+        _dropout_fwd(_F32, lora, ab, 1, o, y)
+        return y
 
     @staticmethod
     def backward(ctx, dy):
@@ -225,10 +267,10 @@ class AttentionWindowsFn(torch.autograd.Function):
         n_lon, types, heads = ctx.geom
         dy = dy.contiguous()
         dw2, db2, dA2, dB2 = _wgrad(ctx, dy, o, 3, 4, ad2)
-        do = ops.linear(dy, _wt(w2))
+        do = _dropout_dx(ctx, ad2, ops.linear(dy, _wt(w2)))
         dqkv, desb = ops.attention_windows_bwd(qkv, esb[0], mask, do, n_lon, types, heads)
         dw1, db1, dA1, dB1 = _wgrad(ctx, dqkv, xw, 1, 2, ad1)
-        dx = ops.linear(dqkv, _wt(w1))
+        dx = _dropout_dx(ctx, ad1, ops.linear(dqkv, _wt(w1)))
         return _keep_needed(ctx, (dx, dw1, db1, dw2, db2, desb.unsqueeze(0), None, None, None, dA1, dB1, dA2, dB2))
 
 
@@ -239,10 +281,16 @@ class MlpFn(torch.autograd.Function):
     def forward(ctx, x, w1, b1, w2, b2, lora=None, *ab):
         # lora: scalings of (linear1, linear2) (layers.lora_args), w1 / w2 then the W_eff tensors, ab = (A1, B1, A2, B2)
         pre = torch.empty((x.shape[0], w1.shape[0]), dtype=x.dtype, device=x.device)
-        h = ops.linear(x, w1, b1, act=ops.ACT_GELU, aux=pre)
+        if lora is not None and type(lora[0]) is tuple:      # (as in EarthBlockFn: the correction makes pre and h)
+            h = torch.empty_like(pre)
+            _dropout_fwd(_F32, lora, ab, 0, x, ops.linear(x, w1, b1, out=pre), act=ops.ACT_GELU, h=h)
+        else:
+            h = ops.linear(x, w1, b1, act=ops.ACT_GELU, aux=pre)
         ctx.save_for_backward(x, pre, h, w1, w2, *ab)
         ctx.lora, ctx.pr = lora, _F32
-        return ops.linear(h, w2, b2)
+        m = ops.linear(h, w2, b2)
+        _dropout_fwd(_F32, lora, ab, 1, h, m)
+        return m
 
     @staticmethod
     def backward(ctx, dm):
@@ -250,9 +298,9 @@ class MlpFn(torch.autograd.Function):
         ad1, ad2 = _adapters(ctx, ab, 2)
         dm = dm.contiguous()
         dw2, db2, dA2, dB2 = _wgrad(ctx, dm, h, 3, 4, ad2)
-        dpre = ops.linear(dm, _wt(w2), None, act=ops.ACT_GELU_BWD, aux=pre)
+        dpre = _dropout_dx(ctx, ad2, ops.linear(dm, _wt(w2), None, act=ops.ACT_GELU_BWD, aux=pre), pre=pre)
         dw1, db1, dA1, dB1 = _wgrad(ctx, dpre, x, 1, 2, ad1)
-        return _keep_needed(ctx, (ops.linear(dpre, _wt(w1)), dw1, db1, dw2, db2, None, dA1, dB1, dA2, dB2))
+        return _keep_needed(ctx, (_dropout_dx(ctx, ad1, ops.linear(dpre, _wt(w1))), dw1, db1, dw2, db2, None, dA1, dB1, dA2, dB2))
 
 
 def refuse_constant_grads(maps, const_h, statistics=()):
@@ -323,15 +371,18 @@ class DownSampleFn(torch.autograd.Function):
         ctx.lora = lora          # (scaling,) of an adapted linear (layers.lora_args): lw is then W_eff, ab = (A, B)
         if skip_grad is not None:
             skip_grad[1] = True                  # armed: this node's backward will consume the slot
-        return pr.k.linear(g, pr.w(lw))
+        y = pr.k.linear(g, pr.w(lw))
+        _dropout_fwd(pr, lora, ab, 0, g, y)
+        return y
 
     @staticmethod
     def backward(ctx, dout):
         x, g, lw, nw, *ab = ctx.saved_tensors
         Z, H, W = ctx.geom
         dout = dout.contiguous()
-        dlw, _, dA, dB = _wgrad(ctx, dout, g, 1, ad=_adapters(ctx, ab, 1)[0])
-        dg = ctx.pr.k.linear(dout, ctx.pr.wt(lw))
+        ad = _adapters(ctx, ab, 1)[0]
+        dlw, _, dA, dB = _wgrad(ctx, dout, g, 1, ad=ad)
+        dg = _dropout_dx(ctx, ad, ctx.pr.k.linear(dout, ctx.pr.wt(lw)))
         add = None
         if ctx.skip_grad is not None:
             add, ctx.skip_grad[0] = ctx.skip_grad[0], None
@@ -348,10 +399,13 @@ class UpSampleFn(torch.autograd.Function):
         Z, H2, W2, H = geom
         ctx.pr = pr = _precision(sh)
         y = pr.k.linear(x, pr.w(l1w))
+        _dropout_fwd(pr, lora, ab, 0, x, y)
         g = pr.k.upsample_ln(y, nw, nb, Z, H2, W2, H)
         ctx.save_for_backward(x, y, g, l1w, l2w, nw, *ab)
         ctx.geom, ctx.lora = geom, lora
-        return pr.k.linear(g, pr.w(l2w))
+        out = pr.k.linear(g, pr.w(l2w))
+        _dropout_fwd(pr, lora, ab, 1, g, out)
+        return out
 
     @staticmethod
     def backward(ctx, dout):
@@ -361,10 +415,10 @@ class UpSampleFn(torch.autograd.Function):
         pr = ctx.pr
         dout = dout.contiguous()
         dl2w, _, dA2, dB2 = _wgrad(ctx, dout, g, 2, ad=ad2)
-        dg = pr.k.linear(dout, pr.wt(l2w))
+        dg = _dropout_dx(ctx, ad2, pr.k.linear(dout, pr.wt(l2w)))
         dy, dnw, dnb = pr.k.upsample_ln_bwd(dg, y, nw, Z, H2, W2, H)
         dl1w, _, dA1, dB1 = _wgrad(ctx, dy, x, 1, ad=ad1)
-        dx = pr.k.linear(dy, pr.wt(l1w))
+        dx = _dropout_dx(ctx, ad1, pr.k.linear(dy, pr.wt(l1w)))
         return _keep_needed(ctx, (dx, dl1w, dl2w, dnw, dnb, None, None, None, dA1, dB1, dA2, dB2))
 
 

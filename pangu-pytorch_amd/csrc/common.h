@@ -144,6 +144,38 @@ __device__ inline float group_sum(float v) {
 }
 __device__ inline float wave_sum(float v) { return group_sum<64>(v); }
 
+// The 32-bit integer hash of the ensemble noise (ensemble.hip) and of the LoRA dropout mask (below).
+__host__ __device__ inline uint32_t lowbias32(uint32_t x) {
+  x ^= x >> 16;
+  x *= 0x7feb352du;
+  x ^= x >> 15;
+  x *= 0x846ca68bu;
+  x ^= x >> 16;
+  return x;
+}
+
+// LoRA adapter dropout (lora_dropout_f32.hip, the dropout policy of lora_f32.hip).  The keep mask of the (M, K) adapter input is a
+// pure function of (seed, row i, column k), so the backward recomputes it and no mask is ever stored:
+//   keep(seed, i, k) = lowbias32(lowbias32(lowbias32(seed) ^ i) ^ k) >= T,   T = clamp(floor(p * 2^32 + 0.5), 1, 2^32 - 1)
+// (restated on the host by layers.lora_dropout_keep).  drop(x) = keep * x / (1 - p) = x + c * x with c = p / (1 - p) where kept, -1
+// where dropped.
+struct LoraDrop {
+  uint32_t hseed, T;      // lowbias32(seed), the threshold
+  float c_keep, inv;      // p / (1 - p), 1 / (1 - p)
+};
+static inline bool lora_drop_make(double p, uint32_t seed, LoraDrop* d) {      // false: p outside (0, 1)
+  if (!(p > 0.0 && p < 1.0)) return false;
+  double t = floor(p * 4294967296.0 + 0.5);
+  t = t < 1.0 ? 1.0 : (t > 4294967295.0 ? 4294967295.0 : t);
+  d->hseed = lowbias32(seed);
+  d->T = (uint32_t)t;
+  d->c_keep = (float)(p / (1.0 - p));
+  d->inv = (float)(1.0 / (1.0 - p));
+  return true;
+}
+__device__ inline uint32_t lora_drop_row(const LoraDrop& d, uint32_t i) { return lowbias32(d.hseed ^ i); }
+__device__ inline bool lora_drop_keep(const LoraDrop& d, uint32_t hrow, uint32_t k) { return lowbias32(hrow ^ k) >= d.T; }
+
 // hipFuncSetAttribute is per (function, DEVICE): remember it per device so that a process driving several GPUs
 // (or a model moved to another GPU) works, while the steady state stays one thread-local hipGetDevice per launch.
 // Runs on the first launch per device, i.e. during warm-up, outside any later graph capture.

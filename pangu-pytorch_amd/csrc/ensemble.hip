@@ -34,15 +34,7 @@
 
 namespace {
 
-__host__ __device__ inline uint32_t lowbias32(uint32_t x) {
-  x ^= x >> 16;
-  x *= 0x7feb352du;
-  x ^= x >> 15;
-  x *= 0x846ca68bu;
-  x ^= x >> 16;
-  return x;
-}
-
+// (lowbias32: common.h)
 __device__ inline float fade(float t) { return t * t * t * fmaf(t, fmaf(t, 6.0f, -15.0f), 10.0f); }
 
 constexpr int EP_ROWS = 4;          // rows per workgroup: every LDS table read serves all of them

@@ -28,13 +28,26 @@ constexpr size_t lora_lds_bytes(int K, int N, int RT) {
   return ((size_t)LR_ROWS * (K + N) + (size_t)LR_WAVES * 2 * RT * 256) * sizeof(float);
 }
 
-// RT = 16-column tiles of the rank (1: r <= 16, 2: r = 32)
-template <int RT>
+// The adapter-dropout policy (pangu_lora_wgrad_dropout_f32): the kernel's one trailing argument, absent in the plain pass
+struct LoraDropOut {
+  LoraDrop d;
+  float* V;      // (M, r): s * dy B, what the input-gradient correction reads (lora_dropout_f32.hip)
+  float s;
+};
+inline __device__ const LoraDropOut* drop_arg() { return nullptr; }
+inline __device__ const LoraDropOut* drop_arg(const LoraDropOut& o) { return &o; }
+
+// RT = 16-column tiles of the rank (1: r <= 16, 2: r = 32).  DropArgs: empty (the plain pass, the instantiation is what it was
+// before the policy existed) or one LoraDropOut: the staged x slab is then turned into drop(x) = keep * x / (1 - p) in LDS
+// before the two products that read it (U = drop(x) A^T and dA = V^T drop(x)), and V of every token is written out as well.
+template <int RT, typename... DropArgs>
 __global__ __launch_bounds__(LR_THREADS, 1) void lora_wgrad_f32_kernel(const float* __restrict__ dy, int lddy,
                                                                        const float* __restrict__ x, int ldx,
                                                                        const float* __restrict__ A, const float* __restrict__ B,
                                                                        float* __restrict__ ws, int M, int N, int K, int r,
-                                                                       int rows_per_wg) {
+                                                                       int rows_per_wg, DropArgs... drop_args) {
+  constexpr bool DROP = sizeof...(DropArgs) != 0;
+  const LoraDropOut* const drop = drop_arg(drop_args...);
   constexpr int MAXB = (LR_MAX_KN / 16 + LR_WAVES - 1) / LR_WAVES;     // column blocks per wave
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* xs = lds;                                             // [16][K] (swizzled, below)
@@ -100,6 +113,21 @@ __global__ __launch_bounds__(LR_THREADS, 1) void lora_wgrad_f32_kernel(const flo
     issue(st * LR_ROWS);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this wave's pieces have landed
     __syncthreads();                                       // ... and everybody's
+    if constexpr (DROP) {
+      // x -> drop(x) = keep * x / (1 - p), once, in the staged slab: the U and the dA product below both read it from there.
+      // 32 threads per token row; slot c of a row holds the column group c ^ (row & 15)
+      const int row = tid >> 5;
+      const uint32_t hrow = lora_drop_row(drop->d, (uint32_t)(m_begin + st * LR_ROWS + row));
+      for (int c = tid & 31; c < x4; c += 32) {
+        f32x4* q = reinterpret_cast<f32x4*>(&xs[row * K + 4 * c]);
+        f32x4 v = *q;
+        const uint32_t k = 4u * (uint32_t)(c ^ (row & 15));
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = lora_drop_keep(drop->d, hrow, k + j) ? v[j] * drop->d.inv : 0.f;
+        *q = v;
+      }
+      __syncthreads();
+    }
 
     // U = x A^T, V = dy B of these 16 tokens.  Within a block, lane quarter q and MFMA step j take column 16 b + 4 q + j on
     // BOTH operands (a permutation of the contraction order: each lane reads 4 consecutive values with one b128 load)
@@ -145,6 +173,13 @@ __global__ __launch_bounds__(LR_THREADS, 1) void lora_wgrad_f32_kernel(const flo
 #pragma unroll
       for (int w = 1; w < LR_WAVES; ++w) s += red[w * 2 * RT * 256 + e];
       red[e] = s;                                              // U = red[0 .. RT*256), V = red[RT*256 .. 2*RT*256)
+      if constexpr (DROP) {
+        if (e >= RT * 256) {                                   // V[token][rank] of this step's tokens, scaled
+          const int v = e - RT * 256, rt = v >> 8, row = (v >> 4) & 15, c = rt * 16 + (v & 15);
+          const int m = m_begin + st * LR_ROWS + row;
+          if (m < m_end && c < r) drop->V[(size_t)m * r + c] = drop->s * s;
+        }
+      }
     }
     __syncthreads();
 
@@ -226,11 +261,10 @@ __global__ __launch_bounds__(256) void lora_merge_f32_kernel(const float* __rest
 
 bool lora_rank_ok(int r) { return r == 4 || r == 8 || r == 16 || r == 32; }
 
-}  // namespace
-
-extern "C" int pangu_lora_wgrad_f32(pangu_stream_t stream, const float* dY, int lddy, const float* X, int ldx, const float* A,
-                                    const float* B, float* dA, float* dB, int M, int N, int K, int r, float scaling,
-                                    float* workspace, long long workspace_bytes) {
+// the launch behind both entries; drop: nullptr (the plain pass) or the dropout policy's argument
+int lora_wgrad_launch(pangu_stream_t stream, const float* dY, int lddy, const float* X, int ldx, const float* A, const float* B,
+                      float* dA, float* dB, int M, int N, int K, int r, float scaling, float* workspace, long long workspace_bytes,
+                      const LoraDropOut* drop) {
   if (!dY || !X || !A || !B || !dA || !dB || !workspace) return PANGU_E_NULL;
   if (M <= 0 || !lora_rank_ok(r) || K <= 0 || N <= 0 || (K & 63) || (N & 63) || K + N > LR_MAX_KN) return PANGU_E_SHAPE;
   if (ldx < K || lddy < N || (ldx & 3) || (lddy & 3)) return PANGU_E_SHAPE;
@@ -249,7 +283,15 @@ extern "C" int pangu_lora_wgrad_f32(pangu_stream_t stream, const float* dY, int 
   // 32-bit byte offsets of the slab descriptors
   if ((long long)(rows + LR_ROWS) * std::max(ldx, lddy) * (long long)sizeof(float) >= 0x7FFFFFFFll) return PANGU_E_RANGE;
   hipStream_t s = (hipStream_t)stream;
-  if (RT == 2) {
+  if (drop && RT == 2) {
+    PANGU_ENSURE_DYN_LDS((lora_wgrad_f32_kernel<2, LoraDropOut>), lds);
+    hipLaunchKernelGGL((lora_wgrad_f32_kernel<2, LoraDropOut>), dim3((unsigned)parts), dim3(LR_THREADS), lds, s, dY, lddy, X, ldx, A,
+                       B, workspace, M, N, K, r, rows, *drop);
+  } else if (drop) {
+    PANGU_ENSURE_DYN_LDS((lora_wgrad_f32_kernel<1, LoraDropOut>), lds);
+    hipLaunchKernelGGL((lora_wgrad_f32_kernel<1, LoraDropOut>), dim3((unsigned)parts), dim3(LR_THREADS), lds, s, dY, lddy, X, ldx, A,
+                       B, workspace, M, N, K, r, rows, *drop);
+  } else if (RT == 2) {
     PANGU_ENSURE_DYN_LDS(lora_wgrad_f32_kernel<2>, lds);
     hipLaunchKernelGGL(lora_wgrad_f32_kernel<2>, dim3((unsigned)parts), dim3(LR_THREADS), lds, s, dY, lddy, X, ldx, A, B,
                        workspace, M, N, K, r, rows);
@@ -263,6 +305,25 @@ extern "C" int pangu_lora_wgrad_f32(pangu_stream_t stream, const float* dY, int 
   hipLaunchKernelGGL(lora_reduce_f32_kernel, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, s, workspace, (int)parts, (int)per,
                      dA, dB, r * K, scaling);
   return pangu_launch_status();
+}
+
+}  // namespace
+
+extern "C" int pangu_lora_wgrad_f32(pangu_stream_t stream, const float* dY, int lddy, const float* X, int ldx, const float* A,
+                                    const float* B, float* dA, float* dB, int M, int N, int K, int r, float scaling,
+                                    float* workspace, long long workspace_bytes) {
+  return lora_wgrad_launch(stream, dY, lddy, X, ldx, A, B, dA, dB, M, N, K, r, scaling, workspace, workspace_bytes, nullptr);
+}
+
+extern "C" int pangu_lora_wgrad_dropout_f32(pangu_stream_t stream, const float* dY, int lddy, const float* X, int ldx, const float* A,
+                                            const float* B, float* dA, float* dB, float* V, int M, int N, int K, int r, float scaling,
+                                            double p, unsigned seed, float* workspace, long long workspace_bytes) {
+  if (!V) return PANGU_E_NULL;
+  LoraDropOut drop;
+  if (!lora_drop_make(p, seed, &drop.d)) return PANGU_E_ARG;
+  drop.V = V;
+  drop.s = scaling;
+  return lora_wgrad_launch(stream, dY, lddy, X, ldx, A, B, dA, dB, M, N, K, r, scaling, workspace, workspace_bytes, &drop);
 }
 
 extern "C" int pangu_lora_merge_f32(pangu_stream_t stream, const float* W, const float* A, const float* B, float* W_eff, int N,

@@ -71,7 +71,7 @@ def concat_halves(x):
 
 def mlp(m, x2d):
     """Mlp.forward on its own (reference layers.py:264-270; the block never comes through here): differentiable."""
-    if _train_path(m, x2d):
+    if _train_path(m, x2d) or _drops(m):
         return MlpFn.apply(x2d.contiguous(), _layers.eff_weight(m.linear1), m.linear1.bias, _layers.eff_weight(m.linear2),
                            m.linear2.bias, *_layers.lora_args(m.linear1, m.linear2))
     h = ops.linear(x2d, _layers.eff_weight(m.linear1), m.linear1.bias, act=ops.ACT_GELU)
@@ -154,11 +154,22 @@ def _block_rows_bf16(blk, sh, x, Z, H, W, roll, out=None):
 # ---- one sample, one layer, on 2-D rows (N, C): THE call site of each layer Function and of its inference composition.
 # sh: None for fp32, the model's fused_bf16.WeightShadow for bf16.  infer: nothing in the whole model asks for a gradient (`not
 # grad_path` of PanguModel.forward); the default is a layer called on its own.
+def _drops(layer):
+    """A layer in train() mode with an active LoRA adapter dropout: it takes its Function also without a graph (the inference
+    compositions have no place for the dropout corrections, and a train-mode output must not depend on grad mode)."""
+    return layer.training and _layers.dropout_active(layer)
+
+
 def _infer_arm(layer, sh, infer, *tensors):
     """Which arm a layer takes.  fp32: the inference composition iff the layer is frozen and no gradient arrives (_train_path
-    false), whatever `infer` says.  bf16: `infer` and nothing else -- on the model's autograd path a frozen bf16 layer runs its
-    Function too, and a fully frozen bf16 model run with grad mode on takes the inference kernels (grad mode alone cannot tell)."""
-    return infer if sh is not None else not _train_path(layer, *tensors)
+    false) and no adapter dropout is active (_drops), whatever `infer` says.  bf16: `infer` and nothing else -- on the model's
+    autograd path a frozen bf16 layer runs its Function too, and a fully frozen bf16 model run with grad mode on takes the inference
+    kernels (grad mode alone cannot tell)."""
+    if sh is not None:
+        if _drops(layer):
+            raise RuntimeError("LoRA adapter dropout in train() mode is fp32 only (no bf16 correction kernels): call eval() first")
+        return infer
+    return not (_train_path(layer, *tensors) or _drops(layer))
 
 
 def sample_block(blk, x, Z, H, W, roll, out=None, sh=None, infer=False):
@@ -264,7 +275,7 @@ def forward_model(model, inp, inp_surface, statistics, maps, const_h, levels_rev
 def earth_block(blk, x, Z, H, W, roll, out=None):
     """x (B,N,C) -> (B,N,C), into the (B,N,C) `out` if given (a half of the inference concat buffer)."""
     B, N, C = x.shape
-    if _train_path(blk, x):
+    if _train_path(blk, x) or _drops(blk):
         y = _stack([sample_block(blk, xb, Z, H, W, roll) for xb in _samples(x)], B)
         return y if out is None else out.copy_(y)
     y = _block_rows(blk, _tok2d(x), B, Z, H, W, roll, None if out is None else _tok2d(out))
@@ -285,13 +296,13 @@ def patch_embed(m, inp, inp_surface, statistics, maps, const_h, levels_reversed=
 
 def down_sample(m, x, Z, H, W):
     B = x.shape[0]
-    rows = _samples(x) if _train_path(m, x) else [_tok2d(x[b:b + 1]) for b in range(B)]
+    rows = _samples(x) if _train_path(m, x) or _drops(m) else [_tok2d(x[b:b + 1]) for b in range(B)]
     return _stack([sample_down(m, xb, Z, H, W) for xb in rows], B)
 
 
 def up_sample(m, x, Z, H2, W2, H):
     B = x.shape[0]
-    if _train_path(m, x):
+    if _train_path(m, x) or _drops(m):
         return _stack([sample_up(m, xb, Z, H2, W2, H) for xb in _samples(x)], B)
     return _up_rows(m, _tok2d(x), B, Z, H2, W2, H).view(B, Z * H * 2 * W2, -1)
 

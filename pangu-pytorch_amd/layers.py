@@ -53,6 +53,40 @@ class DropPath(nn.Module):
         return f"drop_prob={self.drop_prob:.3f}"
 
 
+def _lowbias32(x):
+    """csrc/common.h lowbias32 on an int64 tensor holding uint32 values."""
+    m = 0xFFFFFFFF
+    x = x ^ (x >> 16)
+    x = (x * 0x7feb352d) & m
+    x = x ^ (x >> 15)
+    x = (x * 0x846ca68b) & m
+    return x ^ (x >> 16)
+
+
+def lora_dropout_threshold(p):
+    """T of the keep mask: clamp(floor(p * 2^32 + 0.5), 1, 2^32 - 1), computed from the double `p` (as csrc/common.h does)."""
+    return min(max(int(math.floor(float(p) * 4294967296.0 + 0.5)), 1), 0xFFFFFFFF)
+
+
+def lora_dropout_keep(seed, M, K, p, device=None):
+    """The keep mask of the adapter dropout on an (M, K) adapter input, a pure function of (seed, row, column): the host
+    restatement of what the kernels recompute (csrc/common.h, LoraDrop) -> bool (M, K), True where the entry is kept:
+        keep(seed, i, k) = lowbias32(lowbias32(lowbias32(seed) ^ i) ^ k) >= T,  T = lora_dropout_threshold(p)
+    Integer torch ops (usable on the CPU); seed is a uint32."""
+    seed = int(seed)
+    if not 0 <= seed <= 0xFFFFFFFF:
+        raise ValueError(f"lora_dropout_keep: seed {seed} is not a uint32")
+    hs = _lowbias32(torch.tensor(seed, dtype=torch.int64, device=device))
+    hrow = _lowbias32(hs ^ torch.arange(M, dtype=torch.int64, device=device))
+    return _lowbias32(hrow[:, None] ^ torch.arange(K, dtype=torch.int64, device=device)[None, :]) >= lora_dropout_threshold(p)
+
+
+def draw_lora_dropout_seed():
+    """One uint32 from torch's default CPU generator (the generator DropPath.sample_scale draws from): `torch.manual_seed`
+    reproduces the masks, and the checkpointed training steps, which restore the host RNG state, recompute with the same ones."""
+    return int(torch.randint(0, 1 << 32, (), dtype=torch.int64))
+
+
 class LoraLinear(nn.Linear):
     """An nn.Linear with a LoRA adapter (peft's `lora.Linear`, reference finetune/lora_tune.py:124-135): y = x W_eff^T + b with
     W_eff = W + scaling * lora_B @ lora_A, scaling = alpha / r.  `weight` / `bias` are the frozen base parameters under their own
@@ -62,15 +96,23 @@ class LoraLinear(nn.Linear):
     The kernels never see A and B in the forward: they run on W_eff (`effective_weight()`), a derived tensor made by
     `pangu_lora_merge_f32` and re-made only when the stamp (ops.param_stamp) of W, A or B changes -- like the bf16 weight
     shadows, it is never pickled and is dropped by `.to()` / `invalidate_shadows`.  The adapter gradients come from
-    `pangu_lora_wgrad_f32` (`pangu_lora_wgrad_bf16` on the bf16 training path) in the backward of the layer functions (autograd.py)."""
+    `pangu_lora_wgrad_f32` (`pangu_lora_wgrad_bf16` on the bf16 training path) in the backward of the layer functions (autograd.py).
 
-    def __init__(self, in_features, out_features, bias=True, r=16, alpha=16, device=None, dtype=None):
+    `lora_dropout` (peft's name; default 0): in train() mode the adapter path reads drop(x) = keep * x / (1 - p) instead of x,
+    y = x W^T + b + s drop(x) A^T B^T.  The mask is lora_dropout_keep of a seed drawn per call (`last_dropout_seed` keeps the
+    latest); the layer functions apply it as additive corrections around the W_eff launches (csrc/lora_dropout_f32.hip), fp32 only."""
+
+    def __init__(self, in_features, out_features, bias=True, r=16, alpha=16, device=None, dtype=None, lora_dropout=0.0):
         super().__init__(in_features, out_features, bias=bias, device=device, dtype=dtype)
-        self._init_lora(r, alpha)
+        self._init_lora(r, alpha, lora_dropout)
 
-    def _init_lora(self, r, alpha):
+    def _init_lora(self, r, alpha, lora_dropout=0.0):
         self.r, self.lora_alpha = int(r), alpha
         self.scaling = alpha / r
+        self.lora_dropout = float(lora_dropout)
+        if not 0.0 <= self.lora_dropout < 1.0:
+            raise ValueError(f"LoraLinear: lora_dropout={lora_dropout} is not in [0, 1)")
+        self.last_dropout_seed = None
         w = self.weight
         self.lora_A = nn.Parameter(torch.empty((self.r, self.in_features), device=w.device, dtype=w.dtype))
         self.lora_B = nn.Parameter(torch.zeros((self.out_features, self.r), device=w.device, dtype=w.dtype))
@@ -79,14 +121,14 @@ class LoraLinear(nn.Linear):
         self._w_eff_stamp = None
 
     @classmethod
-    def from_linear(cls, lin, r, alpha):
+    def from_linear(cls, lin, r, alpha, lora_dropout=0.0):
         """Adapt `lin` in place of it: the new module holds the SAME weight / bias Parameter objects."""
         m = cls.__new__(cls)
         nn.Module.__init__(m)
         m.in_features, m.out_features = lin.in_features, lin.out_features
         m.weight = lin.weight
         m.bias = lin.bias
-        m._init_lora(r, alpha)
+        m._init_lora(r, alpha, lora_dropout)
         return m
 
     def to_linear(self, weight=None):
@@ -124,10 +166,24 @@ class LoraLinear(nn.Linear):
         self._w_eff = None
         self._w_eff_stamp = None
 
+    def dropout_active(self):
+        return self.training and getattr(self, "lora_dropout", 0.0) > 0.0
+
+    def next_dropout_seed(self):
+        """Draw (and remember) the seed of this projection's next mask."""
+        self.last_dropout_seed = draw_lora_dropout_seed()
+        return self.last_dropout_seed
+
     def forward(self, x):
-        """The module on its own, plain torch (peft's arithmetic; usable on the CPU)."""
+        """The module on its own, plain torch (peft's arithmetic; usable on the CPU).  In train() mode with lora_dropout > 0 the
+        adapter path reads drop(x), with the kernels' mask on the rows of x flattened to (M, in_features)."""
+        xa = x
+        if self.dropout_active():
+            p = self.lora_dropout
+            keep = lora_dropout_keep(self.next_dropout_seed(), x.numel() // x.shape[-1], x.shape[-1], p, device=x.device)
+            xa = x * (keep.reshape(x.shape).to(x.dtype) / (1.0 - p))
         return nn.functional.linear(x, self.weight, self.bias) + self.scaling * nn.functional.linear(
-            nn.functional.linear(x, self.lora_A), self.lora_B)
+            nn.functional.linear(xa, self.lora_A), self.lora_B)
 
     def _apply(self, fn, *args, **kwargs):
         self.drop_derived()
@@ -140,7 +196,7 @@ class LoraLinear(nn.Linear):
         return state
 
     def extra_repr(self):
-        return super().extra_repr() + f", r={self.r}, alpha={self.lora_alpha}"
+        return super().extra_repr() + f", r={self.r}, alpha={self.lora_alpha}, lora_dropout={getattr(self, 'lora_dropout', 0.0)}"
 
 
 def eff_weight(lin):
@@ -151,10 +207,25 @@ def eff_weight(lin):
     return lin.weight
 
 
+def _lora_scaling(l):
+    """A projection's entry in `lora`: its scaling, or (scaling, p, seed) while its adapter dropout is active (train() mode and
+    lora_dropout > 0) -- the seed of this call's mask is drawn here."""
+    if l.dropout_active():
+        return (l.scaling, l.lora_dropout, l.next_dropout_seed())
+    return l.scaling
+
+
+def dropout_active(*modules):
+    """Does any LoraLinear under `modules` apply adapter dropout in its next forward?"""
+    return any(type(l) is LoraLinear and l.dropout_active() for m in modules for l in m.modules())
+
+
 def lora_args(*lins):
     """The trailing `lora, *ab` arguments of a layer Function (autograd.py) for its projections `lins`: the tuple of scalings, then
-    lora_A, lora_B of each projection (None in every place of a plain nn.Linear); nothing when no projection is adapted."""
-    ad = [(l.scaling, l.lora_A, l.lora_B) if type(l) is LoraLinear else (None, None, None) for l in lins]
+    lora_A, lora_B of each projection (None in every place of a plain nn.Linear); nothing when no projection is adapted.  A
+    projection whose adapter dropout is active carries (scaling, p, seed) in place of its scaling; its seed is one draw from
+    torch's default CPU generator per call, in the order of `lins`."""
+    ad = [(_lora_scaling(l), l.lora_A, l.lora_B) if type(l) is LoraLinear else (None, None, None) for l in lins]
     if all(s is None for s, _, _ in ad):
         return ()
     return (tuple(s for s, _, _ in ad),) + tuple(t for _, A, B in ad for t in (A, B))
@@ -264,7 +335,8 @@ class EarthAttention3D(nn.Module):
         xw = x.to(torch.float32).contiguous().view(-1, self.dim)
         m = None if mask is None else mask.detach().to(device=x.device, dtype=torch.float32).contiguous()
         with torch.cuda.device(x.device):
-            if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            if (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))) or (
+                    self.training and dropout_active(self)):
                 y = AttentionWindowsFn.apply(xw, eff_weight(self.linear1), self.linear1.bias, eff_weight(self.linear2),
                                              self.linear2.bias, self.earth_specific_bias, m,
                                              (n_lon, self.type_of_windows, self.head_number), *lora_args(self.linear1, self.linear2))

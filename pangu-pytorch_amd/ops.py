@@ -456,6 +456,75 @@ def lora_wgrad(dy, x, A, B, scaling):
     return dA, dB
 
 
+def _lora_shapes(what, x, y, A, B):
+    """(M, N, K, r) of an adapted projection's row-strided x (M, K), y / dy (M, N) and its adapters A (r, K), B (N, r)."""
+    M, N = y.shape
+    K = x.shape[1]
+    r = A.shape[0]
+    if x.shape[0] != M or tuple(A.shape) != (r, K) or tuple(B.shape) != (N, r):
+        raise RuntimeError(f"{what}: y {tuple(y.shape)} x {tuple(x.shape)} A {tuple(A.shape)} B {tuple(B.shape)}")
+    return M, N, K, r
+
+
+def lora_dropout_fwd(x, y, A, B, scaling, p, seed, act=ACT_NONE, h=None):
+    """The forward correction of an adapted projection with active adapter dropout (peft's lora_dropout), IN PLACE on the
+    projection's result y (M, N) = x W_eff^T + b:  y += s ((c * x) A^T) B^T, c = keep / (1 - p) - 1 with the mask
+    layers.lora_dropout_keep(seed, M, K, p).  act=ACT_GELU: h (M, N) = gelu(y) of the corrected y is written too (the MLP's first
+    projection).  x, y, h row-strided.  -> y (and h)."""
+    lib = _lib.load()
+    xp, ldx = _rows(x, "lora_dropout_fwd.x")
+    yp, ldy = _rows(y, "lora_dropout_fwd.y")
+    M, N, K, r = _lora_shapes("lora_dropout_fwd", x, y, A, B)
+    if act not in (ACT_NONE, ACT_GELU):
+        raise RuntimeError(f"lora_dropout_fwd: act {act} (ACT_NONE or ACT_GELU)")
+    hp, ldh = (None, 0)
+    if act == ACT_GELU:
+        if h is None:
+            h = torch.empty((M, N), dtype=torch.float32, device=y.device)
+        if tuple(h.shape) != (M, N):
+            raise RuntimeError(f"lora_dropout_fwd: h {tuple(h.shape)} != {(M, N)}")
+        hp, ldh = _rows(h, "lora_dropout_fwd.h")
+    with _timed("lora_dropout_fwd", 4.0 * M * (K + 2 * N + (N if act == ACT_GELU else 0))):      # bytes: streaming, HBM-bound
+        _lib.check(lib.pangu_lora_dropout_fwd_f32(_stream(y), xp, ldx, yp, ldy, _chk(A, "lora_A"), _chk(B, "lora_B"), M, N, K, r,
+                                                  float(scaling), float(p), int(seed), act, hp, ldh), "lora_dropout_fwd")
+    return (y, h) if act == ACT_GELU else y
+
+
+def lora_wgrad_dropout(dy, x, A, B, scaling, p, seed):
+    """lora_wgrad with drop(x) = keep * x / (1 - p) in place of x (the mask recomputed from the seed, nothing stored), and V =
+    s dy B (M, r), which lora_dropout_dx reads -> (dA, dB, V)."""
+    lib = _lib.load()
+    dp, lddy = _rows(dy, "lora_wgrad_dropout.dy")
+    xp, ldx = _rows(x, "lora_wgrad_dropout.x")
+    M, N, K, r = _lora_shapes("lora_wgrad_dropout", x, dy, A, B)
+    ws = wgrad_workspace(dy.device)
+    dA = torch.empty((r, K), dtype=torch.float32, device=dy.device)
+    dB = torch.empty((N, r), dtype=torch.float32, device=dy.device)
+    V = torch.empty((M, r), dtype=torch.float32, device=dy.device)
+    with _timed("lora_wgrad_dropout", 4.0 * M * (K + N + r)):
+        _lib.check(lib.pangu_lora_wgrad_dropout_f32(_stream(dy), dp, lddy, xp, ldx, _chk(A, "lora_A"), _chk(B, "lora_B"),
+                                                    dA.data_ptr(), dB.data_ptr(), V.data_ptr(), M, N, K, r, float(scaling), float(p),
+                                                    int(seed), ws.data_ptr(), _WGRAD_WS_BYTES), "lora_wgrad_dropout")
+    return dA, dB, V
+
+
+def lora_dropout_dx(dx, V, A, p, seed, pre=None):
+    """The input-gradient correction of the same projection, IN PLACE on the result dx (M, K) of its dx GEMM:
+    dx += c * (V A), V (M, r) from lora_wgrad_dropout.  pre (M, K): the projection's input is gelu(pre) and dx is already the
+    gradient of pre (ACT_GELU_BWD epilogue); the correction then carries gelu'(pre) as well.  -> dx."""
+    lib = _lib.load()
+    xp, lddx = _rows(dx, "lora_dropout_dx.dx")
+    M, K = dx.shape
+    r = A.shape[0]
+    if tuple(V.shape) != (M, r) or tuple(A.shape) != (r, K) or (pre is not None and tuple(pre.shape) != (M, K)):
+        raise RuntimeError(f"lora_dropout_dx: dx {tuple(dx.shape)} V {tuple(V.shape)} A {tuple(A.shape)}")
+    pp, ldp = _rows(pre, "lora_dropout_dx.pre") if pre is not None else (None, 0)
+    with _timed("lora_dropout_dx", 4.0 * M * (2 * K + r + (K if pre is not None else 0))):
+        _lib.check(lib.pangu_lora_dropout_dx_f32(_stream(dx), xp, lddx, _chk(V, "lora_V"), _chk(A, "lora_A"), M, K, r, float(p),
+                                                 int(seed), pp, ldp), "lora_dropout_dx")
+    return dx
+
+
 def lora_merge(W, A, B, scaling, out=None):
     """W_eff = W + s * (B @ A) in fp32 (rank sum in a fixed order) -> a new (N, K) tensor, or into `out`."""
     lib = _lib.load()

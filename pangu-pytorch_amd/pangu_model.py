@@ -168,21 +168,29 @@ class PanguModel(nn.Module):
     # modules_to_save=["_output_layer.conv", "_output_layer.conv_surface"])) ------------------------------------------------
 
     def enable_lora(self, r=16, alpha=16, target_modules=None, train_also=("_output_layer.conv", "_output_layer.conv_surface"),
-                    dropout=0.0, bf16_training=False):
+                    dropout=0.0, bf16_training=False, lora_dropout=0.0):
         """Replace each targeted nn.Linear IN PLACE by a layers.LoraLinear holding the same base Parameters (default: all 67, as
         the reference does), and freeze everything except the adapters and the modules named in `train_also` (trained in full,
         peft's `modules_to_save`).  target_modules: None, or names / name suffixes ("linear1", "attention.linear2", ...) as peft
         matches them.  bf16_training: allow the adapted model to TRAIN in bf16 mixed precision (`set_compute_dtype(torch.bfloat16)`
         or bf16 autocast): fp32 master adapters and adapter gradients, bf16 images of W_eff, adapter gradients from
-        `pangu_lora_wgrad_bf16`; without it a bf16 training forward of an adapted model is refused.  Returns the list of adapted
-        module names."""
+        `pangu_lora_wgrad_bf16`; without it a bf16 training forward of an adapted model is refused.  lora_dropout (peft's name, 0 <= p
+        < 1): dropout on the adapter input in train() mode, fp32 training only (layers.LoraLinear; each adapted projection draws one
+        mask seed per sample and forward from torch's default CPU generator, after the block's DropPath draws -- so with dropout
+        active DropPath's draws shift against a run without it; `torch.manual_seed` reproduces a step).  eval() and bf16 inference
+        of such a model are unaffected.  Returns the list of adapted module names."""
         from .layers import LoraLinear
         from .ops import LORA_RANKS
         if r not in LORA_RANKS:
             raise ValueError(f"enable_lora: r={r} is not supported; the adapter-gradient kernel covers r in {LORA_RANKS}")
         if dropout > 0.0:
-            raise ValueError("enable_lora: lora_dropout > 0 is not implemented: dropout on the adapter input cannot be folded into "
-                             "W_eff = W + s*B@A, which the forward kernels run on (it needs a rank-r epilogue on the forward GEMMs)")
+            raise ValueError("enable_lora: the keyword for adapter dropout is peft's own, lora_dropout= (dropout= is not accepted)")
+        lora_dropout = float(lora_dropout)
+        if not 0.0 <= lora_dropout < 1.0:
+            raise ValueError(f"enable_lora: lora_dropout={lora_dropout} is not in [0, 1)")
+        if lora_dropout > 0.0 and bf16_training:
+            raise ValueError("enable_lora: lora_dropout > 0 with bf16_training=True is not implemented (the dropout corrections are "
+                             "fp32 kernels; bf16 is a follow-up, as it was for the adapters): train in fp32, or with lora_dropout=0")
         targets = None if target_modules is None else [target_modules] if isinstance(target_modules, str) else list(target_modules)
 
         def hit(name):
@@ -193,7 +201,7 @@ class PanguModel(nn.Module):
             for cname, child in list(mod.named_children()):
                 full = f"{name}.{cname}" if name else cname
                 if type(child) is nn.Linear and hit(full):
-                    setattr(mod, cname, LoraLinear.from_linear(child, r, alpha))
+                    setattr(mod, cname, LoraLinear.from_linear(child, r, alpha, lora_dropout))
                     adapted.append(full)
         if not adapted:
             raise ValueError(f"enable_lora: no nn.Linear matches target_modules={target_modules!r}")
@@ -238,6 +246,10 @@ class PanguModel(nn.Module):
         keep = tuple(t + "." for t in getattr(self, "_lora_train_also", ()))
         return OrderedDict((k, v) for k, v in self.state_dict().items()
                            if k.endswith(".lora_A") or k.endswith(".lora_B") or k.startswith(keep))
+
+    def has_lora_dropout(self):
+        from .layers import LoraLinear
+        return any(type(m) is LoraLinear and getattr(m, "lora_dropout", 0.0) > 0.0 for m in self.modules())
 
     def has_lora(self):
         from .layers import LoraLinear
@@ -303,6 +315,9 @@ class PanguModel(nn.Module):
                                "MLP / QKV kernels do not keep the operands the adapter gradients need); train in fp32, or "
                                "run bf16 inference under torch.no_grad(); or opt in to bf16 adapter training with "
                                "enable_lora(..., bf16_training=True)")
+        if want_bf16 and self.training and self.has_lora_dropout():
+            raise RuntimeError("PanguModel: LoRA adapter dropout (lora_dropout > 0) in train() mode is fp32 only; call eval() for bf16 "
+                               "inference, or train in fp32")
         if grad_path and not self.training and getattr(self, "eval_grad_mode", "save") == "recompute":
             return _EvalRecomputeFn.apply(self, (statistics, maps, const_h, want_bf16, rev), input, input_surface, *self.parameters())
         return self._forward_dispatch(input, input_surface, statistics, maps, const_h, want_bf16, grad_path, rev)

@@ -12,7 +12,13 @@ Prints one JSON line per section.
 --dtype bf16: `ops_bf16.lora_wgrad` per shape against its roof 2 M (K + N) / 6.29 TB/s and against `ops_bf16.linear_wgrad` of the
 same shape (the launch a LoRA step skips); then, alternating in one process, the bf16 full fine-tune step, the bf16 LoRA step
 (enable_lora(r, bf16_training=True)) and the fp32 LoRA step: ms/step, ratios, peak memory, and the host + GPU time of re-making
-the 67 W_eff images after an optimizer step.  One JSON line, also written to profiles/lora_bf16.json."""
+the 67 W_eff images after an optimizer step.  One JSON line, also written to profiles/lora_bf16.json.
+
+--lora-dropout P (fp32): the adapter-dropout kernels per shape at r = --rank -- `ops.lora_dropout_fwd` (with and without the GELU
+output) and `ops.lora_dropout_dx` against their HBM floors 4 M (K + 2N) (+ 4 M N) and 4 M (2K + r) bytes at 6.29 TB/s, and
+`ops.lora_wgrad_dropout` against `ops.lora_wgrad` on the same operands; then, alternating in one process, DropPath off, the fp32
+LoRA step with lora_dropout = P against the same model with 0: ms/step, ratio, peak memory.  One JSON line, also written to
+profiles/lora_dropout.json."""
 import argparse
 import copy
 import json
@@ -93,6 +99,81 @@ def kernels_bf16(P, r, reps=20):
                      "linear_wgrad_ms": round(wg, 4), "vs_linear_wgrad": round(ms / wg, 3)})
         del x, dy
     return rows
+
+
+def kernels_dropout(P, r, p, reps=20):
+    ops = P.ops
+    rows = []
+    for K, N, M in SHAPES:
+        g = torch.Generator(device="cuda").manual_seed(K + N)
+        x = torch.randn(M, K, device="cuda", generator=g)
+        dy = torch.randn(M, N, device="cuda", generator=g)
+        y, h, dx = torch.zeros(M, N, device="cuda"), torch.empty(M, N, device="cuda"), torch.zeros(M, K, device="cuda")
+        A = torch.randn(r, K, device="cuda", generator=g) * 0.1
+        B = torch.randn(N, r, device="cuda", generator=g) * 0.1
+        V = ops.lora_wgrad_dropout(dy, x, A, B, 1.0, p, 1)[2]
+        ms = {k: [] for k in ("fwd", "fwd_gelu", "dx", "wgrad_dropout", "wgrad")}
+        for _ in range(2):                       # alternately, twice each: all see the same clocks
+            ms["fwd"].append(_time(lambda: ops.lora_dropout_fwd(x, y, A, B, 1e-3, p, 1), reps))
+            ms["fwd_gelu"].append(_time(lambda: ops.lora_dropout_fwd(x, y, A, B, 1e-3, p, 1, act=ops.ACT_GELU, h=h), reps))
+            ms["dx"].append(_time(lambda: ops.lora_dropout_dx(dx, V, A, p, 1), reps))
+            ms["wgrad_dropout"].append(_time(lambda: ops.lora_wgrad_dropout(dy, x, A, B, 1.0, p, 1), reps))
+            ms["wgrad"].append(_time(lambda: ops.lora_wgrad(dy, x, A, B, 1.0), reps))
+        ms = {k: min(v) for k, v in ms.items()}
+        floor = {"fwd": 4.0 * M * (K + 2 * N), "fwd_gelu": 4.0 * M * (K + 3 * N), "dx": 4.0 * M * (2 * K + r)}
+        row = {"K": K, "N": N, "M": M, "r": r, "p": p}
+        for k, byt in floor.items():
+            fl = byt / HBM * 1e3
+            row.update({k + "_ms": round(ms[k], 4), k + "_floor_ms": round(fl, 4), k + "_x_floor": round(ms[k] / fl, 3)})
+        row.update({"wgrad_dropout_ms": round(ms["wgrad_dropout"], 4), "wgrad_ms": round(ms["wgrad"], 4),
+                    "wgrad_dropout_vs_wgrad": round(ms["wgrad_dropout"] / ms["wgrad"], 3)})
+        rows.append(row)
+        del x, dy, y, h, dx, V
+    return rows
+
+
+def train_compare_dropout(P, r, p, steps, warmup):
+    import cases
+    import synth
+    from pangu_pytorch_amd import train
+    base = P.PanguModel(device="cuda").cuda()
+    base.load_state_dict(synth.fill_state_dict(cases.model_param_shapes(), "cuda"))
+    for m in base.modules():
+        if isinstance(m, P.layers.DropPath):
+            m.drop_prob = 0.0
+    inp, inp_s, stats, maps, const_h = cases.model_inputs("cuda")
+    tgt, tgt_s = cases.model_targets("cuda")
+    batch = (inp, inp_s, tgt, tgt_s)
+    plain = copy.deepcopy(base).train()
+    plain.enable_lora(r=r, alpha=r)
+    drop = base.train()
+    drop.enable_lora(r=r, alpha=r, lora_dropout=p)
+    runs = {"lora": (plain, train.make_optimizer(plain)), "lora_dropout": (drop, train.make_optimizer(drop))}
+    times = {k: [] for k in runs}
+    peak = {}
+    torch.manual_seed(0)
+    for i in range(warmup + steps):
+        for k, (m, opt) in runs.items():            # alternating: both see the same clocks and thermal state
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            train.train_step(m, opt, batch, stats, maps, const_h)
+            b.record()
+            torch.cuda.synchronize()
+            if i >= warmup:
+                times[k].append(a.elapsed_time(b))
+            peak[k] = max(peak.get(k, 0), torch.cuda.max_memory_allocated())
+    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    # the new launches' own share of the last kind of step (device events around each launch)
+    P.ops.timing_start()
+    train.train_step(drop, runs["lora_dropout"][1], batch, stats, maps, const_h)
+    tags = ("lora_dropout_fwd", "lora_dropout_dx", "lora_wgrad_dropout")
+    tot = P.ops.timing_stop(tags[0], also=tags)[3]
+    return {"rank": r, "p": p, "steps": steps, **{k + "_ms": round(v, 2) for k, v in med.items()},
+            "ratio": round(med["lora_dropout"] / med["lora"], 3), "added_ms": round(med["lora_dropout"] - med["lora"], 2),
+            **{k + "_peak_GB": round(v / 1e9, 2) for k, v in peak.items()},
+            "launches_in_step": {k: {"ms": round(v[0], 2), "GB": round(v[1] / 1e9, 1), "launches": v[2]} for k, v in tot.items()}}
 
 
 def train_compare_bf16(P, r, steps, warmup):
@@ -208,9 +289,21 @@ def main():
     ap.add_argument("--rank", type=int, default=16)
     ap.add_argument("--skip-train", action="store_true")
     ap.add_argument("--dtype", choices=("fp32", "bf16"), default="fp32")
+    ap.add_argument("--lora-dropout", type=float, default=0.0, metavar="P")
     a = ap.parse_args()
     import pangu_pytorch_amd as P
     P._lib.load()
+    if a.lora_dropout > 0.0:
+        if a.dtype != "fp32":
+            ap.error("--lora-dropout is fp32 only")
+        res = {"box": torch.cuda.get_device_name(0), "lora_dropout_kernels": kernels_dropout(P, a.rank, a.lora_dropout)}
+        if not a.skip_train:
+            res["train_step"] = train_compare_dropout(P, a.rank, a.lora_dropout, a.steps, a.warmup)
+        line = json.dumps(res)
+        print(line, flush=True)
+        with open(os.path.join(ROOT, "profiles", "lora_dropout.json"), "w") as f:
+            f.write(line + "\n")
+        return
     if a.dtype == "bf16":
         res = {"lora_wgrad_bf16": kernels_bf16(P, a.rank)}
         if not a.skip_train:
