@@ -125,6 +125,33 @@ int pangu_lora_wgrad_dropout_f32(pangu_stream_t stream, const float* dY, int ldd
 int pangu_lora_dropout_dx_f32(pangu_stream_t stream, float* dX, int lddx, const float* V, const float* A, int M, int K, int r,
                               double p, unsigned seed, const float* pre, int ldpre);
 
+/* ---- LoRA adapter dropout on the bf16 training path.  The arithmetic and the mask are those of the fp32 entries above (the same
+ * keep(seed, i, k), recomputed in every kernel, never stored; p is a double so that host and device form the same T), on bf16
+ * activations.  Common contract: 0 < p < 1 (PANGU_E_ARG otherwise), r in {4, 8, 16, 32}, K and N multiples of 64 with K + N <= 1920;
+ * bf16 operands are row-strided with strides in elements that are multiples of 8 and at least the row; every pointer 16-B aligned.
+ * A [r][K] and B [N][r] are the fp32 master adapters, rounded to nearest-even bf16 by the kernel (as pangu_lora_wgrad_bf16 does);
+ * products are bf16 MFMA with fp32 accumulation.  No atomics, bit-identical from run to run; capturable.  Arguments are checked
+ * before any memory is touched, with the error codes of pangu_lora_wgrad_bf16: PANGU_E_NULL (a required pointer), PANGU_E_SHAPE (M,
+ * r, K, N, a stride), PANGU_E_ARG (alignment, p, act, a workspace that is too small). */
+
+/* In place on the bf16 Y[M][N] (row stride ldy): v = float(Y) + s * ((c * X) A^T) B^T in fp32, Y = bf16(v); X [M][K] bf16 (row
+ * stride ldx).  c * X and u = s (c * X) A^T are rounded to bf16 once each.  act = PANGU_ACT_GELU: H[M][N] (row stride ldh) =
+ * bf16(gelu(float(bf16(v)))), the exact-erf GELU of the ROUNDED value -- what pangu_linear_gelu_bwd_bf16 re-creates from the stored
+ * Y in the backward; PANGU_ACT_NONE: H is not touched (may be NULL). */
+int pangu_lora_dropout_fwd_bf16(pangu_stream_t stream, const void* X, int ldx, void* Y, int ldy, const float* A, const float* B,
+                                int M, int N, int K, int r, float scaling, double p, unsigned seed, int act, void* H, int ldh);
+/* pangu_lora_wgrad_bf16 with drop(X) in place of X: dA = s * (dY B)^T drop(X), dB = s * dY^T (drop(X) A^T), and one more output,
+ * V[M][r] = s * dY bf16(B) (dense fp32, from the fp32 partials before their bf16 rounding), which pangu_lora_dropout_dx_bf16
+ * reads.  The mask is applied exactly (dropped entries zeroed, 1 / (1 - p) applied in fp32 with s): dropout adds no rounding to
+ * dA / dB.  Workspace and error codes as pangu_lora_wgrad_bf16. */
+int pangu_lora_wgrad_dropout_bf16(pangu_stream_t stream, const void* dY, int lddy, const void* X, int ldx, const float* A,
+                                  const float* B, float* dA, float* dB, float* V, int M, int N, int K, int r, float scaling, double p,
+                                  unsigned seed, float* workspace, long long workspace_bytes);
+/* In place on the bf16 dX[M][K] (row stride lddx): dX = bf16(float(dX) + c * (V A) [* gelu'(float(pre))]), V [M][r] fp32 from the
+ * entry above (rounded to bf16 once).  pre: optional bf16 [M][K] (row stride ldpre), as in pangu_lora_dropout_dx_f32. */
+int pangu_lora_dropout_dx_bf16(pangu_stream_t stream, void* dX, int lddx, const float* V, const float* A, int M, int K, int r,
+                               double p, unsigned seed, const void* pre, int ldpre);
+
 /* ---- Earth-specific window attention -------------------------------------------------------------- */
 
 /* Fused roll + window partition + (q*scale)k^T + earth_specific_bias + shift mask + softmax + .v +

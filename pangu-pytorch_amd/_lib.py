@@ -34,6 +34,10 @@ SIGNATURES = {
     "pangu_lora_wgrad_dropout_f32": [_P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _c.c_double, _c.c_uint, _P,
                                      _c.c_longlong],
     "pangu_lora_dropout_dx_f32": [_P, _P, _I, _P, _P, _I, _I, _I, _c.c_double, _c.c_uint, _P, _I],
+    "pangu_lora_dropout_fwd_bf16": [_P, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _F, _c.c_double, _c.c_uint, _I, _P, _I],
+    "pangu_lora_wgrad_dropout_bf16": [_P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _c.c_double, _c.c_uint, _P,
+                                      _c.c_longlong],
+    "pangu_lora_dropout_dx_bf16": [_P, _P, _I, _P, _P, _I, _I, _I, _c.c_double, _c.c_uint, _P, _I],
     "pangu_window_attn_bwd": [_P] * 10 + [_I] * 6,
     "pangu_ln_residual_bwd": [_P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _F],
     "pangu_downsample_ln_bwd": [_P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P],

@@ -62,9 +62,7 @@ def _dropout_fwd(pr, lora, ab, i, x, y, act=ops.ACT_NONE, h=None):
     e = lora[i] if lora is not None else None
     if type(e) is not tuple:
         return False
-    if pr is not _F32:
-        raise RuntimeError("LoRA adapter dropout in train() mode is fp32 only (no bf16 correction kernels)")
-    ops.lora_dropout_fwd(x, y, ab[2 * i], ab[2 * i + 1], *e, act=act, h=h)
+    pr.k.lora_dropout_fwd(x, y, ab[2 * i], ab[2 * i + 1], *e, act=act, h=h)
     return True
 
 
@@ -72,7 +70,7 @@ def _dropout_dx(ctx, ad, dx, pre=None):
     """After the input-gradient GEMM of the same projection: dx += c * (V A) in place on that GEMM's result `dx` (never the
     incoming gradient), V kept by _wgrad.  pre: see ops.lora_dropout_dx (the projection behind a GELU) -> dx."""
     if ad is not None and type(ad[0]) is tuple:
-        ops.lora_dropout_dx(dx, ctx.lora_V.pop(ad[3]), ad[1], ad[0][1], ad[0][2], pre=pre)
+        ctx.pr.k.lora_dropout_dx(dx, ctx.lora_V.pop(ad[3]), ad[1], ad[0][1], ad[0][2], pre=pre)
     return dx
 
 
@@ -90,7 +88,7 @@ def _wgrad(ctx, dy, x, w, b=None, ad=None, db_into=None, shape=None):
         if shape is not None:
             dw = dw.reshape(shape)
     if ad is not None and type(ad[0]) is tuple:
-        da, dbb, V = ops.lora_wgrad_dropout(dy, x, ad[1], ad[2], *ad[0])
+        da, dbb, V = ctx.pr.k.lora_wgrad_dropout(dy, x, ad[1], ad[2], *ad[0])
         if getattr(ctx, "lora_V", None) is None:
             ctx.lora_V = {}
         ctx.lora_V[ad[3]] = V
@@ -145,10 +143,13 @@ class EarthBlockFn(torch.autograd.Function):
         # (Recomputing the MLP-up GEMM in the backward instead of saving `pre` -- the reference's answer to activation memory,
         # layers.py:115-119 -- measured +2.7 ms per step and was removed in round 4; so were the QKV-inside-attention training
         # forward, +0.3 ms, and weight gradients on a second stream, +0.5 ms.  DESIGN.md keeps the numbers.)
+        # Active adapter dropout on linear.linear1 / linear.linear2: the one launch keeps h on chip, where it cannot be corrected, so
+        # the forward takes the three launches with their corrections -- but where mode 1 would have applied it still saves
+        # (x1, pre, m) only and the backward stays mode 1 (linear_gelu_bwd re-creates the h that the correction wrote: gelu of the
+        # stored bf16 pre): peak memory does not grow by the hidden tensor.
         ctx.mlp_mode = mode = 1 if (sh is not None and x.shape[1] in (192, 384) and x1.is_contiguous()) else 0
-        if sh is not None and lora is not None and any(type(e) is tuple for e in lora):
-            raise RuntimeError("LoRA adapter dropout in train() mode is fp32 only (no bf16 correction kernels)")
-        if s2 != 0.0 and mode:
+        mlp_drop = lora is not None and (type(lora[0]) is tuple or type(lora[1]) is tuple)
+        if s2 != 0.0 and mode and not mlp_drop:
             x2, pre, m = ob.mlp_ln_residual_train(x1, sh.get_mlp(m1w, m2w), m1b, m2b, n2w, n2b, branch_scale=s2, out=out)
             saved += [x1, pre, m]
         elif s2 != 0.0:
@@ -161,7 +162,7 @@ class EarthBlockFn(torch.autograd.Function):
             m = K.linear(h, pr.w(m2w), m2b)
             _dropout_fwd(pr, lora, ab, 1, h, m)
             x2 = K.ln_residual(m, x1, n2w, n2b, out=out, branch_scale=s2)
-            saved += [x1, pre, h, m]
+            saved += [x1, pre, m] if mode else [x1, pre, h, m]
         elif out is not None:
             if x1 is not out:
                 out.copy_(x1)                     # both branches dropped: the block is the identity
@@ -200,11 +201,13 @@ class EarthBlockFn(torch.autograd.Function):
                 g["m2w"], g["m2b"], g["m2A"], g["m2B"] = _wgrad(ctx, dm, h, 7, 8, ad_m2)
             if ctx.mlp_mode == 1:          # h = GELU(pre) comes out of the data-gradient GEMM's epilogue (never stored by the forward)
                 dpre, h = ob.linear_gelu_bwd(dm, pr.wt(m2w), pre,
-                                             want_h=need["m2w"] or need["m2b"] or need.get("m2A", False) or need.get("m2B", False))
+                                             want_h=need["m2w"] or need["m2b"] or need.get("m2A", False) or need.get("m2B", False)
+                                             or (ad_m2 is not None and type(ad_m2[0]) is tuple))
             else:
-                dpre = _dropout_dx(ctx, ad_m2, K.linear(dm, pr.wt(m2w), None, act=ops.ACT_GELU_BWD, aux=pre), pre=pre)
+                dpre = K.linear(dm, pr.wt(m2w), None, act=ops.ACT_GELU_BWD, aux=pre)
             if pr is not _F32:
                 g["m2w"], g["m2b"], g["m2A"], g["m2B"] = _wgrad(ctx, dm, h, 7, 8, ad_m2)
+            _dropout_dx(ctx, ad_m2, dpre, pre=pre)          # (after _wgrad, which leaves the V it reads)
             del dm, h
             g["m1w"], g["m1b"], g["m1A"], g["m1B"] = _wgrad(ctx, dpre, x1, 5, 6, ad_m1)
             if dout.is_contiguous():      # residual gradient added in the GEMM epilogue (no extra pass over N x C)

@@ -45,12 +45,28 @@ __device__ inline s16x4 bf16x4_of(float a, float b, float c, float d) {
   return __builtin_bit_cast(s16x4, u32x2{pack_bf16x2(a, b), pack_bf16x2(c, d)});
 }
 
-// RT = 16-column tiles of the rank (1: r <= 16, 2: r = 32); MAXB = column blocks per wave (8: K + N <= 1024, 15: <= 1920)
-template <int RT, int MAXB>
+// The adapter-dropout policy (pangu_lora_wgrad_dropout_bf16): the kernel's one trailing argument, absent in the plain pass
+struct LoraDropOut {
+  LoraDrop d;
+  float* V;      // (M, r) fp32: s * dy bf16(B), what the input-gradient correction reads (lora_dropout_bf16.hip)
+  float s;
+};
+inline __device__ const LoraDropOut* drop_arg() { return nullptr; }
+inline __device__ const LoraDropOut* drop_arg(const LoraDropOut& o) { return &o; }
+
+// RT = 16-column tiles of the rank (1: r <= 16, 2: r = 32); MAXB = column blocks per wave (8: K + N <= 1024, 15: <= 1920).
+// DropArgs: empty (the plain pass: the instantiation is what it was before the policy existed) or one LoraDropOut: the dropped
+// entries of the staged x slab are then zeroed in LDS, once per step, before the two products that read it (U = drop(x) A^T and
+// dA = V^T drop(x); the factor 1 / (1 - p) is left to the reduce launch, in fp32 with s: both gradients are linear in drop(x) and
+// the masking adds no rounding), and V of every token is written out from the reduced fp32 partials.
+template <int RT, int MAXB, typename... DropArgs>
 __global__ __launch_bounds__(LB_THREADS) void lora_wgrad_bf16_kernel(const u16* __restrict__ dy, int lddy, const u16* __restrict__ x,
                                                                      int ldx, const float* __restrict__ A,
                                                                      const float* __restrict__ B, float* __restrict__ ws, int M,
-                                                                     int N, int K, int r, int rows_per_wg) {
+                                                                     int N, int K, int r, int rows_per_wg,
+                                                                     DropArgs... drop_args) {
+  constexpr bool DROP = sizeof...(DropArgs) != 0;
+  const LoraDropOut* const drop = drop_arg(drop_args...);
   constexpr int NF = MAXB / 2 + 2;      // staged 16-B chunks per thread: ceil(2 K / 512) + ceil(2 N / 512) <= (K + N) / 256 + 2
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int LD = lb_row_bytes(K, N);
@@ -151,6 +167,23 @@ __global__ __launch_bounds__(LB_THREADS) void lora_wgrad_bf16_kernel(const u16* 
     const bool more = st + 1 < steps;
     if (more) fetch((st + 1) * LB_ROWS);
     const unsigned char* img = smem + (st & 1) * STAGE;
+    if constexpr (DROP) {
+      // x -> keep * x, once, in the staged slab: 32 threads per token row, 16-B pieces of 8 columns
+      const int row = tid >> 5;
+      const uint32_t hrow = lora_drop_row(drop->d, (uint32_t)(m_begin + st * LB_ROWS + row));
+      for (int c = tid & 31; c < (K >> 3); c += 32) {
+        u32x4* q = reinterpret_cast<u32x4*>(smem + (st & 1) * STAGE + row * LD + 16 * c);
+        u32x4 v = *q;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const unsigned lo = lora_drop_keep(drop->d, hrow, (uint32_t)(8 * c + 2 * j)) ? 0x0000FFFFu : 0u;
+          const unsigned hi = lora_drop_keep(drop->d, hrow, (uint32_t)(8 * c + 2 * j + 1)) ? 0xFFFF0000u : 0u;
+          v[j] &= lo | hi;
+        }
+        *q = v;
+      }
+      __syncthreads();
+    }
 
     // product 1: U = x A^T, V = dy B of these 16 tokens, this wave's columns (A operand: token l16, columns 16 b + 4 q ..)
     f32x4 pu[RT], pv[RT];
@@ -186,6 +219,12 @@ __global__ __launch_bounds__(LB_THREADS) void lora_wgrad_bf16_kernel(const u16* 
       for (int w = 1; w < LB_WAVES; ++w) s += red[w * 2 * RT * 256 + e];
       const int tile = e >> 8, tok = (e >> 4) & 15, c = e & 15;
       uvt[tile * 256 + c * 16 + tok] = (u16)(pack_bf16x2(s, 0.f) & 0xFFFFu);
+      if constexpr (DROP) {
+        if (tile >= RT) {                                      // V[token][rank] of this step's tokens, scaled, before its rounding
+          const int m = m_begin + st * LB_ROWS + tok, cr = (tile - RT) * 16 + c;
+          if (m < m_end && cr < r) drop->V[(size_t)m * r + cr] = drop->s * s;
+        }
+      }
     }
     __syncthreads();
 
@@ -258,19 +297,20 @@ __global__ __launch_bounds__(256) void lora_reduce_bf16_kernel(const float* __re
   else dB[e - rK] = s * acc;
 }
 
-template <int RT, int MAXB>
+// drop_args: none (the plain pass) or the dropout policy's argument
+template <int RT, int MAXB, typename... DropArgs>
 void launch_lora_wgrad_bf16(hipStream_t s, int parts, size_t lds, const u16* dY, int lddy, const u16* X, int ldx, const float* A,
-                            const float* B, float* ws, int M, int N, int K, int r, int rows) {
-  auto kern = lora_wgrad_bf16_kernel<RT, MAXB>;
+                            const float* B, float* ws, int M, int N, int K, int r, int rows, DropArgs... drop_args) {
+  auto kern = lora_wgrad_bf16_kernel<RT, MAXB, DropArgs...>;
   PANGU_ENSURE_DYN_LDS(kern, lds);
-  hipLaunchKernelGGL(kern, dim3((unsigned)parts), dim3(LB_THREADS), lds, s, dY, lddy, X, ldx, A, B, ws, M, N, K, r, rows);
+  hipLaunchKernelGGL(kern, dim3((unsigned)parts), dim3(LB_THREADS), lds, s, dY, lddy, X, ldx, A, B, ws, M, N, K, r, rows,
+                     drop_args...);
 }
 
-}  // namespace
-
-extern "C" int pangu_lora_wgrad_bf16(pangu_stream_t stream, const void* dY, int lddy, const void* X, int ldx, const float* A,
-                                     const float* B, float* dA, float* dB, int M, int N, int K, int r, float scaling,
-                                     float* workspace, long long workspace_bytes) {
+// the launches behind both entries; drop: nullptr (the plain pass) or the dropout policy's argument
+int lora_wgrad_bf16_launch(pangu_stream_t stream, const void* dY, int lddy, const void* X, int ldx, const float* A, const float* B,
+                           float* dA, float* dB, int M, int N, int K, int r, float scaling, float* workspace,
+                           long long workspace_bytes, const LoraDropOut* drop) {
   if (!dY || !X || !A || !B || !dA || !dB || !workspace) return PANGU_E_NULL;
   if (M <= 0 || !(r == 4 || r == 8 || r == 16 || r == 32) || K <= 0 || N <= 0 || (K & 15) || (N & 15) || K + N > LB_MAX_KN)
     return PANGU_E_SHAPE;
@@ -293,13 +333,39 @@ extern "C" int pangu_lora_wgrad_bf16(pangu_stream_t stream, const void* dY, int 
   hipStream_t s = (hipStream_t)stream;
   const u16* d = (const u16*)dY;
   const u16* x = (const u16*)X;
-  if (RT == 2 && narrow) launch_lora_wgrad_bf16<2, 8>(s, (int)parts, lds, d, lddy, x, ldx, A, B, workspace, M, N, K, r, rows);
+  if (drop) {
+    if (RT == 2 && narrow) launch_lora_wgrad_bf16<2, 8>(s, (int)parts, lds, d, lddy, x, ldx, A, B, workspace, M, N, K, r, rows, *drop);
+    else if (RT == 2) launch_lora_wgrad_bf16<2, 15>(s, (int)parts, lds, d, lddy, x, ldx, A, B, workspace, M, N, K, r, rows, *drop);
+    else if (narrow) launch_lora_wgrad_bf16<1, 8>(s, (int)parts, lds, d, lddy, x, ldx, A, B, workspace, M, N, K, r, rows, *drop);
+    else launch_lora_wgrad_bf16<1, 15>(s, (int)parts, lds, d, lddy, x, ldx, A, B, workspace, M, N, K, r, rows, *drop);
+  } else if (RT == 2 && narrow) launch_lora_wgrad_bf16<2, 8>(s, (int)parts, lds, d, lddy, x, ldx, A, B, workspace, M, N, K, r, rows);
   else if (RT == 2) launch_lora_wgrad_bf16<2, 15>(s, (int)parts, lds, d, lddy, x, ldx, A, B, workspace, M, N, K, r, rows);
   else if (narrow) launch_lora_wgrad_bf16<1, 8>(s, (int)parts, lds, d, lddy, x, ldx, A, B, workspace, M, N, K, r, rows);
   else launch_lora_wgrad_bf16<1, 15>(s, (int)parts, lds, d, lddy, x, ldx, A, B, workspace, M, N, K, r, rows);
   const int rc = pangu_launch_status();
   if (rc != PANGU_OK) return rc;
   hipLaunchKernelGGL(lora_reduce_bf16_kernel, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, s, workspace, (int)parts, (int)per,
-                     dA, dB, r * K, scaling);
+                     dA, dB, r * K, drop ? scaling * drop->d.inv : scaling);
   return pangu_launch_status();
+}
+
+}  // namespace
+
+extern "C" int pangu_lora_wgrad_bf16(pangu_stream_t stream, const void* dY, int lddy, const void* X, int ldx, const float* A,
+                                     const float* B, float* dA, float* dB, int M, int N, int K, int r, float scaling,
+                                     float* workspace, long long workspace_bytes) {
+  return lora_wgrad_bf16_launch(stream, dY, lddy, X, ldx, A, B, dA, dB, M, N, K, r, scaling, workspace, workspace_bytes, nullptr);
+}
+
+extern "C" int pangu_lora_wgrad_dropout_bf16(pangu_stream_t stream, const void* dY, int lddy, const void* X, int ldx, const float* A,
+                                             const float* B, float* dA, float* dB, float* V, int M, int N, int K, int r,
+                                             float scaling, double p, unsigned seed, float* workspace, long long workspace_bytes) {
+  if (!V) return PANGU_E_NULL;
+  if ((K & 63) || (N & 63)) return PANGU_E_SHAPE;              // the dropout entries' common contract
+  if (reinterpret_cast<size_t>(V) & 15) return PANGU_E_ARG;
+  LoraDropOut drop;
+  if (!lora_drop_make(p, seed, &drop.d)) return PANGU_E_ARG;
+  drop.V = V;
+  drop.s = scaling;
+  return lora_wgrad_bf16_launch(stream, dY, lddy, X, ldx, A, B, dA, dB, M, N, K, r, scaling, workspace, workspace_bytes, &drop);
 }

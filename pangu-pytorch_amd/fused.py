@@ -166,8 +166,9 @@ def _infer_arm(layer, sh, infer, *tensors):
     autograd path a frozen bf16 layer runs its Function too, and a fully frozen bf16 model run with grad mode on takes the inference
     kernels (grad mode alone cannot tell)."""
     if sh is not None:
-        if _drops(layer):
-            raise RuntimeError("LoRA adapter dropout in train() mode is fp32 only (no bf16 correction kernels): call eval() first")
+        if infer and _drops(layer):
+            raise RuntimeError("LoRA adapter dropout in a bf16 train()-mode forward runs on the gradient path only (the inference "
+                               "kernels have no materialised projections to correct): call eval() first")
         return infer
     return not (_train_path(layer, *tensors) or _drops(layer))
 

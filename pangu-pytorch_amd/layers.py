@@ -100,7 +100,8 @@ class LoraLinear(nn.Linear):
 
     `lora_dropout` (peft's name; default 0): in train() mode the adapter path reads drop(x) = keep * x / (1 - p) instead of x,
     y = x W^T + b + s drop(x) A^T B^T.  The mask is lora_dropout_keep of a seed drawn per call (`last_dropout_seed` keeps the
-    latest); the layer functions apply it as additive corrections around the W_eff launches (csrc/lora_dropout_f32.hip), fp32 only."""
+    latest); the layer functions apply it as additive corrections around the W_eff launches (csrc/lora_dropout_f32.hip, and
+    csrc/lora_dropout_bf16.hip on the bf16 training path)."""
 
     def __init__(self, in_features, out_features, bias=True, r=16, alpha=16, device=None, dtype=None, lora_dropout=0.0):
         super().__init__(in_features, out_features, bias=bias, device=device, dtype=dtype)

@@ -323,6 +323,79 @@ def lora_wgrad(dy, x, A, B, scaling):
     return dA, dB
 
 
+def _lora_shapes(what, x, y, A, B):
+    """(M, N, K, r) of an adapted projection's bf16 row-strided x (M, K), y / dy (M, N) and its fp32 adapters A (r, K), B (N, r)."""
+    M, N = y.shape
+    K = x.shape[1]
+    r = A.shape[0]
+    if (x.shape[0] != M or tuple(A.shape) != (r, K) or tuple(B.shape) != (N, r) or y.dtype != torch.bfloat16
+            or x.dtype != torch.bfloat16):
+        raise RuntimeError(f"{what}: y {tuple(y.shape)} {y.dtype} x {tuple(x.shape)} {x.dtype} A {tuple(A.shape)} B {tuple(B.shape)}")
+    return M, N, K, r
+
+
+def lora_dropout_fwd(x, y, A, B, scaling, p, seed, act=ACT_NONE, h=None):
+    """ops.lora_dropout_fwd on the bf16 path, IN PLACE on the bf16 projection result y (M, N): y = bf16(float(y) + s ((c * x) A^T)
+    B^T) with the mask layers.lora_dropout_keep(seed, M, K, p) (the fp32 path's).  act=ACT_GELU: h (M, N) = bf16(gelu(y)) of the
+    stored y is written too.  x, y, h bf16 and row-strided; A, B the fp32 master adapters.  -> y (and h)."""
+    lib = _lib.load()
+    xp, ldx = _rows(x, "lora_dropout_fwd.x")
+    yp, ldy = _rows(y, "lora_dropout_fwd.y")
+    M, N, K, r = _lora_shapes("lora_dropout_fwd", x, y, A, B)
+    if act not in (ACT_NONE, ACT_GELU):
+        raise RuntimeError(f"lora_dropout_fwd: act {act} (ACT_NONE or ACT_GELU)")
+    hp, ldh = (None, 0)
+    if act == ACT_GELU:
+        if h is None:
+            h = torch.empty((M, N), dtype=torch.bfloat16, device=y.device)
+        if tuple(h.shape) != (M, N) or h.dtype != torch.bfloat16:
+            raise RuntimeError(f"lora_dropout_fwd: h {tuple(h.shape)} {h.dtype} != {(M, N)} bf16")
+        hp, ldh = _rows(h, "lora_dropout_fwd.h")
+    with _timed("lora_dropout_fwd", 2.0 * M * (K + 2 * N + (N if act == ACT_GELU else 0))):      # bytes: streaming, HBM-bound
+        _lib.check(lib.pangu_lora_dropout_fwd_bf16(_stream(y), xp, ldx, yp, ldy, _p(A, "lora_A", torch.float32),
+                                                   _p(B, "lora_B", torch.float32), M, N, K, r, float(scaling), float(p), int(seed),
+                                                   act, hp, ldh), "lora_dropout_fwd_bf16")
+    return (y, h) if act == ACT_GELU else y
+
+
+def lora_wgrad_dropout(dy, x, A, B, scaling, p, seed):
+    """lora_wgrad with drop(x) = keep * x / (1 - p) in place of x (the mask recomputed from the seed, nothing stored), and the fp32
+    V = s dy B (M, r), which lora_dropout_dx reads -> (dA, dB, V)."""
+    lib = _lib.load()
+    dp, lddy = _rows(dy, "lora_wgrad_dropout.dy")
+    xp, ldx = _rows(x, "lora_wgrad_dropout.x")
+    M, N, K, r = _lora_shapes("lora_wgrad_dropout", x, dy, A, B)
+    ws = _wgrad_workspace(dy.device)
+    dA = torch.empty((r, K), dtype=torch.float32, device=dy.device)
+    dB = torch.empty((N, r), dtype=torch.float32, device=dy.device)
+    V = torch.empty((M, r), dtype=torch.float32, device=dy.device)
+    with _timed("lora_wgrad_dropout", 2.0 * M * (K + N) + 4.0 * M * r):
+        _lib.check(lib.pangu_lora_wgrad_dropout_bf16(_stream(dy), dp, lddy, xp, ldx, _p(A, "lora_A", torch.float32),
+                                                     _p(B, "lora_B", torch.float32), dA.data_ptr(), dB.data_ptr(), V.data_ptr(), M, N,
+                                                     K, r, float(scaling), float(p), int(seed), ws.data_ptr(), _WGRAD_WS_BYTES),
+                   "lora_wgrad_dropout_bf16")
+    return dA, dB, V
+
+
+def lora_dropout_dx(dx, V, A, p, seed, pre=None):
+    """ops.lora_dropout_dx on the bf16 path, IN PLACE on the bf16 result dx (M, K) of the projection's dx GEMM:
+    dx = bf16(float(dx) + c * (V A) [* gelu'(pre)]), V (M, r) fp32 from lora_wgrad_dropout, pre optional bf16 (M, K).  -> dx."""
+    lib = _lib.load()
+    xp, lddx = _rows(dx, "lora_dropout_dx.dx")
+    M, K = dx.shape
+    r = A.shape[0]
+    if (tuple(V.shape) != (M, r) or tuple(A.shape) != (r, K) or dx.dtype != torch.bfloat16
+            or (pre is not None and (tuple(pre.shape) != (M, K) or pre.dtype != torch.bfloat16))):
+        raise RuntimeError(f"lora_dropout_dx: dx {tuple(dx.shape)} {dx.dtype} V {tuple(V.shape)} A {tuple(A.shape)}"
+                           + (f" pre {tuple(pre.shape)} {pre.dtype}" if pre is not None else ""))
+    pp, ldp = _rows(pre, "lora_dropout_dx.pre") if pre is not None else (None, 0)
+    with _timed("lora_dropout_dx", 2.0 * M * (2 * K + (K if pre is not None else 0)) + 4.0 * M * r):
+        _lib.check(lib.pangu_lora_dropout_dx_bf16(_stream(dx), xp, lddx, _p(V, "lora_V", torch.float32),
+                                                  _p(A, "lora_A", torch.float32), M, K, r, float(p), int(seed), pp, ldp),
+                   "lora_dropout_dx_bf16")
+    return dx
+
+
 def window_attention_bwd(qkv, qkv_bias, esb, out, lse, dout, Z, H, W, heads, shifted, desb_out=None):
     lib = _lib.load()
     N, C3 = qkv.shape

@@ -168,17 +168,20 @@ class PanguModel(nn.Module):
     # modules_to_save=["_output_layer.conv", "_output_layer.conv_surface"])) ------------------------------------------------
 
     def enable_lora(self, r=16, alpha=16, target_modules=None, train_also=("_output_layer.conv", "_output_layer.conv_surface"),
-                    dropout=0.0, bf16_training=False, lora_dropout=0.0):
+                    dropout=0.0, bf16_training=False, lora_dropout=0.0, bf16_dropout=False):
         """Replace each targeted nn.Linear IN PLACE by a layers.LoraLinear holding the same base Parameters (default: all 67, as
         the reference does), and freeze everything except the adapters and the modules named in `train_also` (trained in full,
         peft's `modules_to_save`).  target_modules: None, or names / name suffixes ("linear1", "attention.linear2", ...) as peft
         matches them.  bf16_training: allow the adapted model to TRAIN in bf16 mixed precision (`set_compute_dtype(torch.bfloat16)`
         or bf16 autocast): fp32 master adapters and adapter gradients, bf16 images of W_eff, adapter gradients from
         `pangu_lora_wgrad_bf16`; without it a bf16 training forward of an adapted model is refused.  lora_dropout (peft's name, 0 <= p
-        < 1): dropout on the adapter input in train() mode, fp32 training only (layers.LoraLinear; each adapted projection draws one
-        mask seed per sample and forward from torch's default CPU generator, after the block's DropPath draws -- so with dropout
-        active DropPath's draws shift against a run without it; `torch.manual_seed` reproduces a step).  eval() and bf16 inference
-        of such a model are unaffected.  Returns the list of adapted module names."""
+        < 1): dropout on the adapter input in train() mode (layers.LoraLinear; each adapted projection draws one mask seed per
+        sample and forward from torch's default CPU generator, after the block's DropPath draws -- so with dropout active
+        DropPath's draws shift against a run without it; `torch.manual_seed` reproduces a step, with the same masks in fp32 and
+        bf16).  eval() and bf16 inference of such a model are unaffected.  bf16_dropout: with bf16_training, allow lora_dropout > 0
+        on the bf16 training path (the correction kernels of csrc/lora_dropout_bf16.hip; in the blocks whose MLP adapters drop, the
+        one-launch MLP forward gives way to three launches); without it that combination is refused.  Such a model still trains in
+        fp32 through the fp32 kernels.  Returns the list of adapted module names."""
         from .layers import LoraLinear
         from .ops import LORA_RANKS
         if r not in LORA_RANKS:
@@ -188,9 +191,12 @@ class PanguModel(nn.Module):
         lora_dropout = float(lora_dropout)
         if not 0.0 <= lora_dropout < 1.0:
             raise ValueError(f"enable_lora: lora_dropout={lora_dropout} is not in [0, 1)")
-        if lora_dropout > 0.0 and bf16_training:
-            raise ValueError("enable_lora: lora_dropout > 0 with bf16_training=True is not implemented (the dropout corrections are "
-                             "fp32 kernels; bf16 is a follow-up, as it was for the adapters): train in fp32, or with lora_dropout=0")
+        if bf16_dropout and not bf16_training:
+            raise ValueError("enable_lora: bf16_dropout=True needs bf16_training=True (it opts the bf16 training path in to lora_dropout)")
+        if lora_dropout > 0.0 and bf16_training and not bf16_dropout:
+            raise ValueError("enable_lora: lora_dropout > 0 with bf16_training=True needs the opt-in bf16_dropout=True (the bf16 "
+                             "dropout corrections replace the one-launch MLP forward of the adapted blocks by three launches); or "
+                             "train in fp32, or with lora_dropout=0")
         targets = None if target_modules is None else [target_modules] if isinstance(target_modules, str) else list(target_modules)
 
         def hit(name):
@@ -221,6 +227,7 @@ class PanguModel(nn.Module):
                 p.requires_grad_(True)
         self._lora_train_also = train_also
         self._lora_bf16_training = bool(bf16_training)      # (a plain attribute: deepcopy and pickle keep it)
+        self._lora_bf16_dropout = bool(bf16_dropout)        # (likewise)
         self.invalidate_shadows()
         return adapted
 
@@ -237,6 +244,7 @@ class PanguModel(nn.Module):
                         setattr(mod, cname, child.to_linear())
         self._lora_train_also = ()
         self._lora_bf16_training = False
+        self._lora_bf16_dropout = False
         self.invalidate_shadows()
         return self
 
@@ -315,9 +323,11 @@ class PanguModel(nn.Module):
                                "MLP / QKV kernels do not keep the operands the adapter gradients need); train in fp32, or "
                                "run bf16 inference under torch.no_grad(); or opt in to bf16 adapter training with "
                                "enable_lora(..., bf16_training=True)")
-        if want_bf16 and self.training and self.has_lora_dropout():
-            raise RuntimeError("PanguModel: LoRA adapter dropout (lora_dropout > 0) in train() mode is fp32 only; call eval() for bf16 "
-                               "inference, or train in fp32")
+        if want_bf16 and self.training and self.has_lora_dropout() and not (grad_path and getattr(self, "_lora_bf16_dropout", False)):
+            # (under no_grad the inference kernels run, which have no materialised projections to correct)
+            raise RuntimeError("PanguModel: LoRA adapter dropout (lora_dropout > 0) in a bf16 train()-mode forward needs the gradient "
+                               "path and enable_lora(..., bf16_training=True, bf16_dropout=True); call eval() for bf16 inference, or "
+                               "train in fp32")
         if grad_path and not self.training and getattr(self, "eval_grad_mode", "save") == "recompute":
             return _EvalRecomputeFn.apply(self, (statistics, maps, const_h, want_bf16, rev), input, input_surface, *self.parameters())
         return self._forward_dispatch(input, input_surface, statistics, maps, const_h, want_bf16, grad_path, rev)

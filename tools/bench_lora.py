@@ -18,7 +18,12 @@ the 67 W_eff images after an optimizer step.  One JSON line, also written to pro
 output) and `ops.lora_dropout_dx` against their HBM floors 4 M (K + 2N) (+ 4 M N) and 4 M (2K + r) bytes at 6.29 TB/s, and
 `ops.lora_wgrad_dropout` against `ops.lora_wgrad` on the same operands; then, alternating in one process, DropPath off, the fp32
 LoRA step with lora_dropout = P against the same model with 0: ms/step, ratio, peak memory.  One JSON line, also written to
-profiles/lora_dropout.json."""
+profiles/lora_dropout.json.
+
+--dtype bf16 --lora-dropout P: the same for the bf16 kernels (`ops_bf16.lora_dropout_fwd` / `lora_dropout_dx` / `lora_wgrad_dropout`,
+floors 2 M (K + 2N) (+ 2 M N) and 2 M 2K + 4 M r (+ 2 M K with pre) bytes; `lora_wgrad_dropout` against the plain bf16 `lora_wgrad`),
+then the bf16 LoRA step (enable_lora(r, bf16_training=True, bf16_dropout=True)) with lora_dropout = P against the same model with 0,
+with the per-family device-event totals of both.  One JSON line, also written to profiles/lora_dropout_bf16.json."""
 import argparse
 import copy
 import json
@@ -101,26 +106,32 @@ def kernels_bf16(P, r, reps=20):
     return rows
 
 
-def kernels_dropout(P, r, p, reps=20):
-    ops = P.ops
+def kernels_dropout(P, r, p, reps=20, bf16=False):
+    ops = P.ops_bf16 if bf16 else P.ops
+    dt, esz = (torch.bfloat16, 2.0) if bf16 else (torch.float32, 4.0)
     rows = []
     for K, N, M in SHAPES:
         g = torch.Generator(device="cuda").manual_seed(K + N)
-        x = torch.randn(M, K, device="cuda", generator=g)
-        dy = torch.randn(M, N, device="cuda", generator=g)
-        y, h, dx = torch.zeros(M, N, device="cuda"), torch.empty(M, N, device="cuda"), torch.zeros(M, K, device="cuda")
+        x = torch.randn(M, K, device="cuda", generator=g).to(dt)
+        dy = torch.randn(M, N, device="cuda", generator=g).to(dt)
+        y, h, dx = torch.zeros(M, N, device="cuda", dtype=dt), torch.empty(M, N, device="cuda", dtype=dt), torch.zeros(M, K, device="cuda", dtype=dt)
+        pre = torch.randn(M, K, device="cuda", generator=g).to(dt) if bf16 else None
         A = torch.randn(r, K, device="cuda", generator=g) * 0.1
         B = torch.randn(N, r, device="cuda", generator=g) * 0.1
         V = ops.lora_wgrad_dropout(dy, x, A, B, 1.0, p, 1)[2]
-        ms = {k: [] for k in ("fwd", "fwd_gelu", "dx", "wgrad_dropout", "wgrad")}
+        ms = {k: [] for k in ("fwd", "fwd_gelu", "dx", "wgrad_dropout", "wgrad") + (("dx_pre",) if bf16 else ())}
         for _ in range(2):                       # alternately, twice each: all see the same clocks
             ms["fwd"].append(_time(lambda: ops.lora_dropout_fwd(x, y, A, B, 1e-3, p, 1), reps))
             ms["fwd_gelu"].append(_time(lambda: ops.lora_dropout_fwd(x, y, A, B, 1e-3, p, 1, act=ops.ACT_GELU, h=h), reps))
             ms["dx"].append(_time(lambda: ops.lora_dropout_dx(dx, V, A, p, 1), reps))
+            if bf16:
+                ms["dx_pre"].append(_time(lambda: ops.lora_dropout_dx(dx, V, A, p, 1, pre=pre), reps))
             ms["wgrad_dropout"].append(_time(lambda: ops.lora_wgrad_dropout(dy, x, A, B, 1.0, p, 1), reps))
             ms["wgrad"].append(_time(lambda: ops.lora_wgrad(dy, x, A, B, 1.0), reps))
         ms = {k: min(v) for k, v in ms.items()}
-        floor = {"fwd": 4.0 * M * (K + 2 * N), "fwd_gelu": 4.0 * M * (K + 3 * N), "dx": 4.0 * M * (2 * K + r)}
+        floor = {"fwd": esz * M * (K + 2 * N), "fwd_gelu": esz * M * (K + 3 * N), "dx": esz * M * 2 * K + 4.0 * M * r}
+        if bf16:
+            floor["dx_pre"] = esz * M * 3 * K + 4.0 * M * r
         row = {"K": K, "N": N, "M": M, "r": r, "p": p}
         for k, byt in floor.items():
             fl = byt / HBM * 1e3
@@ -128,11 +139,15 @@ def kernels_dropout(P, r, p, reps=20):
         row.update({"wgrad_dropout_ms": round(ms["wgrad_dropout"], 4), "wgrad_ms": round(ms["wgrad"], 4),
                     "wgrad_dropout_vs_wgrad": round(ms["wgrad_dropout"] / ms["wgrad"], 3)})
         rows.append(row)
-        del x, dy, y, h, dx, V
+        del x, dy, y, h, dx, V, pre
     return rows
 
 
-def train_compare_dropout(P, r, p, steps, warmup):
+FAMILIES = ("linear_bf16", "wgrad_bf16", "attn_bf16", "attn_bwd_bf16", "mlp_fused_bf16", "lora_wgrad", "lora_dropout_fwd",
+            "lora_dropout_dx", "lora_wgrad_dropout")
+
+
+def train_compare_dropout(P, r, p, steps, warmup, bf16=False):
     import cases
     import synth
     from pangu_pytorch_amd import train
@@ -145,9 +160,12 @@ def train_compare_dropout(P, r, p, steps, warmup):
     tgt, tgt_s = cases.model_targets("cuda")
     batch = (inp, inp_s, tgt, tgt_s)
     plain = copy.deepcopy(base).train()
-    plain.enable_lora(r=r, alpha=r)
+    plain.enable_lora(r=r, alpha=r, bf16_training=bf16)
     drop = base.train()
-    drop.enable_lora(r=r, alpha=r, lora_dropout=p)
+    drop.enable_lora(r=r, alpha=r, lora_dropout=p, bf16_training=bf16, bf16_dropout=bf16)
+    if bf16:
+        plain.set_compute_dtype(torch.bfloat16)
+        drop.set_compute_dtype(torch.bfloat16)
     runs = {"lora": (plain, train.make_optimizer(plain)), "lora_dropout": (drop, train.make_optimizer(drop))}
     times = {k: [] for k in runs}
     peak = {}
@@ -170,10 +188,18 @@ def train_compare_dropout(P, r, p, steps, warmup):
     train.train_step(drop, runs["lora_dropout"][1], batch, stats, maps, const_h)
     tags = ("lora_dropout_fwd", "lora_dropout_dx", "lora_wgrad_dropout")
     tot = P.ops.timing_stop(tags[0], also=tags)[3]
+    families = {}
+    if bf16:                # device-event totals per launch family, of both kinds of step
+        for k, (m, opt) in runs.items():
+            P.ops.timing_start()
+            train.train_step(m, opt, batch, stats, maps, const_h)
+            fam = P.ops.timing_stop(FAMILIES[0], also=FAMILIES)[3]
+            families[k] = {t: {"ms": round(v[0], 2), "launches": v[2]} for t, v in fam.items() if v[2]}
     return {"rank": r, "p": p, "steps": steps, **{k + "_ms": round(v, 2) for k, v in med.items()},
             "ratio": round(med["lora_dropout"] / med["lora"], 3), "added_ms": round(med["lora_dropout"] - med["lora"], 2),
             **{k + "_peak_GB": round(v / 1e9, 2) for k, v in peak.items()},
-            "launches_in_step": {k: {"ms": round(v[0], 2), "GB": round(v[1] / 1e9, 1), "launches": v[2]} for k, v in tot.items()}}
+            "launches_in_step": {k: {"ms": round(v[0], 2), "GB": round(v[1] / 1e9, 1), "launches": v[2]} for k, v in tot.items()},
+            **({"families_ms": families} if bf16 else {})}
 
 
 def train_compare_bf16(P, r, steps, warmup):
@@ -294,14 +320,14 @@ def main():
     import pangu_pytorch_amd as P
     P._lib.load()
     if a.lora_dropout > 0.0:
-        if a.dtype != "fp32":
-            ap.error("--lora-dropout is fp32 only")
-        res = {"box": torch.cuda.get_device_name(0), "lora_dropout_kernels": kernels_dropout(P, a.rank, a.lora_dropout)}
+        bf16 = a.dtype == "bf16"
+        res = {"box": torch.cuda.get_device_name(0), "dtype": a.dtype,
+               "lora_dropout_kernels": kernels_dropout(P, a.rank, a.lora_dropout, bf16=bf16)}
         if not a.skip_train:
-            res["train_step"] = train_compare_dropout(P, a.rank, a.lora_dropout, a.steps, a.warmup)
+            res["train_step"] = train_compare_dropout(P, a.rank, a.lora_dropout, a.steps, a.warmup, bf16=bf16)
         line = json.dumps(res)
         print(line, flush=True)
-        with open(os.path.join(ROOT, "profiles", "lora_dropout.json"), "w") as f:
+        with open(os.path.join(ROOT, "profiles", "lora_dropout_bf16.json" if bf16 else "lora_dropout.json"), "w") as f:
             f.write(line + "\n")
         return
     if a.dtype == "bf16":
