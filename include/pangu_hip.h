@@ -68,6 +68,17 @@ int pangu_window_mask_export(pangu_stream_t stream, float* out, int Z, int H, in
 int pangu_linear_fwd(pangu_stream_t stream, const float* A, int lda, const float* W, const float* bias,
                      float* C, int ldc, int M, int N, int K, int act, float* aux);
 
+/* The same product for frozen fp32 inference on the bf16 matrix pipe, bit-for-bit fp32 operands: every fp32 value is the exact
+ * sum of three bf16 values (hi, mid, lo), and the six partial products of order >= 2^-16 are accumulated in fp32 (error at the
+ * level of pangu_linear_fwd's own: profiles/f32_split_error.md).
+ *   pangu_split_weight_bf16x3: W[N,K] fp32 -> `image`, 6 * N * K bytes: the three bf16 planes in the fragment order of the GEMM,
+ *     [N/192][K/16][plane][k-half][192 rows][8 bf16].  Once per weight.  N % 192 == 0, K % 16 == 0.
+ *   pangu_linear_fwd_split: C = act(A @ W^T + bias) from that image; A / C row-strided fp32, any M, act NONE or GELU.
+ *     PANGU_E_SHAPE for N % 192 != 0 or K % 16 != 0 means "not served": call pangu_linear_fwd. */
+int pangu_split_weight_bf16x3(pangu_stream_t stream, const float* W, int N, int K, void* image);
+int pangu_linear_fwd_split(pangu_stream_t stream, const float* A, int lda, const void* image, const float* bias,
+                           float* C, int ldc, int M, int N, int K, int act);
+
 /* Weight/bias gradient of a projection (autograd of the calls above; the training step of reference
  * models/pangu_sample.py:71 `loss.backward()`):
  *   dW[N,K] += dC[M,N]^T @ A[M,K]      db[N] += sum_m dC[m,:]   (db may be NULL)

@@ -1,0 +1,266 @@
+// fp32 projection GEMM on the bf16 matrix pipe: C[M,N] = act(A[M,K] @ W[N,K]^T + bias), fp32 in, fp32 out.
+//
+// An fp32 number is EXACTLY the sum of three bf16 numbers, hi = bf16(a), mid = bf16(a - hi), lo = bf16(a - hi - mid) (24
+// significand bits = 3 x 8, both subtractions exact, bf16 has fp32's exponent range), so a product a*b is the sum of nine exact
+// bf16 x bf16 products.  The six of order >= 2^-16 -- (lo,hi) (hi,lo) (mid,mid) (mid,hi) (hi,mid) (hi,hi), small terms first into
+// one fp32 accumulator -- drop only terms of relative size <= 2^-23 per product: the size of the one rounding the fp32 MFMA
+// chain commits per product.  Six v_mfma_f32_32x32x16_bf16 (32 cycles each) replace eight v_mfma_f32_32x32x2_f32 (64 each).
+//
+//   * W is split ONCE per weight (pangu_split_weight_bf16x3) into an image that is already the LDS stage image of the GEMM:
+//     [n-tile of 192][k-step of 16][plane hi/mid/lo][k-half][row 0..191][8 bf16], 18 KB per (n-tile, k-step), streamed by 18
+//     linear 1-KB LDS-DMA pieces; a fragment read (32 consecutive rows of one plane and k-half, 16 B each) is conflict-free.
+//   * A stays fp32 in memory, travels L2 -> LDS by LDS-DMA into the swizzled 64-byte-row image of gemm_f32_dma.hip; a lane
+//     reads its 8 consecutive k as two b128 and splits them in registers (plain casts: v_cvt_pk_bf16_f32, two exact subtracts).
+//   * 128 x 192 tile, 2 x 2 waves of 64 x 96, a ring of three 26-KB stages (LDS-DMA two k-steps ahead, one barrier per step):
+//     78 KB -> two workgroups per CU at <= 256 VGPRs.
+//
+// Values whose bf16 rounding overflows (|a| >= 2^128 - 2^119) or whose lo part falls below the bf16 denormal range lose the
+// exactness of the split; neither occurs in weights or activations of this model.
+#include "common.h"
+
+namespace {
+
+typedef short bf16x8 __attribute__((ext_vector_type(8)));
+
+constexpr int BM = 128;
+constexpr int BN = 192;
+constexpr int BK = 16;
+constexpr int A_BYTES = BM * 64;                 // fp32 A image: 128 rows of 64 B
+constexpr int PLANE = 2 * BN * 16;               // one bf16 plane of a stage: [k-half][row][8 bf16]
+constexpr int B_BYTES = 3 * PLANE;               // 18432
+constexpr int STAGE = A_BYTES + B_BYTES;         // 26624
+constexpr int NSTAGE = 3;
+constexpr int A_PIECES = A_BYTES / 1024;         // 8
+constexpr int PIECES = STAGE / 1024;             // 26: piece q goes to wave q & 3 (waves 0, 1 issue 7, waves 2, 3 issue 6)
+
+// byte offset of logical 16-B chunk `chunk` of row `row` (64-byte rows, chunk XOR F[(row>>2)&3], F = {0,2,3,1}): gemm_f32_dma.hip
+__device__ inline int kswz64(int row, int chunk) {
+  const int f = (0x78 >> (((row >> 2) & 3) * 2)) & 3;
+  return row * 64 + ((chunk ^ f) << 4);
+}
+
+// two fp32 -> their bf16 triples, packed (low half = a): hi + mid + lo == the fp32 value, exactly
+__device__ inline void split2(float a, float b, unsigned& hi, unsigned& mid, unsigned& lo) {
+  const bf16x2_t h = __builtin_convertvector(f32x2_t{a, b}, bf16x2_t);
+  const f32x2_t r1 = f32x2_t{a, b} - __builtin_convertvector(h, f32x2_t);
+  const bf16x2_t m = __builtin_convertvector(r1, bf16x2_t);
+  const f32x2_t r2 = r1 - __builtin_convertvector(m, f32x2_t);
+  hi = __builtin_bit_cast(unsigned, h);
+  mid = __builtin_bit_cast(unsigned, m);
+  lo = __builtin_bit_cast(unsigned, __builtin_convertvector(r2, bf16x2_t));
+}
+
+__device__ inline void split8(const f32x4 c0, const f32x4 c1, bf16x8& hi, bf16x8& mid, bf16x8& lo) {
+  unsigned h0, h1, h2, h3, m0, m1, m2, m3, l0, l1, l2, l3;
+  split2(c0[0], c0[1], h0, m0, l0);
+  split2(c0[2], c0[3], h1, m1, l1);
+  split2(c1[0], c1[1], h2, m2, l2);
+  split2(c1[2], c1[3], h3, m3, l3);
+  hi = __builtin_bit_cast(bf16x8, u32x4{h0, h1, h2, h3});
+  mid = __builtin_bit_cast(bf16x8, u32x4{m0, m1, m2, m3});
+  lo = __builtin_bit_cast(bf16x8, u32x4{l0, l1, l2, l3});
+}
+
+// One thread per (row n, 8 consecutive k): W[N][K] fp32 -> the three planes of the image (layout above; N % 192 == 0, K % 16 == 0)
+__global__ __launch_bounds__(256) void split_weight_kernel(const float* __restrict__ W, unsigned char* __restrict__ image, int N,
+                                                           int K) {
+  const int kc = K >> 3;
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (long long)N * kc) return;
+  const int n = (int)(t / kc), c = (int)(t - (long long)n * kc);
+  const float* src = W + (size_t)n * K + c * 8;
+  const f32x4 c0 = *reinterpret_cast<const f32x4*>(src), c1 = *reinterpret_cast<const f32x4*>(src + 4);
+  bf16x8 p[3];
+  split8(c0, c1, p[0], p[1], p[2]);
+  const int nt = n / BN, nl = n - nt * BN, kt = c >> 1, lh = c & 1;
+  unsigned char* dst = image + ((size_t)nt * (K / BK) + kt) * B_BYTES + (lh * BN + nl) * 16;
+#pragma unroll
+  for (int q = 0; q < 3; ++q) *reinterpret_cast<bf16x8*>(dst + q * PLANE) = p[q];
+}
+
+template <int ACT, bool HAS_BIAS>
+__global__ __launch_bounds__(256, 2) void gemm_f32_split_kernel(const float* __restrict__ A, int lda,
+                                                                const unsigned char* __restrict__ image,
+                                                                const float* __restrict__ bias, float* __restrict__ C, int ldc,
+                                                                int M, int N, int K, int m_tiles, int n_tiles) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[NSTAGE * STAGE];
+
+  // XCD-aware tile assignment (blocks b, b+8, b+16.. share an XCD; they walk the n-tiles of one m-tile).
+  const int b = blockIdx.x;
+  const int xcd = b & 7, local = b >> 3;
+  const int m_tile = (local / n_tiles) * 8 + xcd;
+  const int n_tile = local % n_tiles;
+  if (m_tile >= m_tiles) return;
+  const int m0 = m_tile * BM, n0 = n_tile * BN;
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 1, wn = wave & 1;
+  const int lr = lane & 31, lh = lane >> 5;
+  const int KT = K / BK;
+
+  const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float*>(A), 0, (int)(((size_t)(M - 1) * lda + K) * sizeof(float)), 0x00020000);
+  const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<unsigned char*>(image), 0, (int)((size_t)N * K * 6), 0x00020000);
+  // piece q = i*4 + wave (q < 26).  q < 8: rows 16q .. 16q+15 of A, this lane fills (row 16q + lane>>2, physical chunk lane&3),
+  // i.e. fetches logical chunk (lane&3) ^ F(row); rows >= M are out of range: zeros.  q >= 8: bytes 1024(q-8) .. +1023 of the
+  // (n-tile, k-step) block of the image, copied linearly.
+  unsigned voff_a[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int row = 16 * (i * 4 + wave) + (lane >> 2);
+    const int f = (0x78 >> (((row >> 2) & 3) * 2)) & 3;
+    voff_a[i] = ((unsigned)(m0 + row) * (unsigned)lda + ((lane & 3) ^ f) * 4) * 4u;
+  }
+  const unsigned voff_w = (unsigned)n_tile * (unsigned)KT * (unsigned)B_BYTES + (unsigned)(wave - A_PIECES) * 1024u + lane * 16;
+  auto issue = [&](int kt, int slot) {
+    unsigned char* base = smem + slot * STAGE;
+#pragma unroll
+    for (int i = 0; i < (PIECES + 3) / 4; ++i) {
+      const int q = i * 4 + wave;
+      auto dst = (__attribute__((address_space(3))) void*)(base + q * 1024);
+      if (i < A_PIECES / 4) {
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, dst, 16, (int)voff_a[i], kt * BK * 4, 0, 0);
+      } else if (i * 4 + 3 < PIECES || q < PIECES) {
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, dst, 16, (int)(voff_w + i * 4096u), kt * B_BYTES, 0, 0);
+      }
+    }
+  };
+
+  f32x16 acc[2][3];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+  // fragment byte offsets: lane (lr, lh) owns k = 8lh .. 8lh+7 of its row: logical chunks 2lh, 2lh+1 of the fp32 A row, and
+  // chunk (k-half lh, row) of each W plane
+  int off_a[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int h = 0; h < 2; ++h) off_a[i][h] = kswz64(wm * 64 + i * 32 + lr, 2 * lh + h);
+  const int off_w = A_BYTES + (lh * BN + wn * 96 + lr) * 16;
+
+  issue(0, 0);
+  if (KT > 1) issue(1, 1);
+  int slot = 0;
+  for (int kt = 0; kt < KT; ++kt) {
+    // this wave's pieces of step kt have landed (those of step kt+1 may still fly: 7 pieces on waves 0 and 1, 6 on 2 and 3)
+    if (kt + 1 < KT) {
+      if (wave < 2) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __builtin_amdgcn_s_barrier();                          // ... and everybody's; the slot read in step kt-1 is free
+    asm volatile("" ::: "memory");
+    if (kt + 2 < KT) issue(kt + 2, slot == 0 ? 2 : slot - 1);
+    const unsigned char* St = smem + slot * STAGE;
+    slot = slot == NSTAGE - 1 ? 0 : slot + 1;
+
+    bf16x8 bw[3][3];                                       // [column block][plane]
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+#pragma unroll
+      for (int p = 0; p < 3; ++p) bw[j][p] = *reinterpret_cast<const bf16x8*>(St + off_w + p * PLANE + j * 512);
+    f32x4 ca[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) ca[i][h] = *reinterpret_cast<const f32x4*>(St + off_a[i][h]);
+    bf16x8 ah[2], am[2], al[2];
+    split8(ca[0][0], ca[0][1], ah[0], am[0], al[0]);
+    auto products = [&](int i) {                            // small terms first, one accumulator per output block
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bw[j][0], acc[i][j], 0, 0, 0);
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bw[j][2], acc[i][j], 0, 0, 0);
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[i], bw[j][1], acc[i][j], 0, 0, 0);
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[i], bw[j][0], acc[i][j], 0, 0, 0);
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bw[j][1], acc[i][j], 0, 0, 0);
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bw[j][0], acc[i][j], 0, 0, 0);
+      }
+    };
+    // the split of the second row block (44 VALU instructions) goes into the issue gaps of the first block's 18 MFMAs
+    __builtin_amdgcn_sched_barrier(0);
+    products(0);
+    split8(ca[1][0], ca[1][1], ah[1], am[1], al[1]);
+#pragma unroll
+    for (int g = 0; g < 18; ++g) {
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    products(1);
+  }
+  __syncthreads();                                         // every wave is done with the ring before the epilogue reuses it
+
+  // epilogue (as gemm_f32_dma.hip): each 32x32 tile is transposed through a wave-private LDS patch -> 16-B row segments
+  constexpr int EP_LD = 36;
+  float* ep = reinterpret_cast<float*>(smem) + wave * (32 * EP_LD);
+  const int er = lane >> 3, ec = (lane & 7) * 4;
+  const __amdgpu_buffer_rsrc_t c_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+      C, 0, (int)(((size_t)(M - 1) * ldc + N) * sizeof(float)), 0x00020000);
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const int col = n0 + wn * 96 + j * 32 + ec;
+    f32x4 bv = {0.f, 0.f, 0.f, 0.f};
+    if (HAS_BIAS) bv = *reinterpret_cast<const f32x4*>(bias + col);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) ep[((r & 3) + 8 * (r >> 2) + 4 * lh) * EP_LD + lr] = acc[i][j][r];
+      const int row0 = m0 + wm * 64 + i * 32 + er;
+#pragma unroll
+      for (int it = 0; it < 4; ++it) {
+        f32x4 v = *reinterpret_cast<const f32x4*>(&ep[(er + 8 * it) * EP_LD + ec]);
+        v += bv;
+        if (ACT == PANGU_ACT_GELU) {
+#pragma unroll
+          for (int c = 0; c < 4; ++c) v[c] = gelu_erf(v[c]);
+        }
+        // rows >= M fall outside the descriptor's range and are dropped; non-temporal as in gemm_f32_dma.hip
+        const unsigned off = ((unsigned)(row0 + 8 * it) * (unsigned)ldc + (unsigned)col) * 4u;
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), c_rsrc, (int)off, 0, 2);
+      }
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int pangu_split_weight_bf16x3(pangu_stream_t stream, const float* W, int N, int K, void* image) {
+  if (!W || !image) return PANGU_E_NULL;
+  if (N <= 0 || K <= 0 || (N % BN) != 0 || (K % BK) != 0) return PANGU_E_SHAPE;
+  if ((long long)N * K * 6 >= 0xFFFFFFFFll) return PANGU_E_RANGE;
+  const long long threads = (long long)N * (K / 8);
+  hipLaunchKernelGGL(split_weight_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, W,
+                     reinterpret_cast<unsigned char*>(image), N, K);
+  return pangu_launch_status();
+}
+
+extern "C" int pangu_linear_fwd_split(pangu_stream_t stream, const float* A, int lda, const void* image, const float* bias,
+                                      float* C, int ldc, int M, int N, int K, int act) {
+  if (!A || !image || !C) return PANGU_E_NULL;
+  if (M <= 0 || N <= 0 || K <= 0 || lda < K || ldc < N || (lda & 3) || (ldc & 3)) return PANGU_E_SHAPE;
+  if (act != PANGU_ACT_NONE && act != PANGU_ACT_GELU) return PANGU_E_ARG;
+  if ((N % BN) != 0 || (K % BK) != 0) return PANGU_E_SHAPE;      // not served: the caller takes pangu_linear_fwd
+  if (!pangu_fits_u32(M, lda, 4) || !pangu_fits_u32(M, ldc, 4) || (long long)N * K * 6 >= 0xFFFFFFFFll) return PANGU_E_RANGE;
+  const int m_tiles = (M + BM - 1) / BM, n_tiles = N / BN;
+  const dim3 g(((m_tiles + 7) / 8) * 8 * n_tiles), blk(256);
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned char* img = reinterpret_cast<const unsigned char*>(image);
+#define PANGU_SPLIT_LAUNCH(ACT, HB) \
+  hipLaunchKernelGGL((gemm_f32_split_kernel<ACT, HB>), g, blk, 0, s, A, lda, img, bias, C, ldc, M, N, K, m_tiles, n_tiles)
+  if (act == PANGU_ACT_GELU) {
+    if (bias) PANGU_SPLIT_LAUNCH(PANGU_ACT_GELU, true); else PANGU_SPLIT_LAUNCH(PANGU_ACT_GELU, false);
+  } else {
+    if (bias) PANGU_SPLIT_LAUNCH(PANGU_ACT_NONE, true); else PANGU_SPLIT_LAUNCH(PANGU_ACT_NONE, false);
+  }
+#undef PANGU_SPLIT_LAUNCH
+  return pangu_launch_status();
+}

@@ -78,6 +78,19 @@ def mlp(m, x2d):
     return ops.linear(h, _layers.eff_weight(m.linear2), m.linear2.bias)
 
 
+def _plain_proj(blk, lin, x2, act=ops.ACT_NONE):
+    """A block's plain projection (qkv, MLP-up) in frozen fp32 inference: the exact-split bf16-MFMA kernel from the weight's cached
+    split image where the block allows it (PanguModel.use_split_projections) and the shape is served; the fp32-MFMA kernel
+    otherwise.  A LoRA layer's image is that of its W_eff, keyed by the stamps of W, A and B: a model with adapters, the same model
+    merged and (with B = 0) the base model compute the same bits, as they do on the fp32-MFMA kernels."""
+    w = _layers.eff_weight(lin)
+    if getattr(blk, "split_projections", True):
+        image = ops.split_image(lin, w, None if w is lin.weight else ("lora",) + tuple(lin._stamp()))
+        if image is not None:
+            return ops.linear_split(x2, image, w.shape[0], lin.bias, act=act)
+    return ops.linear(x2, w, lin.bias, act=act)
+
+
 def _block_rows(blk, x2, B, Z, H, W, roll, out=None):
     """The inference composition of a block on the 2-D rows x2 (B*N, C) of B samples -> (B*N, C), written into the 2-D `out` if
     given: 5 kernel launches per sample (qkv, attention core, proj+LN+residual, MLP-up+GELU, MLP-down+LN+residual)."""
@@ -85,7 +98,7 @@ def _block_rows(blk, x2, B, Z, H, W, roll, out=None):
     att = blk.attention
     s1, s2 = drop_path_scales(blk)
     if s1 != 0.0:
-        qkv = ops.linear(x2, _layers.eff_weight(att.linear1), att.linear1.bias)      # (B*N, 3C)
+        qkv = _plain_proj(blk, att.linear1, x2)      # (B*N, 3C)
         # inference on the paper's compact bias table (PanguModel.use_compact_bias): 10 MB instead of 62 MB per block
         esb_c = getattr(att, "_esb_compact", None)
         if esb_c is not None:                 # stale table (weights changed since it was folded): the expanded parameter
@@ -108,7 +121,7 @@ def _block_rows(blk, x2, B, Z, H, W, roll, out=None):
     if s2 == 0.0:
         return x1 if out is None else out.copy_(x1)
     if C in (192, 384):
-        h = ops.linear(x1, _layers.eff_weight(blk.linear.linear1), blk.linear.linear1.bias, act=ops.ACT_GELU)
+        h = _plain_proj(blk, blk.linear.linear1, x1, act=ops.ACT_GELU)
         return ops.linear_ln_residual(h, _layers.eff_weight(blk.linear.linear2), blk.linear.linear2.bias, x1,
                                       blk.norm2.weight, blk.norm2.bias, out=out, branch_scale=s2)
     return ops.ln_residual(mlp(blk.linear, x1), x1, blk.norm2.weight, blk.norm2.bias, out=out, branch_scale=s2)

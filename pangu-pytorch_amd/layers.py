@@ -359,6 +359,9 @@ class EarthAttention3D(nn.Module):
 class EarthSpecificBlock(nn.Module):
     """reference layers.py:127-253."""
 
+    # frozen fp32 inference: qkv and MLP-up on the exact-split bf16-MFMA kernel (PanguModel.use_split_projections sets it per block)
+    split_projections = True
+
     def __init__(self, dim, drop_path_ratio, heads, device=None):
         super().__init__()
         self.device = device

@@ -3,6 +3,7 @@
 Every function requires CUDA(HIP) fp32 contiguous tensors and launches on torch's current stream.
 """
 import threading
+import weakref
 
 import torch
 
@@ -360,6 +361,69 @@ def linear(a, weight, bias=None, act=ACT_NONE, out=None, aux=None):
     with _timed("linear", 2.0 * M * N * K):
         _lib.check(lib.pangu_linear_fwd(_stream(a), ap, lda, wp, bp, op, ldc, M, N, K, act,
                       _chk(aux, "linear.aux") if aux is not None else None), "linear_fwd")
+    return out
+
+
+def split_served(N, K):
+    """The shapes pangu_linear_fwd_split serves (its 192-column tile, 16-wide k-steps)."""
+    return N % 192 == 0 and K % 16 == 0
+
+
+def split_weight_image(weight):
+    """The exact bf16 hi/mid/lo image of an fp32 weight (N, K) in the fragment order of `linear_split` (uint8, 6 N K bytes:
+    [N/192][K/16][plane][k-half][192 rows][8 bf16]; split_layout.image_index states it), or None for a shape the kernel does not
+    serve.  Made once per weight: callers cache it under `param_stamp(weight)` (split_image)."""
+    w2 = weight.detach().reshape(weight.shape[0], -1)
+    N, K = w2.shape
+    if not split_served(N, K) or 6 * N * K >= _U32_BYTES:
+        return None
+    image = torch.empty((6 * N * K,), dtype=torch.uint8, device=w2.device)
+    _lib.check(_lib.load().pangu_split_weight_bf16x3(_stream(w2), _chk(w2, "split.weight"), N, K, image.data_ptr()), "split_weight")
+    return image
+
+
+_split_images = weakref.WeakKeyDictionary()      # projection module -> (param_stamp of its weight, image or None)
+
+
+def split_image(lin, weight, stamp=None):
+    """The image of `weight`, the weight the projection module `lin` computes with, cached per module under `stamp` (a stale stamp
+    rebuilds it); None when the shape is not served.  stamp: what identifies the weight's content -- by default the stamp of the
+    parameter `weight`; for a derived weight (a LoRA layer's W_eff) the stamp of what it was derived from.  The cache holds the
+    modules weakly and lives here, not on the module: pickling or deep-copying a model never carries the images."""
+    if stamp is None:
+        stamp = param_stamp(weight)
+    hit = _split_images.get(lin)
+    if hit is None or hit[0] != stamp:
+        require_epoch_hook()
+        hit = _split_images[lin] = (stamp, split_weight_image(weight))
+    return hit[1]
+
+
+def drop_split_images(modules):
+    """Forget the images of these modules (PanguModel.invalidate_shadows)."""
+    for m in modules:
+        _split_images.pop(m, None)
+
+
+def linear_split(a, image, N, bias=None, act=ACT_NONE, out=None):
+    """out[M,N] = act(a[M,K] @ W[N,K]^T + bias) from W's split image (split_weight_image): fp32 in and out, the product on the
+    bf16 matrix pipe as six exact-split partial products.  `a`/`out` may be row-strided views; act NONE or GELU."""
+    lib = _lib.load()
+    ap, lda = _rows(a, "linear_split.a")
+    M, K = a.shape
+    if image.dtype != torch.uint8 or image.numel() != 6 * N * K or not image.is_cuda or not split_served(N, K):
+        raise RuntimeError(f"linear_split: image of {image.numel()} bytes does not belong to a served ({N}, {K}) weight")
+    bp = _chk(bias, "linear_split.bias") if bias is not None else None
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=a.device)
+    op, ldc = _rows(out, "linear_split.out")
+    chunks = _row_chunks(M, 4 * lda, 4 * ldc)
+    if chunks is not None:
+        for m0, m1 in chunks:
+            linear_split(a[m0:m1], image, N, bias, act, out[m0:m1])
+        return out
+    with _timed("linear", 2.0 * M * N * K):
+        _lib.check(lib.pangu_linear_fwd_split(_stream(a), ap, lda, image.data_ptr(), bp, op, ldc, M, N, K, act), "linear_fwd_split")
     return out
 
 

@@ -12,7 +12,7 @@ import torch
 from torch import nn
 
 from . import fused, ops
-from .layers import (DownSample, EarthSpecificLayer, PatchEmbedding_pretrain, PatchRecovery_pretrain, UpSample,
+from .layers import (DownSample, EarthSpecificBlock, EarthSpecificLayer, PatchEmbedding_pretrain, PatchRecovery_pretrain, UpSample,
                      _trunc_normal_)
 
 
@@ -101,6 +101,7 @@ class PanguModel(nn.Module):
         through `param.data` in place (`p.data.copy_(..)`), which leaves no trace the cache could check."""
         if self._shadow is not None:
             self._shadow.clear()
+        ops.drop_split_images(self.modules())  # the fp32 split images of the inference projections
         for m in self.modules():              # compact bias tables are derived from the parameters too
             if hasattr(m, "_esb_compact"):
                 m._esb_compact = None
@@ -123,6 +124,20 @@ class PanguModel(nn.Module):
                     m._esb_compact = None
             return self
         self._build_compact_bias()
+        return self
+
+    def use_split_projections(self, enable=True):
+        """Frozen fp32 INFERENCE runs the plain projections of every block (qkv, MLP-up + GELU) on the bf16 matrix pipe as
+        exact-split products (csrc/gemm_f32_split.hip: each fp32 operand is the exact sum of three bf16 values; error at the
+        level of the fp32-MFMA kernel's own) from a per-weight image made once and cached under the
+        weight's stamp (about 140 MB for the whole model).  This is the default; `use_split_projections(False)` selects the
+        fp32-MFMA kernels.  LoRA layers compute on the image of their merged weight; training and the bf16 path never take the
+        split kernel."""
+        for m in self.modules():
+            if isinstance(m, EarthSpecificBlock):
+                m.split_projections = bool(enable)
+        if not enable:
+            ops.drop_split_images(self.modules())
         return self
 
     def _build_compact_bias(self):

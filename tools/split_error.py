@@ -1,0 +1,127 @@
+#!/usr/bin/env python3
+"""Error (and, with --time, kernel time) of the exact-split fp32 projection against the fp32-MFMA kernel on one MI355X:
+rel-L2 and max-abs / max error of both against an fp64 product of the same fp32 inputs, as a markdown table.
+
+  python tools/split_error.py [--time] > profiles/f32_split_error.md
+
+Shapes: the cases of tests/test_gpu_parity.py::test_linear, the generator of ::test_linear_random_shapes, and the four plain
+projections of the model at M = 4096.  A shape the split kernel does not serve is listed as such."""
+import os
+import random
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "oracle"))
+import torch  # noqa: E402
+import synth  # noqa: E402
+from pangu_pytorch_amd import ops  # noqa: E402
+
+TEST_LINEAR = [
+    (1000, 192, 192, 0, True), (4099, 576, 192, 0, True), (2048, 768, 192, 1, True), (777, 192, 768, 0, True),
+    (1531, 1152, 384, 0, True), (513, 1536, 384, 1, True), (300, 384, 1536, 0, True), (999, 384, 768, 0, False),
+    (1234, 160, 384, 0, True), (321, 64, 384, 0, True), (650, 192, 112, 0, True), (128, 128, 16, 0, False),
+]
+MODEL = [(4096, 576, 192, 0, "s0 qkv"), (4096, 768, 192, 1, "s0 mlp1+gelu"), (4096, 1152, 384, 0, "s1 qkv"),
+         (4096, 1536, 384, 1, "s1 mlp1+gelu")]
+FULL = [(521280, 576, 192, 0, "s0 qkv"), (521280, 768, 192, 1, "s0 mlp1+gelu"), (131040, 1152, 384, 0, "s1 qkv"),
+        (131040, 1536, 384, 1, "s1 mlp1+gelu")]
+
+
+def errors(got, ref):
+    d = got.double() - ref
+    return (d.norm() / ref.norm()).item(), (d.abs().max() / ref.abs().max()).item()
+
+
+def measure(a, w, b, act):
+    N, K = w.shape
+    ref = a.double() @ w.double().t()
+    if b is not None:
+        ref = ref + b.double()
+    if act:
+        ref = torch.nn.functional.gelu(ref)
+    f32 = errors(ops.linear(a, w, b, act=act), ref)
+    if not ops.split_served(N, K):
+        return f32, None
+    return f32, errors(ops.linear_split(a, ops.split_weight_image(w), N, b, act=act), ref)
+
+
+def row(tag, M, N, K, act, bias, f32, split):
+    head = f"| {tag} | {M}x{N}x{K} | {'gelu' if act else 'none'} | {'yes' if bias else 'no'} | {f32[0]:.3e} / {f32[1]:.3e} |"
+    if split is None:
+        return head + " not served | |"
+    return head + f" {split[0]:.3e} / {split[1]:.3e} | {split[0] / f32[0]:.3f} |"
+
+
+def timeit(fn, iters=10, warm=3):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def main():
+    print("# Exact-split fp32 projection: error against an fp64 product\n")
+    print("rel-L2 / (max-abs / max) of `pangu_linear_fwd` (fp32 MFMA) and `pangu_linear_fwd_split` (six bf16 MFMA terms, one "
+          "accumulator) on the same fp32 inputs; ratio = split rel-L2 / fp32 rel-L2.  Made by `tools/split_error.py`.\n")
+    print("| set | MxNxK | act | bias | fp32 MFMA | split | ratio |")
+    print("|---|---|---|---|---|---|---|")
+    worst = 0.0
+    worst_abs = 0.0
+    for M, N, K, act, bias in TEST_LINEAR:
+        a = synth.uniform((M, K), 11).cuda()
+        w = synth.uniform((N, K), 12, 1.0 / K ** 0.5).cuda()
+        b = synth.uniform((N,), 13, 0.5).cuda() if bias else None
+        f32, split = measure(a, w, b, act)
+        print(row("test_linear", M, N, K, act, bias, f32, split))
+        if split:
+            worst, worst_abs = max(worst, split[0] / f32[0]), max(worst_abs, split[0])
+    rnd = random.Random(7)
+    torch.manual_seed(7)
+    for _ in range(40):
+        N = rnd.choice([160, 192, 384, 576, 768, 1152, 1536, 132, 176, 64])
+        K = 16 * rnd.randint(1, 100)
+        M = rnd.randint(1, 3000)
+        act = rnd.choice([0, 0, 1, 3])
+        a = torch.randn(M, K, device="cuda")
+        w = torch.randn(N, K, device="cuda") / K ** 0.5
+        b = torch.randn(N, device="cuda") if rnd.random() < 0.7 else None
+        if act == 3:
+            torch.randn(M, N, device="cuda")          # (keeps the generator's random stream; the split kernel has no ADD epilogue)
+            act = 0
+        f32, split = measure(a, w, b, act)
+        print(row("random_shapes", M, N, K, act, b is not None, f32, split))
+        if split:
+            worst, worst_abs = max(worst, split[0] / f32[0]), max(worst_abs, split[0])
+    torch.manual_seed(11)
+    for M, N, K, act, name in MODEL:
+        a = torch.randn(M, K, device="cuda")
+        w = torch.randn(N, K, device="cuda") / K ** 0.5
+        b = torch.randn(N, device="cuda")
+        f32, split = measure(a, w, b, act)
+        print(row(name, M, N, K, act, True, f32, split))
+        worst, worst_abs = max(worst, split[0] / f32[0]), max(worst_abs, split[0])
+    print(f"\nWorst ratio {worst:.3f} (required <= 1.5); worst split rel-L2 {worst_abs:.3e} (required < 2e-6).")
+    if "--time" in sys.argv:
+        print("\n## Kernel time at the model's shapes (HIP events, 10 launches)\n")
+        print("| projection | MxNxK | fp32 MFMA ms | split ms | speed-up | split TFLOP/s |")
+        print("|---|---|---|---|---|---|")
+        for M, N, K, act, name in FULL:
+            a = torch.randn(M, K, device="cuda")
+            w = torch.randn(N, K, device="cuda") / K ** 0.5
+            b = torch.randn(N, device="cuda")
+            out = torch.empty(M, N, device="cuda")
+            image = ops.split_weight_image(w)
+            t0 = timeit(lambda: ops.linear(a, w, b, act=act, out=out))
+            t1 = timeit(lambda: ops.linear_split(a, image, N, b, act=act, out=out))
+            print(f"| {name} | {M}x{N}x{K} | {t0:.3f} | {t1:.3f} | {t0 / t1:.2f}x | {2.0 * M * N * K / t1 / 1e9:.0f} |")
+
+
+if __name__ == "__main__":
+    main()
