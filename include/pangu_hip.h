@@ -229,6 +229,15 @@ int pangu_linear_ln_residual_fwd(pangu_stream_t stream, const float* A, int lda,
                                  const float* shortcut, int lds, const float* gamma, const float* beta, float* out, int ldo,
                                  int M, int N, int K, float branch_scale);
 
+/* The same fused op for frozen fp32 inference with the product on the bf16 matrix pipe: W given as its exact-split image
+ * (pangu_split_weight_bf16x3: for N = 384 the kernel reads the image's two 192-row n-tile blocks of every k-step), six partial
+ * products into one fp32 accumulator as in pangu_linear_fwd_split, the LayerNorm / residual epilogue of
+ * pangu_linear_ln_residual_fwd operation for operation (error: profiles/f32_split_ln_error.md).  Same arguments otherwise, same
+ * checks and error codes: N = 192 or 384, K % 16 == 0, bias may be NULL. */
+int pangu_linear_ln_residual_fwd_split(pangu_stream_t stream, const float* A, int lda, const void* image, const float* bias,
+                                       const float* shortcut, int lds, const float* gamma, const float* beta, float* out,
+                                       int ldo, int M, int N, int K, float branch_scale);
+
 /* Backward of the LayerNorm branch of pangu_ln_residual_fwd (the shortcut's gradient is dout itself):
  *   dy [N][C] overwritten;  dgamma[C], dbeta[C] ACCUMULATED (atomics).  dout may be row-strided (lddo). */
 int pangu_ln_residual_bwd(pangu_stream_t stream, const float* dout, int lddo, const float* y, const float* gamma,

@@ -16,50 +16,18 @@
 //
 // Values whose bf16 rounding overflows (|a| >= 2^128 - 2^119) or whose lo part falls below the bf16 denormal range lose the
 // exactness of the split; neither occurs in weights or activations of this model.
-#include "common.h"
+#include "split_f32.h"
 
 namespace {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
+using namespace pangu_split;      // bf16x8, BK, PLANE, B_BYTES, NSTAGE, kswz64, split2 / split8
 
 constexpr int BM = 128;
-constexpr int BN = 192;
-constexpr int BK = 16;
+constexpr int BN = W_ROWS;                       // 192
 constexpr int A_BYTES = BM * 64;                 // fp32 A image: 128 rows of 64 B
-constexpr int PLANE = 2 * BN * 16;               // one bf16 plane of a stage: [k-half][row][8 bf16]
-constexpr int B_BYTES = 3 * PLANE;               // 18432
 constexpr int STAGE = A_BYTES + B_BYTES;         // 26624
-constexpr int NSTAGE = 3;
 constexpr int A_PIECES = A_BYTES / 1024;         // 8
 constexpr int PIECES = STAGE / 1024;             // 26: piece q goes to wave q & 3 (waves 0, 1 issue 7, waves 2, 3 issue 6)
-
-// byte offset of logical 16-B chunk `chunk` of row `row` (64-byte rows, chunk XOR F[(row>>2)&3], F = {0,2,3,1}): gemm_f32_dma.hip
-__device__ inline int kswz64(int row, int chunk) {
-  const int f = (0x78 >> (((row >> 2) & 3) * 2)) & 3;
-  return row * 64 + ((chunk ^ f) << 4);
-}
-
-// two fp32 -> their bf16 triples, packed (low half = a): hi + mid + lo == the fp32 value, exactly
-__device__ inline void split2(float a, float b, unsigned& hi, unsigned& mid, unsigned& lo) {
-  const bf16x2_t h = __builtin_convertvector(f32x2_t{a, b}, bf16x2_t);
-  const f32x2_t r1 = f32x2_t{a, b} - __builtin_convertvector(h, f32x2_t);
-  const bf16x2_t m = __builtin_convertvector(r1, bf16x2_t);
-  const f32x2_t r2 = r1 - __builtin_convertvector(m, f32x2_t);
-  hi = __builtin_bit_cast(unsigned, h);
-  mid = __builtin_bit_cast(unsigned, m);
-  lo = __builtin_bit_cast(unsigned, __builtin_convertvector(r2, bf16x2_t));
-}
-
-__device__ inline void split8(const f32x4 c0, const f32x4 c1, bf16x8& hi, bf16x8& mid, bf16x8& lo) {
-  unsigned h0, h1, h2, h3, m0, m1, m2, m3, l0, l1, l2, l3;
-  split2(c0[0], c0[1], h0, m0, l0);
-  split2(c0[2], c0[3], h1, m1, l1);
-  split2(c1[0], c1[1], h2, m2, l2);
-  split2(c1[2], c1[3], h3, m3, l3);
-  hi = __builtin_bit_cast(bf16x8, u32x4{h0, h1, h2, h3});
-  mid = __builtin_bit_cast(bf16x8, u32x4{m0, m1, m2, m3});
-  lo = __builtin_bit_cast(bf16x8, u32x4{l0, l1, l2, l3});
-}
 
 // One thread per (row n, 8 consecutive k): W[N][K] fp32 -> the three planes of the image (layout above; N % 192 == 0, K % 16 == 0)
 __global__ __launch_bounds__(256) void split_weight_kernel(const float* __restrict__ W, unsigned char* __restrict__ image, int N,

@@ -91,6 +91,27 @@ def _plain_proj(blk, lin, x2, act=ops.ACT_NONE):
     return ops.linear(x2, w, lin.bias, act=act)
 
 
+# (N, K) of the fused projections that stay on the fp32-MFMA kernel although the split kernel serves them and is faster (1.5 x): the
+# stage-1/2 attention out-projection.  With all four shapes on the split kernel the 7-step rollout's step-7 fingerprint error against
+# the reference reads 1.04e-3, over the 1e-3 that tests/test_gpu_rollout.py allows (8.74e-4 before); that figure moves between
+# 8.5e-4 and 1.5e-3 over the 16 subsets of the four shapes, each of them more accurate per launch than the fp32 kernel
+# (profiles/f32_split_ln_per_shape.md), and the subset without this shape reads 8.54e-4.
+_LN_SPLIT_NOT_DISPATCHED = {(384, 384)}
+
+
+def _ln_proj(blk, lin, x2, shortcut, norm, out=None, branch_scale=1.0):
+    """A block's fused projection (attention out-projection, MLP-down) + LayerNorm + residual in frozen fp32 inference, C = 192 /
+    384: like _plain_proj the exact-split kernel from the cached image of the weight (of W_eff for a LoRA layer) where the block
+    allows it, the fp32-MFMA kernel otherwise."""
+    w = _layers.eff_weight(lin)
+    if getattr(blk, "split_projections", True) and tuple(w.shape) not in _LN_SPLIT_NOT_DISPATCHED:
+        image = ops.split_image(lin, w, None if w is lin.weight else ("lora",) + tuple(lin._stamp()))
+        if image is not None:
+            return ops.linear_ln_residual_split(x2, image, w.shape[0], lin.bias, shortcut, norm.weight, norm.bias, out=out,
+                                                branch_scale=branch_scale)
+    return ops.linear_ln_residual(x2, w, lin.bias, shortcut, norm.weight, norm.bias, out=out, branch_scale=branch_scale)
+
+
 def _block_rows(blk, x2, B, Z, H, W, roll, out=None):
     """The inference composition of a block on the 2-D rows x2 (B*N, C) of B samples -> (B*N, C), written into the 2-D `out` if
     given: 5 kernel launches per sample (qkv, attention core, proj+LN+residual, MLP-up+GELU, MLP-down+LN+residual)."""
@@ -111,8 +132,7 @@ def _block_rows(blk, x2, B, Z, H, W, roll, out=None):
                                             att.head_number, roll, compact=cp) for b in range(B)], 0) if B > 1 else \
             ops.window_attention(qkv, att.linear1.bias, esb, Z, H, W, att.head_number, roll, compact=cp)
         if C in (192, 384):     # projection + post-norm residual in one launch (the GEMM tile spans the row)
-            x1 = ops.linear_ln_residual(o, _layers.eff_weight(att.linear2), att.linear2.bias, x2, blk.norm1.weight,
-                                        blk.norm1.bias, branch_scale=s1)
+            x1 = _ln_proj(blk, att.linear2, o, x2, blk.norm1, branch_scale=s1)
         else:
             y = ops.linear(o, _layers.eff_weight(att.linear2), att.linear2.bias)
             x1 = ops.ln_residual(y, x2, blk.norm1.weight, blk.norm1.bias, branch_scale=s1)
@@ -122,8 +142,7 @@ def _block_rows(blk, x2, B, Z, H, W, roll, out=None):
         return x1 if out is None else out.copy_(x1)
     if C in (192, 384):
         h = _plain_proj(blk, blk.linear.linear1, x1, act=ops.ACT_GELU)
-        return ops.linear_ln_residual(h, _layers.eff_weight(blk.linear.linear2), blk.linear.linear2.bias, x1,
-                                      blk.norm2.weight, blk.norm2.bias, out=out, branch_scale=s2)
+        return _ln_proj(blk, blk.linear.linear2, h, x1, blk.norm2, out=out, branch_scale=s2)
     return ops.ln_residual(mlp(blk.linear, x1), x1, blk.norm2.weight, blk.norm2.bias, out=out, branch_scale=s2)
 
 

@@ -451,6 +451,33 @@ def linear_ln_residual(a, weight, bias, shortcut, gamma, beta, out=None, branch_
     return out
 
 
+def linear_ln_residual_split(a, image, N, bias, shortcut, gamma, beta, out=None, branch_scale=1.0):
+    """`linear_ln_residual` from W's split image (split_weight_image): the product on the bf16 matrix pipe as six exact-split
+    partial products, the LayerNorm / residual epilogue of the fp32 kernel operation for operation (N = 192 or 384; inference)."""
+    lib = _lib.load()
+    ap, lda = _rows(a, "linear_ln_split.a")
+    M, K = a.shape
+    if image.dtype != torch.uint8 or image.numel() != 6 * N * K or not image.is_cuda or not split_served(N, K):
+        raise RuntimeError(f"linear_ln_residual_split: image of {image.numel()} bytes does not belong to a served ({N}, {K}) weight")
+    if tuple(shortcut.shape) != (M, N):
+        raise RuntimeError(f"linear_ln_residual_split: a {tuple(a.shape)} weight ({N}, {K}) shortcut {tuple(shortcut.shape)}")
+    sp, lds = _rows(shortcut, "linear_ln_split.shortcut")
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=a.device)
+    op, ldo = _rows(out, "linear_ln_split.out")
+    chunks = _row_chunks(M, 4 * lda, 4 * ldo, 4 * lds)
+    if chunks is not None:
+        for m0, m1 in chunks:
+            linear_ln_residual_split(a[m0:m1], image, N, bias, shortcut[m0:m1], gamma, beta, out[m0:m1], branch_scale)
+        return out
+    with _timed("linear_ln", 2.0 * M * N * K):      # the bucket of linear_ln_residual: bench.py's roofline keeps counting these
+        _lib.check(lib.pangu_linear_ln_residual_fwd_split(
+            _stream(a), ap, lda, image.data_ptr(), _chk(bias, "linear_ln_split.bias") if bias is not None else None,
+            sp, lds, _chk(gamma, "gamma"), _chk(beta, "beta"), op, ldo, M, N, K, float(branch_scale)),
+            "linear_ln_residual_fwd_split")
+    return out
+
+
 _WGRAD_WS_BYTES = 96 << 20
 _wgrad_ws = {}      # (device, stream) -> fp32 scratch buffer of the two-stage weight-gradient reduction (shared with ops_bf16)
 

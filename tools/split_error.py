@@ -3,9 +3,12 @@
 rel-L2 and max-abs / max error of both against an fp64 product of the same fp32 inputs, as a markdown table.
 
   python tools/split_error.py [--time] > profiles/f32_split_error.md
+  python tools/split_error.py --ln [--time] > profiles/f32_split_ln_error.md      (the fused projection + LayerNorm + residual)
 
 Shapes: the cases of tests/test_gpu_parity.py::test_linear, the generator of ::test_linear_random_shapes, and the four plain
-projections of the model at M = 4096.  A shape the split kernel does not serve is listed as such."""
+projections of the model at M = 4096.  A shape the split kernel does not serve is listed as such.  --ln: the cases of
+tests/test_gpu_linear_ln_split.py::test_parity_against_fp64 and ::test_wide_dynamic_range, and the four fused projections of the
+model at M = 4096, against the fp64 value of shortcut + s * LN(a W^T + b)."""
 import os
 import random
 import sys
@@ -66,7 +69,77 @@ def timeit(fn, iters=10, warm=3):
     return a.elapsed_time(b) / iters
 
 
+LN_MODEL = [(4096, 192, 192, "s0 proj"), (4096, 192, 768, "s0 mlp2"), (4096, 384, 384, "s1 proj"), (4096, 384, 1536, "s1 mlp2")]
+LN_FULL = [(521280, 192, 192, "s0 proj"), (521280, 192, 768, "s0 mlp2"), (131040, 384, 384, "s1 proj"), (131040, 384, 1536, "s1 mlp2")]
+
+
+def ln_problem(M, N, K, seed):
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    r = lambda *shape: torch.randn(shape, generator=g, device="cuda")
+    return r(M, K), r(N, K) / K ** 0.5, r(N), 1.5 * r(M, N), 1.0 + 0.5 * r(N), 0.3 * r(N)
+
+
+def ln_measure(a, w, b, sc, g, be, s):
+    N = w.shape[0]
+    y = a.double() @ w.double().t()
+    if b is not None:
+        y = y + b.double()
+    ref = sc.double() + s * torch.nn.functional.layer_norm(y, (N,), g.double(), be.double(), 1e-5)
+    f32 = errors(ops.linear_ln_residual(a, w, b, sc, g, be, branch_scale=s), ref)
+    return f32, errors(ops.linear_ln_residual_split(a, ops.split_weight_image(w), N, b, sc, g, be, branch_scale=s), ref)
+
+
+def main_ln():
+    print("# Exact-split fused projection + LayerNorm + residual: error against fp64\n")
+    print("rel-L2 / (max-abs / max) of `pangu_linear_ln_residual_fwd` (fp32 MFMA) and `pangu_linear_ln_residual_fwd_split` (six bf16 "
+          "MFMA terms, one accumulator, the same epilogue) against the fp64 value of shortcut + s * LN(a W^T + b) on the same fp32 "
+          "inputs; ratio = split rel-L2 / fp32 rel-L2.  Made by `tools/split_error.py --ln`.\n")
+    print("| set | MxNxK | s | bias | fp32 MFMA | split | ratio |")
+    print("|---|---|---|---|---|---|---|")
+    worst, worst_l2, worst_max = 0.0, 0.0, 0.0
+
+    def one(tag, M, N, K, bias, s, prob):
+        nonlocal worst, worst_l2, worst_max
+        a, w, b, sc, g, be = prob
+        f32, split = ln_measure(a, w, b if bias else None, sc, g, be, s)
+        print(f"| {tag} | {M}x{N}x{K} | {s} | {'yes' if bias else 'no'} | {f32[0]:.3e} / {f32[1]:.3e} | {split[0]:.3e} / {split[1]:.3e} "
+              f"| {split[0] / f32[0]:.3f} |")
+        worst, worst_l2, worst_max = max(worst, split[0] / f32[0]), max(worst_l2, split[0]), max(worst_max, split[1])
+
+    for M in (1, 127, 129, 1000):
+        for N in (192, 384):
+            for K in (16, 32, 48, 64, 400):
+                prob = ln_problem(M, N, K, 1000 * M + N + K)
+                for bias in (True, False):
+                    for s in (1.0, 0.5):
+                        one("parity", M, N, K, bias, s, prob)
+    for M, N, K in [(129, 192, 192), (1000, 384, 400)]:
+        gen = torch.Generator(device="cuda").manual_seed(5)
+        mag = lambda shape: torch.exp2(torch.randint(-20, 21, shape, generator=gen, device="cuda").float())
+        prob = list(ln_problem(M, N, K, 61 + N))
+        prob[0] = torch.randn((M, K), generator=gen, device="cuda") * mag((M, K))
+        prob[1] = torch.randn((N, K), generator=gen, device="cuda") * mag((N, K))
+        one("wide range", M, N, K, True, 1.0, prob)
+    for M, N, K, name in LN_MODEL:
+        one(name, M, N, K, True, 1.0, ln_problem(M, N, K, 11 + K))
+    print(f"\nWorst ratio {worst:.3f} (required <= 1.5); worst split rel-L2 {worst_l2:.3e}; worst split max-abs / max "
+          f"{worst_max:.3e} (required < 2e-4).")
+    if "--time" in sys.argv:
+        print("\n## Kernel time at the model's shapes (HIP events, 10 launches)\n")
+        print("| projection | MxNxK | fp32 MFMA ms | split ms | speed-up | split TFLOP/s |")
+        print("|---|---|---|---|---|---|")
+        for M, N, K, name in LN_FULL:
+            a, w, b, sc, g, be = ln_problem(M, N, K, 3)
+            out = torch.empty(M, N, device="cuda")
+            image = ops.split_weight_image(w)
+            t0 = timeit(lambda: ops.linear_ln_residual(a, w, b, sc, g, be, out=out))
+            t1 = timeit(lambda: ops.linear_ln_residual_split(a, image, N, b, sc, g, be, out=out))
+            print(f"| {name} | {M}x{N}x{K} | {t0:.3f} | {t1:.3f} | {t0 / t1:.2f}x | {2.0 * M * N * K / t1 / 1e9:.0f} |")
+
+
 def main():
+    if "--ln" in sys.argv:
+        return main_ln()
     print("# Exact-split fp32 projection: error against an fp64 product\n")
     print("rel-L2 / (max-abs / max) of `pangu_linear_fwd` (fp32 MFMA) and `pangu_linear_fwd_split` (six bf16 MFMA terms, one "
           "accumulator) on the same fp32 inputs; ratio = split rel-L2 / fp32 rel-L2.  Made by `tools/split_error.py`.\n")
