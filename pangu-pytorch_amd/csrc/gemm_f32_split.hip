@@ -9,10 +9,11 @@
 //   * W is split ONCE per weight (pangu_split_weight_bf16x3) into an image that is already the LDS stage image of the GEMM:
 //     [n-tile of 192][k-step of 16][plane hi/mid/lo][k-half][row 0..191][8 bf16], 18 KB per (n-tile, k-step), streamed by 18
 //     linear 1-KB LDS-DMA pieces; a fragment read (32 consecutive rows of one plane and k-half, 16 B each) is conflict-free.
-//   * A stays fp32 in memory, travels L2 -> LDS by LDS-DMA into the swizzled 64-byte-row image of gemm_f32_dma.hip; a lane
+//   * A stays fp32 in memory, travels L2 -> LDS by LDS-DMA into the swizzled 64-byte-row image of gemm_f32_dma_loop.h; a lane
 //     reads its 8 consecutive k as two b128 and splits them in registers (plain casts: v_cvt_pk_bf16_f32, two exact subtracts).
 //   * 128 x 192 tile, 2 x 2 waves of 64 x 96, a ring of three 26-KB stages (LDS-DMA two k-steps ahead, one barrier per step):
-//     78 KB -> two workgroups per CU at <= 256 VGPRs.
+//     78 KB -> two workgroups per CU at <= 256 VGPRs.  The main loop is split_main_loop<2, 2, 3> of split_f32.h, shared with
+//     gemm_ln_f32_split.hip; this file holds the weight split and the plain store epilogue.
 //
 // Values whose bf16 rounding overflows (|a| >= 2^128 - 2^119) or whose lo part falls below the bf16 denormal range lose the
 // exactness of the split; neither occurs in weights or activations of this model.
@@ -20,14 +21,11 @@
 
 namespace {
 
-using namespace pangu_split;      // bf16x8, BK, PLANE, B_BYTES, NSTAGE, kswz64, split2 / split8
+using namespace pangu_split;      // bf16x8, BK, PLANE, B_BYTES, split8, SplitTile, split_main_loop
 
-constexpr int BM = 128;
-constexpr int BN = W_ROWS;                       // 192
-constexpr int A_BYTES = BM * 64;                 // fp32 A image: 128 rows of 64 B
-constexpr int STAGE = A_BYTES + B_BYTES;         // 26624
-constexpr int A_PIECES = A_BYTES / 1024;         // 8
-constexpr int PIECES = STAGE / 1024;             // 26: piece q goes to wave q & 3 (waves 0, 1 issue 7, waves 2, 3 issue 6)
+using Tile = SplitTile<2, 2, 3>;
+constexpr int BM = Tile::BM;                     // 128
+constexpr int BN = Tile::BN;                     // 192 = W_ROWS: one n-tile block of the image per tile
 
 // One thread per (row n, 8 consecutive k): W[N][K] fp32 -> the three planes of the image (layout above; N % 192 == 0, K % 16 == 0)
 __global__ __launch_bounds__(256) void split_weight_kernel(const float* __restrict__ W, unsigned char* __restrict__ image, int N,
@@ -51,7 +49,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_split_kernel(const float* __r
                                                                 const unsigned char* __restrict__ image,
                                                                 const float* __restrict__ bias, float* __restrict__ C, int ldc,
                                                                 int M, int N, int K, int m_tiles, int n_tiles) {
-  __shared__ __attribute__((aligned(16))) unsigned char smem[NSTAGE * STAGE];
+  __shared__ __attribute__((aligned(16))) unsigned char smem[Tile::SMEM];
 
   // XCD-aware tile assignment (blocks b, b+8, b+16.. share an XCD; they walk the n-tiles of one m-tile).
   const int b = blockIdx.x;
@@ -61,111 +59,13 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_split_kernel(const float* __r
   if (m_tile >= m_tiles) return;
   const int m0 = m_tile * BM, n0 = n_tile * BN;
 
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wm = wave >> 1, wn = wave & 1;
   const int lr = lane & 31, lh = lane >> 5;
-  const int KT = K / BK;
-
-  const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(A), 0, (int)(((size_t)(M - 1) * lda + K) * sizeof(float)), 0x00020000);
-  const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<unsigned char*>(image), 0, (int)((size_t)N * K * 6), 0x00020000);
-  // piece q = i*4 + wave (q < 26).  q < 8: rows 16q .. 16q+15 of A, this lane fills (row 16q + lane>>2, physical chunk lane&3),
-  // i.e. fetches logical chunk (lane&3) ^ F(row); rows >= M are out of range: zeros.  q >= 8: bytes 1024(q-8) .. +1023 of the
-  // (n-tile, k-step) block of the image, copied linearly.
-  unsigned voff_a[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int row = 16 * (i * 4 + wave) + (lane >> 2);
-    const int f = (0x78 >> (((row >> 2) & 3) * 2)) & 3;
-    voff_a[i] = ((unsigned)(m0 + row) * (unsigned)lda + ((lane & 3) ^ f) * 4) * 4u;
-  }
-  const unsigned voff_w = (unsigned)n_tile * (unsigned)KT * (unsigned)B_BYTES + (unsigned)(wave - A_PIECES) * 1024u + lane * 16;
-  auto issue = [&](int kt, int slot) {
-    unsigned char* base = smem + slot * STAGE;
-#pragma unroll
-    for (int i = 0; i < (PIECES + 3) / 4; ++i) {
-      const int q = i * 4 + wave;
-      auto dst = (__attribute__((address_space(3))) void*)(base + q * 1024);
-      if (i < A_PIECES / 4) {
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, dst, 16, (int)voff_a[i], kt * BK * 4, 0, 0);
-      } else if (i * 4 + 3 < PIECES || q < PIECES) {
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, dst, 16, (int)(voff_w + i * 4096u), kt * B_BYTES, 0, 0);
-      }
-    }
-  };
 
   f32x16 acc[2][3];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  // fragment byte offsets: lane (lr, lh) owns k = 8lh .. 8lh+7 of its row: logical chunks 2lh, 2lh+1 of the fp32 A row, and
-  // chunk (k-half lh, row) of each W plane
-  int off_a[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int h = 0; h < 2; ++h) off_a[i][h] = kswz64(wm * 64 + i * 32 + lr, 2 * lh + h);
-  const int off_w = A_BYTES + (lh * BN + wn * 96 + lr) * 16;
-
-  issue(0, 0);
-  if (KT > 1) issue(1, 1);
-  int slot = 0;
-  for (int kt = 0; kt < KT; ++kt) {
-    // this wave's pieces of step kt have landed (those of step kt+1 may still fly: 7 pieces on waves 0 and 1, 6 on 2 and 3)
-    if (kt + 1 < KT) {
-      if (wave < 2) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __builtin_amdgcn_s_barrier();                          // ... and everybody's; the slot read in step kt-1 is free
-    asm volatile("" ::: "memory");
-    if (kt + 2 < KT) issue(kt + 2, slot == 0 ? 2 : slot - 1);
-    const unsigned char* St = smem + slot * STAGE;
-    slot = slot == NSTAGE - 1 ? 0 : slot + 1;
-
-    bf16x8 bw[3][3];                                       // [column block][plane]
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-#pragma unroll
-      for (int p = 0; p < 3; ++p) bw[j][p] = *reinterpret_cast<const bf16x8*>(St + off_w + p * PLANE + j * 512);
-    f32x4 ca[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int h = 0; h < 2; ++h) ca[i][h] = *reinterpret_cast<const f32x4*>(St + off_a[i][h]);
-    bf16x8 ah[2], am[2], al[2];
-    split8(ca[0][0], ca[0][1], ah[0], am[0], al[0]);
-    auto products = [&](int i) {                            // small terms first, one accumulator per output block
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bw[j][0], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bw[j][2], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[i], bw[j][1], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[i], bw[j][0], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bw[j][1], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bw[j][0], acc[i][j], 0, 0, 0);
-      }
-    };
-    // the split of the second row block (44 VALU instructions) goes into the issue gaps of the first block's 18 MFMAs
-    __builtin_amdgcn_sched_barrier(0);
-    products(0);
-    split8(ca[1][0], ca[1][1], ah[1], am[1], al[1]);
-#pragma unroll
-    for (int g = 0; g < 18; ++g) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    products(1);
-  }
-  __syncthreads();                                         // every wave is done with the ring before the epilogue reuses it
+  split_main_loop<2, 2, 3>(smem, A, lda, image, M, N, K, m0, n_tile, acc);
 
   // epilogue (as gemm_f32_dma.hip): each 32x32 tile is transposed through a wave-private LDS patch -> 16-B row segments
   constexpr int EP_LD = 36;

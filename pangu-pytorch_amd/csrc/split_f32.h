@@ -1,25 +1,21 @@
 // What the exact-split fp32 GEMMs (gemm_f32_split.hip, gemm_ln_f32_split.hip) share: the bf16 hi/mid/lo split of fp32 values, the
-// layout constants of the weight image (pangu_split_weight_bf16x3) and of the LDS stage both kernels stream it into, and the
-// swizzle of the fp32 A image.
+// layout constants of the weight image (pangu_split_weight_bf16x3) and of the LDS stage it is streamed into, and the main loop
+// (one definition: the two kernels differ in their epilogues only).  The fp32 A image and its swizzle are those of the fp32-MFMA
+// LDS-DMA loop (gemm_f32_dma_loop.h).
 #pragma once
-#include "common.h"
+#include "gemm_f32_dma_loop.h"
 
 namespace pangu_split {
 
+using pangu_dma::BK;                             // k-step of 16: one 64-byte fp32 A row, two 8-wide bf16 k-halves
+using pangu_dma::kswz64;
+
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 
-constexpr int BK = 16;                           // k-step: one 64-byte fp32 A row, two 8-wide bf16 k-halves
 constexpr int W_ROWS = 192;                      // rows of one n-tile block of the image
 constexpr int PLANE = 2 * W_ROWS * 16;           // one bf16 plane of an (n-tile, k-step) block: [k-half][row][8 bf16]
 constexpr int B_BYTES = 3 * PLANE;               // 18432: hi, mid, lo
 constexpr int W_PIECES = B_BYTES / 1024;         // 18 linear 1-KB LDS-DMA pieces per block
-constexpr int NSTAGE = 3;                        // ring depth: LDS-DMA two k-steps ahead, one barrier per step
-
-// byte offset of logical 16-B chunk `chunk` of row `row` (64-byte rows, chunk XOR F[(row>>2)&3], F = {0,2,3,1}): gemm_f32_dma.hip
-__device__ inline int kswz64(int row, int chunk) {
-  const int f = (0x78 >> (((row >> 2) & 3) * 2)) & 3;
-  return row * 64 + ((chunk ^ f) << 4);
-}
 
 // two fp32 -> their bf16 triples, packed (low half = a): hi + mid + lo == the fp32 value, exactly
 __device__ inline void split2(float a, float b, unsigned& hi, unsigned& mid, unsigned& lo) {
@@ -41,6 +37,153 @@ __device__ inline void split8(const f32x4 c0, const f32x4 c1, bf16x8& hi, bf16x8
   hi = __builtin_bit_cast(bf16x8, u32x4{h0, h1, h2, h3});
   mid = __builtin_bit_cast(bf16x8, u32x4{m0, m1, m2, m3});
   lo = __builtin_bit_cast(bf16x8, u32x4{l0, l1, l2, l3});
+}
+
+// WMW x WNW waves of 64 x 96; NST ring stages (3: LDS-DMA two k-steps ahead; 2: one ahead), one barrier per step.  A stage is
+// the fp32 A image (BM rows of 64 B) followed by the NT n-tile blocks of the weight image the tile's columns span.
+template <int WMW, int WNW, int NST>
+struct SplitTile {
+  static constexpr int NW = WMW * WNW;                 // waves
+  static constexpr int BM = 64 * WMW;
+  static constexpr int BN = 96 * WNW;
+  static constexpr int NT = BN / W_ROWS;               // n-tile blocks of the image per k-step
+  static constexpr int A_BYTES = BM * 64;
+  static constexpr int STAGE = A_BYTES + NT * B_BYTES;
+  static constexpr int SMEM = NST * STAGE;
+  static_assert(NST == 2 || NST == 3, "ring depth");
+  static_assert(BN % W_ROWS == 0, "whole n-tile blocks");
+};
+
+// acc[i][j] += A[m0 + wm 64 + i 32 .. +31, :] @ W[first_n_tile 192 + wn 96 + j 32 .. +31, :]^T over all of K (K % 16 == 0), W
+// given as its split image of N rows; wave = wm * WNW + wn.  smem: SplitTile::SMEM bytes.  Ends behind a barrier: every wave is
+// done with the ring, the caller's epilogue may reuse it.
+template <int WMW, int WNW, int NST>
+__device__ __forceinline__ void split_main_loop(unsigned char* smem, const float* __restrict__ A, int lda,
+                                                const unsigned char* __restrict__ image, int M, int N, int K, int m0,
+                                                int first_n_tile, f32x16 (&acc)[2][3]) {
+  using T = SplitTile<WMW, WNW, NST>;
+  constexpr int NW = T::NW, A_BYTES = T::A_BYTES, STAGE = T::STAGE;
+  constexpr int A_PIECES = A_BYTES / 1024;
+  constexpr int PIECES = STAGE / 1024;             // piece q goes to wave q % NW
+  constexpr int A_IT = A_PIECES / NW;              // issue rounds that are all A
+  constexpr int IT = (PIECES + NW - 1) / NW;       // issue rounds; waves < REM issue IT pieces, the others IT - 1 (REM = 0: all IT)
+  constexpr int REM = PIECES % NW;                 // <2, 2, 3>: 26 pieces, IT = 7, REM = 2: waves 0, 1 issue 7, waves 2, 3 issue 6
+  static_assert(A_PIECES % NW == 0, "piece rounds");
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave / WNW, wn = wave % WNW;
+  const int lr = lane & 31, lh = lane >> 5;
+  const int KT = K / BK;
+
+  const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float*>(A), 0, (int)(((size_t)(M - 1) * lda + K) * sizeof(float)), 0x00020000);
+  const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<unsigned char*>(image), 0, (int)((size_t)N * K * 6), 0x00020000);
+  // piece q = i*NW + wave (q < PIECES).  q < A_PIECES: rows 16q .. 16q+15 of A, this lane fills (row 16q + lane>>2, physical chunk
+  // lane&3), i.e. fetches logical chunk (lane&3) ^ F(row); rows >= M are out of range: zeros.  Otherwise piece p = q - A_PIECES of
+  // the W part: bytes 1024 (p % 18) .. +1023 of the (n-tile first_n_tile + p / 18, k-step) block of the image, copied linearly.
+  unsigned voff_a[A_IT], voff_w[IT - A_IT];
+#pragma unroll
+  for (int i = 0; i < A_IT; ++i) {
+    const int row = 16 * (i * NW + wave) + (lane >> 2);
+    const int f = (0x78 >> (((row >> 2) & 3) * 2)) & 3;
+    voff_a[i] = ((unsigned)(m0 + row) * (unsigned)lda + ((lane & 3) ^ f) * 4) * 4u;
+  }
+#pragma unroll
+  for (int i = A_IT; i < IT; ++i) {
+    const int p = i * NW + wave - A_PIECES;
+    voff_w[i - A_IT] = (unsigned)(first_n_tile + p / W_PIECES) * (unsigned)KT * (unsigned)B_BYTES +
+                       (unsigned)(p % W_PIECES) * 1024u + lane * 16;
+  }
+  auto issue = [&](int kt, int slot) {
+    unsigned char* base = smem + slot * STAGE;
+#pragma unroll
+    for (int i = 0; i < IT; ++i) {
+      const int q = i * NW + wave;
+      auto dst = (__attribute__((address_space(3))) void*)(base + q * 1024);
+      if (i < A_IT) {
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, dst, 16, (int)voff_a[i], kt * BK * 4, 0, 0);
+      } else if (i * NW + NW - 1 < PIECES || q < PIECES) {
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, dst, 16, (int)voff_w[i - A_IT], kt * B_BYTES, 0, 0);
+      }
+    }
+  };
+
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+  // fragment byte offsets: lane (lr, lh) owns k = 8lh .. 8lh+7 of its row: logical chunks 2lh, 2lh+1 of the fp32 A row, and
+  // chunk (k-half lh, row) of each W plane of the wave's n-tile block
+  int off_a[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int h = 0; h < 2; ++h) off_a[i][h] = kswz64(wm * 64 + i * 32 + lr, 2 * lh + h);
+  const int off_w = A_BYTES + (wn >> 1) * B_BYTES + (lh * W_ROWS + (wn & 1) * 96 + lr) * 16;
+
+  issue(0, 0);
+  if (NST == 3 && KT > 1) issue(1, 1);
+  int slot = 0;
+  for (int kt = 0; kt < KT; ++kt) {
+    // this wave's pieces of step kt have landed.  Three stages: those of step kt+1 may still fly, and vmcnt counts this wave's
+    // own loads only, so the count to wait down to is the wave's pieces per step: IT, or IT - 1 on the waves past REM
+    if (NST == 3 && kt + 1 < KT) {
+      if (REM == 0 || wave < REM) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(IT) : "memory");
+      else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(IT - 1) : "memory");
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __builtin_amdgcn_s_barrier();                          // ... and everybody's; the slot read in step kt-1 is free
+    asm volatile("" ::: "memory");
+    if (NST == 3) {
+      if (kt + 2 < KT) issue(kt + 2, slot == 0 ? 2 : slot - 1);
+    } else {
+      if (kt + 1 < KT) issue(kt + 1, slot ^ 1);
+    }
+    const unsigned char* St = smem + slot * STAGE;
+    slot = slot == NST - 1 ? 0 : slot + 1;
+
+    bf16x8 bw[3][3];                                       // [column block][plane]
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+#pragma unroll
+      for (int p = 0; p < 3; ++p) bw[j][p] = *reinterpret_cast<const bf16x8*>(St + off_w + p * PLANE + j * 512);
+    f32x4 ca[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) ca[i][h] = *reinterpret_cast<const f32x4*>(St + off_a[i][h]);
+    bf16x8 ah[2], am[2], al[2];
+    split8(ca[0][0], ca[0][1], ah[0], am[0], al[0]);
+    auto products = [&](int i) {                            // small terms first, one accumulator per output block
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bw[j][0], acc[i][j], 0, 0, 0);
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bw[j][2], acc[i][j], 0, 0, 0);
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[i], bw[j][1], acc[i][j], 0, 0, 0);
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[i], bw[j][0], acc[i][j], 0, 0, 0);
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bw[j][1], acc[i][j], 0, 0, 0);
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bw[j][0], acc[i][j], 0, 0, 0);
+      }
+    };
+    // the split of the second row block (44 VALU instructions) goes into the issue gaps of the first block's 18 MFMAs
+    __builtin_amdgcn_sched_barrier(0);
+    products(0);
+    split8(ca[1][0], ca[1][1], ah[1], am[1], al[1]);
+#pragma unroll
+    for (int g = 0; g < 18; ++g) {
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    products(1);
+  }
+  __syncthreads();
 }
 
 }  // namespace pangu_split

@@ -405,14 +405,18 @@ def drop_split_images(modules):
         _split_images.pop(m, None)
 
 
+def _check_split_image(what, image, N, K):
+    if image.dtype != torch.uint8 or image.numel() != 6 * N * K or not image.is_cuda or not split_served(N, K):
+        raise RuntimeError(f"{what}: image of {image.numel()} bytes does not belong to a served ({N}, {K}) weight")
+
+
 def linear_split(a, image, N, bias=None, act=ACT_NONE, out=None):
     """out[M,N] = act(a[M,K] @ W[N,K]^T + bias) from W's split image (split_weight_image): fp32 in and out, the product on the
     bf16 matrix pipe as six exact-split partial products.  `a`/`out` may be row-strided views; act NONE or GELU."""
     lib = _lib.load()
     ap, lda = _rows(a, "linear_split.a")
     M, K = a.shape
-    if image.dtype != torch.uint8 or image.numel() != 6 * N * K or not image.is_cuda or not split_served(N, K):
-        raise RuntimeError(f"linear_split: image of {image.numel()} bytes does not belong to a served ({N}, {K}) weight")
+    _check_split_image("linear_split", image, N, K)
     bp = _chk(bias, "linear_split.bias") if bias is not None else None
     if out is None:
         out = torch.empty((M, N), dtype=torch.float32, device=a.device)
@@ -457,8 +461,7 @@ def linear_ln_residual_split(a, image, N, bias, shortcut, gamma, beta, out=None,
     lib = _lib.load()
     ap, lda = _rows(a, "linear_ln_split.a")
     M, K = a.shape
-    if image.dtype != torch.uint8 or image.numel() != 6 * N * K or not image.is_cuda or not split_served(N, K):
-        raise RuntimeError(f"linear_ln_residual_split: image of {image.numel()} bytes does not belong to a served ({N}, {K}) weight")
+    _check_split_image("linear_ln_residual_split", image, N, K)
     if tuple(shortcut.shape) != (M, N):
         raise RuntimeError(f"linear_ln_residual_split: a {tuple(a.shape)} weight ({N}, {K}) shortcut {tuple(shortcut.shape)}")
     sp, lds = _rows(shortcut, "linear_ln_split.shortcut")

@@ -1,4 +1,5 @@
-"""The layouts of the exact-split fp32 GEMM (csrc/gemm_f32_split.hip), stated in plain Python: the weight image written by
+"""The layouts of the exact-split fp32 GEMMs (the image written in csrc/gemm_f32_split.hip, the LDS stage of split_main_loop
+<2, 2, 3> in csrc/split_f32.h, its fp32 A part that of csrc/gemm_f32_dma_loop.h), stated in plain Python: the weight image written by
 pangu_split_weight_bf16x3, and the LDS stage the kernel reads its MFMA fragments from.  No torch, no GPU: the tests un-permute an
 image and check the bank behaviour of the fragment reads with these."""
 

@@ -1,5 +1,5 @@
-"""The exact-split fused projection + LayerNorm + residual (csrc/gemm_ln_f32_split.hip): the product of gemm_f32_split.hip under
-the epilogue of gemm_ln_f32_dma.hip.  Needs an MI355X: run with `-m gpu`.
+"""The exact-split fused projection + LayerNorm + residual (csrc/gemm_ln_f32_split.hip): the main loop gemm_f32_split.hip runs
+(csrc/split_f32.h) under the epilogue gemm_ln_f32_dma.hip runs (csrc/ln_epilogue_f32.h).  Needs an MI355X: run with `-m gpu`.
 
 The error rule (the rule of tests/test_gpu_linear_split.py applied to the fused op): against the fp64 value of
 shortcut + s * LN(a @ W^T + b) on the same fp32 inputs, the rel-L2 error of the split op is at most 1.5 x the error of

@@ -90,7 +90,7 @@ def test_parity_against_fp64(P, M):
     """Every N x K of the served family at this M, act none / GELU, with and without bias."""
     torch.manual_seed(M)
     for N in (192, 384, 576):
-        for K in (16, 192, 400):
+        for K in (16, 32, 48, 192, 400):      # 1, 2, 3 k-steps: up to the ring depth
             a = torch.randn(M, K, device="cuda")
             w = torch.randn(N, K, device="cuda") / K ** 0.5
             b = torch.randn(N, device="cuda")

@@ -2,6 +2,7 @@
 """Register / scratch / LDS budget of every kernel of libpangu_hip.so, from the compiler's own resource report:
 
   python tools/codeobj_resources.py > profiles/r03_codeobj_resources.md        (no GPU needed: hipcc cross-compiles gfx950)
+  python tools/codeobj_resources.py --csrc DIR gemm_f32_dma.hip ...           (another checkout's csrc; only these files)
 
 Each csrc/*.hip is compiled with the Makefile's flags plus -Rpass-analysis=kernel-resource-usage (the numbers that end up in
 the code object's kernel descriptors: .vgpr_count, .agpr_count, .private_segment_fixed_size, .group_segment_fixed_size).
@@ -56,9 +57,12 @@ def scratch_in_loops(src):
 
 
 def main():
+    args = sys.argv[1:]
+    csrc = args.pop(1) if args[:1] == ["--csrc"] and len(args) > 1 else CSRC
+    args = [a for a in args if a != "--csrc"]
     rows = []
     loops = {}
-    for src in sorted(glob.glob(os.path.join(CSRC, "*.hip"))):
+    for src in [os.path.join(csrc, a) for a in args] or sorted(glob.glob(os.path.join(csrc, "*.hip"))):
         loops.update(scratch_in_loops(src))
         with tempfile.NamedTemporaryFile(suffix=".o") as tmp:
             r = subprocess.run([HIPCC] + FLAGS + [src, "-o", tmp.name], capture_output=True, text=True)
