@@ -11,9 +11,13 @@
 //     linear 1-KB LDS-DMA pieces; a fragment read (32 consecutive rows of one plane and k-half, 16 B each) is conflict-free.
 //   * A stays fp32 in memory, travels L2 -> LDS by LDS-DMA into the swizzled 64-byte-row image of gemm_f32_dma_loop.h; a lane
 //     reads its 8 consecutive k as two b128 and splits them in registers (plain casts: v_cvt_pk_bf16_f32, two exact subtracts).
-//   * 128 x 192 tile, 2 x 2 waves of 64 x 96, a ring of three 26-KB stages (LDS-DMA two k-steps ahead, one barrier per step):
-//     78 KB -> two workgroups per CU at <= 256 VGPRs.  The main loop is split_main_loop<2, 2, 3> of split_f32.h, shared with
-//     gemm_ln_f32_split.hip; this file holds the weight split and the plain store epilogue.
+//   * 128 x 192 tile, 4 x 1 waves of 32 x 192: a wave owns its 32 rows, so every A element is split once (two waves shared the
+//     rows of the 2 x 2 waves of 64 x 96 this replaces, and each split them: 88 VALU instructions per wave and k-step, now 40).
+//     A ring of two 26-KB stages (LDS-DMA one k-step ahead, one barrier per step): 52 KB and 163 VGPRs -> THREE workgroups per
+//     CU, which is where the time comes from on the K = 192 / 384 launches (prologue and epilogue of one workgroup under the
+//     loops of two others): 5-7 % at K = 192, 0.6-3 % at K = 384, bit for bit the same product (profiles/f32_split_rows_speed.md).
+//     The main loop is split_main_loop<4, 1, 2, true, true> of split_f32.h, shared with gemm_ln_f32_split.hip; this file holds
+//     the weight split and the plain store epilogue.
 //
 // Values whose bf16 rounding overflows (|a| >= 2^128 - 2^119) or whose lo part falls below the bf16 denormal range lose the
 // exactness of the split; neither occurs in weights or activations of this model.
@@ -23,7 +27,7 @@ namespace {
 
 using namespace pangu_split;      // bf16x8, BK, PLANE, B_BYTES, split8, SplitTile, split_main_loop
 
-using Tile = SplitTile<2, 2, 3>;
+using Tile = SplitTile<4, 1, 2, true>;           // 4 x 1 row-owning waves, ring of two stages
 constexpr int BM = Tile::BM;                     // 128
 constexpr int BN = Tile::BN;                     // 192 = W_ROWS: one n-tile block of the image per tile
 
@@ -45,7 +49,7 @@ __global__ __launch_bounds__(256) void split_weight_kernel(const float* __restri
 }
 
 template <int ACT, bool HAS_BIAS>
-__global__ __launch_bounds__(256, 2) void gemm_f32_split_kernel(const float* __restrict__ A, int lda,
+__global__ __launch_bounds__(256, 3) void gemm_f32_split_kernel(const float* __restrict__ A, int lda,
                                                                 const unsigned char* __restrict__ image,
                                                                 const float* __restrict__ bias, float* __restrict__ C, int ldc,
                                                                 int M, int N, int K, int m_tiles, int n_tiles) {
@@ -61,11 +65,10 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_split_kernel(const float* __r
 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
   const int lr = lane & 31, lh = lane >> 5;
 
-  f32x16 acc[2][3];
-  split_main_loop<2, 2, 3>(smem, A, lda, image, M, N, K, m0, n_tile, acc);
+  f32x16 acc[1][6];                                // the wave's rows 32 wave .. +31 x the tile's 192 columns
+  split_main_loop<4, 1, 2, true, true>(smem, A, lda, image, M, N, K, m0, n_tile, acc);
 
   // epilogue (as gemm_f32_dma.hip): each 32x32 tile is transposed through a wave-private LDS patch -> 16-B row segments
   constexpr int EP_LD = 36;
@@ -73,28 +76,25 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_split_kernel(const float* __r
   const int er = lane >> 3, ec = (lane & 7) * 4;
   const __amdgpu_buffer_rsrc_t c_rsrc = __builtin_amdgcn_make_buffer_rsrc(
       C, 0, (int)(((size_t)(M - 1) * ldc + N) * sizeof(float)), 0x00020000);
+  const int row0 = m0 + wave * 32 + er;
 #pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    const int col = n0 + wn * 96 + j * 32 + ec;
+  for (int j = 0; j < 6; ++j) {
+    const int col = n0 + j * 32 + ec;
     f32x4 bv = {0.f, 0.f, 0.f, 0.f};
     if (HAS_BIAS) bv = *reinterpret_cast<const f32x4*>(bias + col);
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
+    for (int r = 0; r < 16; ++r) ep[((r & 3) + 8 * (r >> 2) + 4 * lh) * EP_LD + lr] = acc[0][j][r];
 #pragma unroll
-      for (int r = 0; r < 16; ++r) ep[((r & 3) + 8 * (r >> 2) + 4 * lh) * EP_LD + lr] = acc[i][j][r];
-      const int row0 = m0 + wm * 64 + i * 32 + er;
+    for (int it = 0; it < 4; ++it) {
+      f32x4 v = *reinterpret_cast<const f32x4*>(&ep[(er + 8 * it) * EP_LD + ec]);
+      v += bv;
+      if (ACT == PANGU_ACT_GELU) {
 #pragma unroll
-      for (int it = 0; it < 4; ++it) {
-        f32x4 v = *reinterpret_cast<const f32x4*>(&ep[(er + 8 * it) * EP_LD + ec]);
-        v += bv;
-        if (ACT == PANGU_ACT_GELU) {
-#pragma unroll
-          for (int c = 0; c < 4; ++c) v[c] = gelu_erf(v[c]);
-        }
-        // rows >= M fall outside the descriptor's range and are dropped; non-temporal as in gemm_f32_dma.hip
-        const unsigned off = ((unsigned)(row0 + 8 * it) * (unsigned)ldc + (unsigned)col) * 4u;
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), c_rsrc, (int)off, 0, 2);
+        for (int c = 0; c < 4; ++c) v[c] = gelu_erf(v[c]);
       }
+      // rows >= M fall outside the descriptor's range and are dropped; non-temporal as in gemm_f32_dma.hip
+      const unsigned off = ((unsigned)(row0 + 8 * it) * (unsigned)ldc + (unsigned)col) * 4u;
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), c_rsrc, (int)off, 0, 2);
     }
   }
 }

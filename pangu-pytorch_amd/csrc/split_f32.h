@@ -39,13 +39,19 @@ __device__ inline void split8(const f32x4 c0, const f32x4 c1, bf16x8& hi, bf16x8
   lo = __builtin_bit_cast(bf16x8, u32x4{l0, l1, l2, l3});
 }
 
-// WMW x WNW waves of 64 x 96; NST ring stages (3: LDS-DMA two k-steps ahead; 2: one ahead), one barrier per step.  A stage is
-// the fp32 A image (BM rows of 64 B) followed by the NT n-tile blocks of the weight image the tile's columns span.
-template <int WMW, int WNW, int NST>
+// WMW x WNW waves, each of RB row blocks x CB column tiles of 32 x 32; NST ring stages (3: LDS-DMA two k-steps ahead; 2: one
+// ahead), one barrier per step.  ROWS = true is the row-owning tiling: a wave holds ONE 32-row block and all 192 columns of an
+// n-tile block (32 x 192), so every A element is split by exactly one wave; ROWS = false is the 64 x 96 wave (two row blocks, half
+// an n-tile block), where the WNW waves that share rows each split them again.  A stage is the fp32 A image (BM rows of 64 B)
+// followed by the NT n-tile blocks of the weight image the tile's columns span: the same image, the same LDS-DMA pieces and, per
+// output element, the same six MFMAs per k-step in the same order under either tiling, so the two compute the same bits.
+template <int WMW, int WNW, int NST, bool ROWS>
 struct SplitTile {
+  static constexpr int RB = ROWS ? 1 : 2;              // 32-row blocks per wave
+  static constexpr int CB = ROWS ? 6 : 3;              // 32-column tiles per wave
   static constexpr int NW = WMW * WNW;                 // waves
-  static constexpr int BM = 64 * WMW;
-  static constexpr int BN = 96 * WNW;
+  static constexpr int BM = 32 * RB * WMW;
+  static constexpr int BN = 32 * CB * WNW;
   static constexpr int NT = BN / W_ROWS;               // n-tile blocks of the image per k-step
   static constexpr int A_BYTES = BM * 64;
   static constexpr int STAGE = A_BYTES + NT * B_BYTES;
@@ -54,15 +60,17 @@ struct SplitTile {
   static_assert(BN % W_ROWS == 0, "whole n-tile blocks");
 };
 
-// acc[i][j] += A[m0 + wm 64 + i 32 .. +31, :] @ W[first_n_tile 192 + wn 96 + j 32 .. +31, :]^T over all of K (K % 16 == 0), W
+// acc[i][j] += A[m0 + (wm RB + i) 32 .. +31, :] @ W[first_n_tile 192 + (wn CB + j) 32 .. +31, :]^T over all of K (K % 16 == 0), W
 // given as its split image of N rows; wave = wm * WNW + wn.  smem: SplitTile::SMEM bytes.  Ends behind a barrier: every wave is
-// done with the ring, the caller's epilogue may reuse it.
-template <int WMW, int WNW, int NST>
+// done with the ring, the caller's epilogue may reuse it.  LEAN (ROWS only): the W fragments of three column tiles in flight
+// instead of all six, 163 VGPRs instead of 198: the form that fits three workgroups per CU (<= 168).
+template <int WMW, int WNW, int NST, bool ROWS, bool LEAN = false>
 __device__ __forceinline__ void split_main_loop(unsigned char* smem, const float* __restrict__ A, int lda,
                                                 const unsigned char* __restrict__ image, int M, int N, int K, int m0,
-                                                int first_n_tile, f32x16 (&acc)[2][3]) {
-  using T = SplitTile<WMW, WNW, NST>;
-  constexpr int NW = T::NW, A_BYTES = T::A_BYTES, STAGE = T::STAGE;
+                                                int first_n_tile,
+                                                f32x16 (&acc)[SplitTile<WMW, WNW, NST, ROWS>::RB][SplitTile<WMW, WNW, NST, ROWS>::CB]) {
+  using T = SplitTile<WMW, WNW, NST, ROWS>;
+  constexpr int NW = T::NW, A_BYTES = T::A_BYTES, STAGE = T::STAGE, RB = T::RB, CB = T::CB;
   constexpr int A_PIECES = A_BYTES / 1024;
   constexpr int PIECES = STAGE / 1024;             // piece q goes to wave q % NW
   constexpr int A_IT = A_PIECES / NW;              // issue rounds that are all A
@@ -111,20 +119,21 @@ __device__ __forceinline__ void split_main_loop(unsigned char* smem, const float
   };
 
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
+  for (int i = 0; i < RB; ++i)
 #pragma unroll
-    for (int j = 0; j < 3; ++j)
+    for (int j = 0; j < CB; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
   // fragment byte offsets: lane (lr, lh) owns k = 8lh .. 8lh+7 of its row: logical chunks 2lh, 2lh+1 of the fp32 A row, and
   // chunk (k-half lh, row) of each W plane of the wave's n-tile block
-  int off_a[2][2];
+  int off_a[RB][2];
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
+  for (int i = 0; i < RB; ++i)
 #pragma unroll
-    for (int h = 0; h < 2; ++h) off_a[i][h] = kswz64(wm * 64 + i * 32 + lr, 2 * lh + h);
-  const int off_w = A_BYTES + (wn >> 1) * B_BYTES + (lh * W_ROWS + (wn & 1) * 96 + lr) * 16;
+    for (int h = 0; h < 2; ++h) off_a[i][h] = kswz64((wm * RB + i) * 32 + lr, 2 * lh + h);
+  const int wcol = wn * CB * 32;                           // the wave's first column in the tile
+  const int off_w = A_BYTES + (wcol / W_ROWS) * B_BYTES + (lh * W_ROWS + wcol % W_ROWS + lr) * 16;
 
   issue(0, 0);
   if (NST == 3 && KT > 1) issue(1, 1);
@@ -148,40 +157,76 @@ __device__ __forceinline__ void split_main_loop(unsigned char* smem, const float
     const unsigned char* St = smem + slot * STAGE;
     slot = slot == NST - 1 ? 0 : slot + 1;
 
-    bf16x8 bw[3][3];                                       // [column block][plane]
+    bf16x8 bw[CB][3];                                      // [column tile][plane]
+    f32x4 ca[RB][2];
+    auto read_w = [&](int j0, int j1) {
 #pragma unroll
-    for (int j = 0; j < 3; ++j)
+      for (int j = j0; j < j1; ++j)
 #pragma unroll
-      for (int p = 0; p < 3; ++p) bw[j][p] = *reinterpret_cast<const bf16x8*>(St + off_w + p * PLANE + j * 512);
-    f32x4 ca[2][2];
+        for (int p = 0; p < 3; ++p) bw[j][p] = *reinterpret_cast<const bf16x8*>(St + off_w + p * PLANE + j * 512);
+    };
+    read_w(0, LEAN ? 3 : CB);
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < RB; ++i)
 #pragma unroll
       for (int h = 0; h < 2; ++h) ca[i][h] = *reinterpret_cast<const f32x4*>(St + off_a[i][h]);
-    bf16x8 ah[2], am[2], al[2];
-    split8(ca[0][0], ca[0][1], ah[0], am[0], al[0]);
-    auto products = [&](int i) {                            // small terms first, one accumulator per output block
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bw[j][0], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bw[j][2], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[i], bw[j][1], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[i], bw[j][0], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bw[j][1], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bw[j][0], acc[i][j], 0, 0, 0);
-      }
+    bf16x8 ah[RB], am[RB], al[RB];
+    auto tile = [&](int i, int j) {                         // small terms first, one accumulator per output block
+      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bw[j][0], acc[i][j], 0, 0, 0);
+      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bw[j][2], acc[i][j], 0, 0, 0);
+      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[i], bw[j][1], acc[i][j], 0, 0, 0);
+      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[i], bw[j][0], acc[i][j], 0, 0, 0);
+      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bw[j][1], acc[i][j], 0, 0, 0);
+      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bw[j][0], acc[i][j], 0, 0, 0);
     };
-    // the split of the second row block (44 VALU instructions) goes into the issue gaps of the first block's 18 MFMAs
-    __builtin_amdgcn_sched_barrier(0);
-    products(0);
-    split8(ca[1][0], ca[1][1], ah[1], am[1], al[1]);
+    auto products = [&](int i) {
 #pragma unroll
-    for (int g = 0; g < 18; ++g) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
+      for (int j = 0; j < CB; ++j) tile(i, j);
+    };
+    if constexpr (ROWS) {
+      // One split per wave and k-step.  Every accumulator's first product takes the lo part, the end of the split's dependency
+      // chain, so no MFMA of this wave can start under the split (the SIMD's other waves run theirs meanwhile); what can be
+      // arranged is that the LDS reads are out before it.  Left free, the compiler reads A, splits, and only then reads W, a pair
+      // of column tiles at a time into the same registers, so the MFMAs wait for LDS three more times per step (measured: up to 2.4 %
+      // slower, profiles/f32_split_rows_speed.md).
+      if constexpr (LEAN) {
+        // A and three tiles of W before the split; behind each of the first three tiles' MFMAs the reads of the tile three
+        // further on, into the registers that tile frees: two tiles' MFMAs (384 matrix cycles) between a read and its use
+        static_assert(CB == 6, "three tiles ahead");
+        __builtin_amdgcn_sched_barrier(0);
+        split8(ca[0][0], ca[0][1], ah[0], am[0], al[0]);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+          tile(0, j);
+          read_w(j + 3, j + 4);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll
+        for (int j = 3; j < CB; ++j) tile(0, j);
+      } else {
+        // all 20 reads before the split: at two workgroups per CU the wave has the registers for all of W (96 accumulators + 72
+        // + the split's)
+        split8(ca[0][0], ca[0][1], ah[0], am[0], al[0]);
+        __builtin_amdgcn_sched_group_barrier(0x100, 2 + 3 * CB, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, 40, 0);
+        products(0);
+      }
+    } else {
+      static_assert(!LEAN, "LEAN is a schedule of the row-owning tiling");
+      split8(ca[0][0], ca[0][1], ah[0], am[0], al[0]);
+      // the split of the second row block (44 VALU instructions) goes into the issue gaps of the first block's 18 MFMAs
+      __builtin_amdgcn_sched_barrier(0);
+      products(0);
+      split8(ca[1][0], ca[1][1], ah[1], am[1], al[1]);
+#pragma unroll
+      for (int g = 0; g < 18; ++g) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      products(1);
     }
-    __builtin_amdgcn_sched_barrier(0);
-    products(1);
   }
   __syncthreads();
 }

@@ -1,7 +1,9 @@
-"""The layouts of the exact-split fp32 GEMMs (the image written in csrc/gemm_f32_split.hip, the LDS stage of split_main_loop
-<2, 2, 3> in csrc/split_f32.h, its fp32 A part that of csrc/gemm_f32_dma_loop.h), stated in plain Python: the weight image written by
-pangu_split_weight_bf16x3, and the LDS stage the kernel reads its MFMA fragments from.  No torch, no GPU: the tests un-permute an
-image and check the bank behaviour of the fragment reads with these."""
+"""The layouts of the exact-split fp32 GEMMs (the image written in csrc/gemm_f32_split.hip, the LDS stage of split_main_loop in
+csrc/split_f32.h, its fp32 A part that of csrc/gemm_f32_dma_loop.h), stated in plain Python: the weight image written by
+pangu_split_weight_bf16x3, and the LDS stage the kernel reads its MFMA fragments from, under both wave tilings of the loop: 2 x 2
+waves of 64 x 96 (a_fragment_address, w_fragment_address: gemm_ln_f32_split.hip at N = 192) and row-owning waves of 32 x 192
+(a_row_fragment_address, w_row_fragment_address: gemm_f32_split.hip, gemm_ln_f32_split.hip at N = 384 from K = 1536).  No torch, no GPU: the
+tests un-permute an image and check the bank behaviour of the fragment reads with these."""
 
 BM, BN, BK = 128, 192, 16
 A_BYTES = BM * 64                 # the fp32 A image of a stage: 128 rows of 64 B (16 floats), 16-B chunks XOR-swizzled
@@ -43,6 +45,19 @@ def w_fragment_address(lane, wn, j, plane):
     """The ds_read_b128 of the lane for column block j (0..2) of wave column wn (0, 1): the 8 bf16 k = 8 lh .. 8 lh + 7 of `plane`
     of tile row 96 wn + 32 j + lr."""
     return A_BYTES + plane * PLANE + ((lane >> 5) * BN + wn * 96 + j * 32 + (lane & 31)) * 16
+
+
+def a_row_fragment_address(lane, wm, h):
+    """Row-owning wave tiling (SplitTile<.., ROWS = true>): the ds_read_b128 of the lane for the ONE 32-row block of wave row wm
+    (0..3 in the 128-row tile, 0..1 in the 64-row tile): half h of its 8 consecutive k of row 32 wm + lr."""
+    return a_chunk_offset(wm * 32 + (lane & 31), 2 * (lane >> 5) + h)
+
+
+def w_row_fragment_address(lane, wn, j, plane, a_bytes=A_BYTES):
+    """Row-owning wave tiling: the ds_read_b128 of the lane for column tile j (0..5) of wave column wn, whose columns are the
+    whole n-tile block wn of the stage (wn = 0 in the 128 x 192 tile; 0, 1 in the 64 x 384 tile, a_bytes = 64 * 64): the 8 bf16
+    k = 8 lh .. 8 lh + 7 of `plane` of block row 32 j + lr."""
+    return a_bytes + wn * B_BYTES + plane * PLANE + ((lane >> 5) * BN + j * 32 + (lane & 31)) * 16
 
 
 def dma_piece_destination(q, lane):
