@@ -206,15 +206,15 @@ __global__ __launch_bounds__(192 * G) void window_attn_qkv_walk_bf16_kernel(cons
     bf16x8 qf[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-      qf[i] = __builtin_bit_cast(bf16x8, u32x4{pack2(acc[0][i][0], acc[0][i][1]), pack2(acc[0][i][2], acc[0][i][3]),
-                                               pack2(acc[1][i][0], acc[1][i][1]), pack2(acc[1][i][2], acc[1][i][3])});
+      qf[i] = __builtin_bit_cast(bf16x8, u32x4{pack_bf16x2(acc[0][i][0], acc[0][i][1]), pack_bf16x2(acc[0][i][2], acc[0][i][3]),
+                                               pack_bf16x2(acc[1][i][0], acc[1][i][1]), pack_bf16x2(acc[1][i][2], acc[1][i][3])});
       const int n = (tile0 + i) * 16 + lq;
-      *reinterpret_cast<u32x4*>(Ks + kswz(n, lg)) = u32x4{pack2(acc[2][i][0], acc[2][i][1]), pack2(acc[2][i][2], acc[2][i][3]),
-                                                          pack2(acc[3][i][0], acc[3][i][1]), pack2(acc[3][i][2], acc[3][i][3])};
+      *reinterpret_cast<u32x4*>(Ks + kswz(n, lg)) = u32x4{pack_bf16x2(acc[2][i][0], acc[2][i][1]), pack_bf16x2(acc[2][i][2], acc[2][i][3]),
+                                                          pack_bf16x2(acc[3][i][0], acc[3][i][1]), pack_bf16x2(acc[3][i][2], acc[3][i][3])};
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt)
         *reinterpret_cast<u32x2*>(Vt + vt_off<true>(dt * 16 + lq, (tile0 + i) * 16 + 4 * lg)) =
-            u32x2{pack2(acc[4 + dt][i][0], acc[4 + dt][i][1]), pack2(acc[4 + dt][i][2], acc[4 + dt][i][3])};
+            u32x2{pack_bf16x2(acc[4 + dt][i][0], acc[4 + dt][i][1]), pack_bf16x2(acc[4 + dt][i][2], acc[4 + dt][i][3])};
     }
     pipe_rendezvous(ctr, target, lane);
     if (BIAS) {

@@ -28,7 +28,6 @@ constexpr int SLAB = 32 * 128;            // bytes
 constexpr int STAGE_SLABS = 6;
 constexpr int STAGE = STAGE_SLABS * SLAB; // 24 576 B
 constexpr int RING = 4;
-constexpr float LN_EPS = 1e-5f;
 // timing-only ablations (tools/ablate_mlp_f32.sh builds them into scratch/; never in the shipped library)
 #ifndef MLP_PIN
 #define MLP_PIN 1          // scheduling barrier after every MFMA gap
@@ -42,9 +41,6 @@ constexpr float LN_EPS = 1e-5f;
 #ifndef MLP_DUAL
 #define MLP_DUAL 0         // 1: the first product alternates two accumulators (independent MFMA chains), summed per chunk
 #endif
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 template <int C>
 __global__ __launch_bounds__(256) void mlp_ln_residual_f32_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ w1,

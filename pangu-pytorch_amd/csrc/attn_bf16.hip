@@ -129,14 +129,6 @@ __global__ __launch_bounds__(192, 3) void window_attn_bf16_kernel(const u16* __r
 constexpr int QK_ROWS = PANGU_WTOK + 96;                 // rows of one ring slot: 144 x rows, then q/k/v weight rows
 constexpr int QK_SLOT = QK_ROWS * 64;                    // slot bytes at 32 channels per K-step (BK = 64: twice that)
 
-__device__ inline int kswz64(int row, int chunk) {      // 64-byte rows, 4 chunks: F = {0,2,3,1}[(row>>2)&3]
-  const int f = (0x78 >> (((row >> 2) & 3) * 2)) & 3;
-  return row * 64 + ((chunk ^ f) << 4);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
 // win_src_token (common.h) with the window type already split into (zwin, hwin): the split is a runtime division of a
 // workgroup-uniform value that the compiler would redo on the vector ALU for each of the kernel's eight token lookups.
 __device__ inline void split_type(const WinGeom& g, int t, int& zwin, int& hwin) {
@@ -300,15 +292,15 @@ __global__ __launch_bounds__(192, 2) void window_attn_qkv_bf16_kernel(const u16*
   bf16x8 qf[3];
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
-    qf[i] = __builtin_bit_cast(bf16x8, u32x4{pack2(acc[0][i][0], acc[0][i][1]), pack2(acc[0][i][2], acc[0][i][3]),
-                                             pack2(acc[1][i][0], acc[1][i][1]), pack2(acc[1][i][2], acc[1][i][3])});
+    qf[i] = __builtin_bit_cast(bf16x8, u32x4{pack_bf16x2(acc[0][i][0], acc[0][i][1]), pack_bf16x2(acc[0][i][2], acc[0][i][3]),
+                                             pack_bf16x2(acc[1][i][0], acc[1][i][1]), pack_bf16x2(acc[1][i][2], acc[1][i][3])});
     const int n = (tile0 + i) * 16 + lq;
-    *reinterpret_cast<u32x4*>(Ks + kswz(n, lg)) = u32x4{pack2(acc[2][i][0], acc[2][i][1]), pack2(acc[2][i][2], acc[2][i][3]),
-                                                        pack2(acc[3][i][0], acc[3][i][1]), pack2(acc[3][i][2], acc[3][i][3])};
+    *reinterpret_cast<u32x4*>(Ks + kswz(n, lg)) = u32x4{pack_bf16x2(acc[2][i][0], acc[2][i][1]), pack_bf16x2(acc[2][i][2], acc[2][i][3]),
+                                                        pack_bf16x2(acc[3][i][0], acc[3][i][1]), pack_bf16x2(acc[3][i][2], acc[3][i][3])};
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt)
       *reinterpret_cast<u32x2*>(Vt + vt_off<true>(dt * 16 + lq, (tile0 + i) * 16 + 4 * lg)) =
-          u32x2{pack2(acc[4 + dt][i][0], acc[4 + dt][i][1]), pack2(acc[4 + dt][i][2], acc[4 + dt][i][3])};
+          u32x2{pack_bf16x2(acc[4 + dt][i][0], acc[4 + dt][i][1]), pack_bf16x2(acc[4 + dt][i][2], acc[4 + dt][i][3])};
   }
 
   bool zcut = false, hcut = false;

@@ -28,8 +28,6 @@ __device__ inline int vt_off(int d, int key) {
 constexpr int VT_BYTES_PAD = 32 * 336, VT_BYTES_SWZ = 32 * 384;
 static_assert(PANGU_WTOK * 64 + VT_BYTES_SWZ <= 2 * (PANGU_WTOK + 96) * 64, "the K + V^T images reuse the ring of the fused kernel");
 
-__device__ inline u16 f2bf(float f) { return __builtin_bit_cast(u16, (__bf16)f); }
-__device__ inline unsigned pack2(float a, float b) { return pack_bf16x2(a, b); }
 __device__ inline float bflo(unsigned u) { return __builtin_bit_cast(float, u << 16); }
 __device__ inline float bfhi(unsigned u) { return __builtin_bit_cast(float, u & 0xFFFF0000u); }
 
@@ -157,11 +155,11 @@ __device__ __forceinline__ void attn_tile(const unsigned char* Ks, const unsigne
 #pragma unroll
   for (int u = 0; u < 5; ++u) {
     u32x4 pb;
-    pb[0] = pack2(s[2 * u][0], s[2 * u][1]);
-    pb[1] = pack2(s[2 * u][2], s[2 * u][3]);
+    pb[0] = pack_bf16x2(s[2 * u][0], s[2 * u][1]);
+    pb[1] = pack_bf16x2(s[2 * u][2], s[2 * u][3]);
     if (u < 4) {
-      pb[2] = pack2(s[2 * u + 1][0], s[2 * u + 1][1]);
-      pb[3] = pack2(s[2 * u + 1][2], s[2 * u + 1][3]);
+      pb[2] = pack_bf16x2(s[2 * u + 1][0], s[2 * u + 1][1]);
+      pb[3] = pack_bf16x2(s[2 * u + 1][2], s[2 * u + 1][3]);
     } else {
       pb[2] = 0u; pb[3] = 0u;
     }
@@ -188,8 +186,8 @@ __device__ __forceinline__ void attn_tile(const unsigned char* Ks, const unsigne
   // consecutive d -- rows 0..3: d = 0, 16, 8, 24 .. +7 -- and the row leaves as ONE 16-B store per lane instead of two 8-B stores
   // (half the store instructions, whole 64-B segments per instruction: the epilogue is store-issue-bound, not byte-bound)
   const float inv = 1.0f / sum;
-  const auto r0 = __builtin_amdgcn_permlane16_swap(pack2(o0[0] * inv, o0[1] * inv), pack2(o1[0] * inv, o1[1] * inv), false, false);
-  const auto r1 = __builtin_amdgcn_permlane16_swap(pack2(o0[2] * inv, o0[3] * inv), pack2(o1[2] * inv, o1[3] * inv), false, false);
+  const auto r0 = __builtin_amdgcn_permlane16_swap(pack_bf16x2(o0[0] * inv, o0[1] * inv), pack_bf16x2(o1[0] * inv, o1[1] * inv), false, false);
+  const auto r1 = __builtin_amdgcn_permlane16_swap(pack_bf16x2(o0[2] * inv, o0[3] * inv), pack_bf16x2(o1[2] * inv, o1[3] * inv), false, false);
   if (qtok >= 0) {
     u16* dst = out + (size_t)qtok * C + hd * 32 + ((lg & 1) << 4) + ((lg >> 1) << 3);
     *reinterpret_cast<u32x4*>(dst) = u32x4{r0[0], r1[0], r0[1], r1[1]};

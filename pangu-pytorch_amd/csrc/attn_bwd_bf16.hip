@@ -15,14 +15,12 @@ typedef unsigned short u16;
 constexpr int NW = 9, NT = NW * 64;
 constexpr int ROWIMG = PANGU_WTOK * 64;        // bytes of a row-major [144][32] bf16 image
 
-__device__ inline u16 f2bf(float f) { return __builtin_bit_cast(u16, (__bf16)f); }
-__device__ inline unsigned pack2(float a, float b) { return pack_bf16x2(a, b); }
 
 // x0 / x1: this lane's four values of d = 4lg.. / 16 + 4lg.. of one token -> the 16-B piece d = {0, 16, 8, 24}[lg] .. +7 of that token
 // (all 64 lanes must be active: the swap exchanges whole 16-lane rows)
 __device__ inline u32x4 wide16(const f32x4 x0, const f32x4 x1) {
-  const auto r0 = __builtin_amdgcn_permlane16_swap(pack2(x0[0], x0[1]), pack2(x1[0], x1[1]), false, false);
-  const auto r1 = __builtin_amdgcn_permlane16_swap(pack2(x0[2], x0[3]), pack2(x1[2], x1[3]), false, false);
+  const auto r0 = __builtin_amdgcn_permlane16_swap(pack_bf16x2(x0[0], x0[1]), pack_bf16x2(x1[0], x1[1]), false, false);
+  const auto r1 = __builtin_amdgcn_permlane16_swap(pack_bf16x2(x0[2], x0[3]), pack_bf16x2(x1[2], x1[3]), false, false);
   return u32x4{r0[0], r1[0], r0[1], r1[1]};
 }
 __device__ inline float bflo(unsigned u) { return __builtin_bit_cast(float, u << 16); }
@@ -33,7 +31,7 @@ __device__ inline int kswz(int row, int chunk) {
   return row * 64 + ((chunk ^ f) << 4);
 }
 __device__ inline bf16x8 pack8(const f32x4& a, const f32x4& b) {
-  return __builtin_bit_cast(bf16x8, u32x4{pack2(a[0], a[1]), pack2(a[2], a[3]), pack2(b[0], b[1]), pack2(b[2], b[3])});
+  return __builtin_bit_cast(bf16x8, u32x4{pack_bf16x2(a[0], a[1]), pack_bf16x2(a[2], a[3]), pack_bf16x2(b[0], b[1]), pack_bf16x2(b[2], b[3])});
 }
 // ===================================================================================================================
 // v2 (round 2): ONE score orientation.  Wave w owns KEY tile w in phase 1: S = Q K^T and dP = dO V^T with the key on
@@ -244,8 +242,8 @@ __global__ __launch_bounds__(NT) void window_attn_bwd2_bf16_kernel(
             }
             if (i < DB2_REG) dbias[i < DB2_REG ? i : 0] += ds;
             else *ldsp<f32x4>(b_db + (i - DB2_REG) * NT * 16) += ds;
-            ppk[h] = u32x2{pack2(p[0], p[1]), pack2(p[2], p[3])};
-            dsk[h] = u32x2{pack2(ds[0], ds[1]), pack2(ds[2], ds[3])};
+            ppk[h] = u32x2{pack_bf16x2(p[0], p[1]), pack_bf16x2(p[2], p[3])};
+            dsk[h] = u32x2{pack_bf16x2(ds[0], ds[1]), pack_bf16x2(ds[2], ds[3])};
             *ldsp<u32x2>(b_kqds + 32 * i) = dsk[h];
           }
         }

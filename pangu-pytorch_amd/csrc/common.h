@@ -7,6 +7,22 @@
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned short u16;                                        // a bf16 as raw bits
+typedef short bf16x8 __attribute__((ext_vector_type(8)));          // one bf16 MFMA operand fragment (16 B)
+
+constexpr float LN_EPS = 1e-5f;      // every LayerNorm of the model (nn.LayerNorm's default)
+
+// byte offset of logical 16-B chunk `chunk` of row `row` in an LDS image of 64-byte rows (4 chunks: 32 bf16 or 16 fp32 of one
+// K-step): chunk XOR F[(row>>2)&3], F = {0,2,3,1} -- conflict-free for the ds_read_b128 lane groups of the MFMA fragment reads
+__device__ inline int kswz64(int row, int chunk) {
+  const int f = (0x78 >> (((row >> 2) & 3) * 2)) & 3;
+  return row * 64 + ((chunk ^ f) << 4);
+}
+
+// counted wait on the in-order vector-memory queue: at most N of this wave's requests still in flight
+template <int N>
+__device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 #define PANGU_WZ 2
 #define PANGU_WH 6

@@ -10,23 +10,14 @@
 //   LDS image: [row][64 bf16] (128-B rows), 16-B chunk index XOR-swizzled with (row>>1)&7: conflict-free for the
 //   ds_read_b128 lane groups (each group holds 16 distinct rows with chunks c / c^1) and for the staging writes.
 //   Staging: global_load_dwordx4 -> registers -> ds_write_b128 one K-step ahead (double-buffered LDS).
-#include "common.h"
+// The register-staged main loop, the K-step, the DMA issue and the leaf helpers are in gemm_bf16_loop.h, shared with gemm_ln_bf16.hip.
+#include "gemm_bf16_loop.h"
 
 namespace {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+using namespace pangu_bf16;
 
 constexpr int BBM = 128;
-constexpr int BBK = 64;
-
-__device__ inline u16 f2bf(float f) {   // round-to-nearest-even, NaN-preserving via the hardware convert
-  return __builtin_bit_cast(u16, (__bf16)f);
-}
-__device__ inline unsigned pack2(float a, float b) { return pack_bf16x2(a, b); }
-
-__device__ inline int swz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }   // byte offset
 
 template <int TN, int ACT, bool HAS_BIAS, bool OUT_F32>
 __device__ __forceinline__ void bf16_epilogue(f32x4 (&acc)[4][2 * TN], unsigned char* smem, const float* __restrict__ bias,
@@ -75,6 +66,8 @@ __device__ __forceinline__ void bf16_epilogue(f32x4 (&acc)[4][2 * TN], unsigned 
       aux2, 0, ACT == PANGU_ACT_GELU_BWD_H ? (int)((size_t)M * N * sizeof(u16)) : 0, 0x00020000);
   if (ACT == PANGU_ACT_GELU_BWD || ACT == PANGU_ACT_GELU_BWD_H || ACT == PANGU_ACT_ADD) {
     // stage the saved pre-activation (or addend) patch first (coalesced 16-B loads), so gelu' can be applied in the MFMA layout
+    // (in place, not patch_stage_rows / patch_store_rows of gemm_bf16_loop.h: behind a helper the compiler waits for this patch's loads in
+    // two batches of four instead of one of eight and linear_gelu_bwd measured +2.8 / +5.5 %: profiles/gemm_bf16_shared_speed.md)
 #pragma unroll
     for (int it = 0; it < CPR; ++it) {
       const int f = lane + 64 * it, row = f / CPR, ch = f - row * CPR;
@@ -101,17 +94,13 @@ __device__ __forceinline__ void bf16_epilogue(f32x4 (&acc)[4][2 * TN], unsigned 
       f32x4 v = acc[i][j] + bv[j];
       unsigned char* slot = ep + (i * 16 + lc) * EP_LD + (j * 16 + lg * 4) * 2;
       if (ACT == PANGU_ACT_GELU_BWD) {
-        const u32x2 xp = *reinterpret_cast<const u32x2*>(slot);
-        v[0] *= gelu_erf_grad_lp(__builtin_bit_cast(float, xp[0] << 16));
-        v[1] *= gelu_erf_grad_lp(__builtin_bit_cast(float, xp[0] & 0xFFFF0000u));
-        v[2] *= gelu_erf_grad_lp(__builtin_bit_cast(float, xp[1] << 16));
-        v[3] *= gelu_erf_grad_lp(__builtin_bit_cast(float, xp[1] & 0xFFFF0000u));
+        const f32x4 x = unpack_bf16x4(*reinterpret_cast<const u32x2*>(slot));
+#pragma unroll
+        for (int c = 0; c < 4; ++c) v[c] *= gelu_erf_grad_lp(x[c]);
       }
       if (ACT == PANGU_ACT_GELU_BWD_H) {
         // gelu'(x) = Phi(x) + x phi(x) and h = gelu(x) = x Phi(x) share Phi
-        const u32x2 xp = *reinterpret_cast<const u32x2*>(slot);
-        const f32x4 x = {__builtin_bit_cast(float, xp[0] << 16), __builtin_bit_cast(float, xp[0] & 0xFFFF0000u),
-                         __builtin_bit_cast(float, xp[1] << 16), __builtin_bit_cast(float, xp[1] & 0xFFFF0000u)};
+        const f32x4 x = unpack_bf16x4(*reinterpret_cast<const u32x2*>(slot));
         f32x4 hh;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
@@ -119,23 +108,17 @@ __device__ __forceinline__ void bf16_epilogue(f32x4 (&acc)[4][2 * TN], unsigned 
           hh[c] = x[c] * phi_c;
           v[c] *= phi_c + x[c] * 0.3989422804014327f * __expf(-0.5f * x[c] * x[c]);
         }
-        hp[j] = u32x2{pack2(hh[0], hh[1]), pack2(hh[2], hh[3])};
+        hp[j] = pack_bf16x4(hh);
       }
-      if (ACT == PANGU_ACT_ADD) {
-        const u32x2 xp = *reinterpret_cast<const u32x2*>(slot);
-        v[0] += __builtin_bit_cast(float, xp[0] << 16);
-        v[1] += __builtin_bit_cast(float, xp[0] & 0xFFFF0000u);
-        v[2] += __builtin_bit_cast(float, xp[1] << 16);
-        v[3] += __builtin_bit_cast(float, xp[1] & 0xFFFF0000u);
-      }
+      if (ACT == PANGU_ACT_ADD) v += unpack_bf16x4(*reinterpret_cast<const u32x2*>(slot));
       if (ACT == PANGU_ACT_GELU) {
         if (aux) {                                          // pre-activation out (rounded to bf16, as it will be re-read)
           const unsigned xo = col < N ? ((unsigned)(wave_m0 + i * 16 + lc) * (unsigned)N + (unsigned)col) * 2u : 0xFFFFFFFFu;
-          __builtin_amdgcn_raw_buffer_store_b64(u32x2{pack2(v[0], v[1]), pack2(v[2], v[3])}, x_rsrc, (int)xo, 0, 0);
+          __builtin_amdgcn_raw_buffer_store_b64(pack_bf16x4(v), x_rsrc, (int)xo, 0, 0);
         }
         v = gelu_erf_lp4(v);
       }
-      *reinterpret_cast<u32x2*>(slot) = u32x2{pack2(v[0], v[1]), pack2(v[2], v[3])};
+      *reinterpret_cast<u32x2*>(slot) = pack_bf16x4(v);
     }
     // read back rows 16i .. 16i+15 of the patch: 16 * CPR chunks of 16 B
 #pragma unroll
@@ -155,6 +138,7 @@ __device__ __forceinline__ void bf16_epilogue(f32x4 (&acc)[4][2 * TN], unsigned 
 #pragma unroll
       for (int j = 0; j < 2 * TN; ++j)
         *reinterpret_cast<u32x2*>(ep + (i * 16 + lc) * EP_LD + (j * 16 + lg * 4) * 2) = hp[j];
+      // (in place like the store of C above: behind patch_store_rows this path came out 27 instructions longer)
 #pragma unroll
       for (int it = 0; it < (16 * CPR + 63) / 64; ++it) {
         const int f = lane + 64 * it;
@@ -176,7 +160,6 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_bf16_kernel(const u16* __restr
                                                               void* __restrict__ Cv, int ldc, int M, int N, int K,
                                                               int m_tiles, int n_tiles, u16* __restrict__ aux, u16* __restrict__ aux2) {
   constexpr int BN = 64 * TN;
-  constexpr int STAGE = (BBM + BN) * 128;                 // bytes per LDS stage
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
   const int b = blockIdx.x;
@@ -187,98 +170,25 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_bf16_kernel(const u16* __restr
   const int m0 = m_tile * BBM, n0 = n_tile * BN;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
   const int lc = lane & 15, lg = lane >> 4;
 
-  // staging: (BBM + BN) rows x 8 chunks of 16 B; chunk id f = tid + 256*i -> row f>>3, chunk f&7
-  constexpr int NCH = (BBM + BN) * 8 / 256;               // 4 + 2*TN chunks per thread
-  const u16* src[NCH];
-  int dst[NCH];
-  const int kchunk = tid & 7;
-#pragma unroll
-  for (int i = 0; i < NCH; ++i) {
-    const int row = (tid >> 3) + 32 * i;                   // 0 .. BBM+BN-1
-    if (row < BBM) {
-      int r = m0 + row;
-      r = r < M ? r : M - 1;
-      src[i] = A + (size_t)r * lda + kchunk * 8;
-    } else {
-      int r = n0 + row - BBM;
-      r = r < N ? r : N - 1;
-      src[i] = W + (size_t)r * K + kchunk * 8;
-    }
-    dst[i] = (row < BBM ? swz(row, kchunk) : BBM * 128 + swz(row - BBM, kchunk));
-  }
-  const int KT = (K + BBK - 1) / BBK;
-  u32x4 stg[NCH];
-  auto fetch = [&](int kt) {
-    const bool in = kt * BBK + kchunk * 8 < K;             // K % 8 == 0: a chunk is entirely inside or outside
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-      stg[i] = in ? *reinterpret_cast<const u32x4*>(src[i] + (size_t)kt * BBK) : u32x4{0u, 0u, 0u, 0u};
-    }
-  };
-  auto stash = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) *reinterpret_cast<u32x4*>(smem + buf * STAGE + dst[i]) = stg[i];
-  };
-
   f32x4 acc[4][2 * TN];                                    // [m tile 16][n tile 16], lane: 4 consecutive n of row m=lc
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2 * TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  fetch(0);
-  stash(0);
-  __syncthreads();
-  for (int kt = 0; kt < KT; ++kt) {
-    const bool more = kt + 1 < KT;
-    if (more) fetch(kt + 1);
-    const unsigned char* As = smem + (kt & 1) * STAGE;
-    const unsigned char* Ws = As + BBM * 128;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      bf16x8 fa[4], fw[2 * TN];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        fa[i] = *reinterpret_cast<const bf16x8*>(As + swz(wm * 64 + i * 16 + lc, kk * 4 + lg));
-#pragma unroll
-      for (int j = 0; j < 2 * TN; ++j)
-        fw[j] = *reinterpret_cast<const bf16x8*>(Ws + swz(wn * 32 * TN + j * 16 + lc, kk * 4 + lg));
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2 * TN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[j], fa[i], acc[i][j], 0, 0, 0);   // D[n][m]
-    }
-    if (more) stash((kt + 1) & 1);
-    __syncthreads();
-  }
+  bf16_staged_main_loop<2, 2 * TN>(smem, A, lda, W, M, N, K, m0, n0, tid, wave, lc, lg, acc);
   bf16_epilogue<TN, ACT, HAS_BIAS, OUT_F32>(acc, smem, bias, Cv, ldc, M, N, aux, m0, n0, wave, lane, aux2);
 }
 
 // ---- direct-to-LDS variant -------------------------------------------------------------------------------------------
 // Same tile and fragment scheme, but the operands travel HBM/L2 -> LDS with buffer_load_dwordx4 ... lds (no staging VGPRs,
-// no ds_write pass), BK = 32 and a FOUR-stage LDS ring (4 x 20 KB, still two workgroups per CU): loads run three K-steps
-// ahead of the MFMAs behind counted s_waitcnt vmcnt(N) and ONE raw s_barrier per step.  An LDS-DMA wave-instruction
-// writes 1 KB linearly (16 rows x 64 B), so the bank swizzle is applied on the SOURCE side: the lane that fills
-// physical chunk p of row r fetches logical chunk p ^ F(r).  Rows >= M / >= N fall outside the descriptor's range
-// and arrive as zeros.
+// no ds_write pass; addressing and source-side swizzle: gemm_bf16_loop.h), BK = 32 and a ring of TWO slots (40 KB ring, 53 KB
+// with the epilogue patches: THREE workgroups per CU at <= 168 VGPRs -- there are no staging registers), loads one K-step
+// ahead of the MFMAs behind s_waitcnt vmcnt(0) and ONE raw s_barrier per step.  Rows >= M / >= N fall outside the
+// descriptor's range and arrive as zeros.
+// (A ring of FOUR slots -- 4 x 20 KB, two workgroups per CU, loads three K-steps ahead behind counted vmcnt(LPS), vmcnt(2 LPS) --
+// measured equal to register staging everywhere: removed, and the ring-depth template parameter with it.)
 constexpr int GBK = 32;
 
-__device__ inline int kswz64(int row, int chunk) {      // 64-byte rows, 4 chunks: F = {0,2,3,1}[(row>>2)&3]
-  const int f = (0x78 >> (((row >> 2) & 3) * 2)) & 3;
-  return row * 64 + ((chunk ^ f) << 4);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-// RING = LDS ring depth: 4 (80 KB, two workgroups per CU, loads three K-steps ahead) or 2 (40 KB ring, 53 KB with the
-// epilogue patches: THREE workgroups per CU at <= 168 VGPRs -- there are no staging registers -- loads one K-step ahead)
-template <int TN, int ACT, bool HAS_BIAS, bool OUT_F32, int RING>
-__global__ __launch_bounds__(256, RING == 2 ? 3 : 2) void gemm_tn_bf16_glds_kernel(const u16* __restrict__ A, int lda,
+template <int TN, int ACT, bool HAS_BIAS, bool OUT_F32>
+__global__ __launch_bounds__(256, 3) void gemm_tn_bf16_glds_kernel(const u16* __restrict__ A, int lda,
                                                                    const u16* __restrict__ W, const float* __restrict__ bias,
                                                                    void* __restrict__ Cv, int ldc, int M, int N, int K,
                                                                    int m_tiles, int n_tiles, u16* __restrict__ aux, u16* __restrict__ aux2) {
@@ -306,23 +216,14 @@ __global__ __launch_bounds__(256, RING == 2 ? 3 : 2) void gemm_tn_bf16_glds_kern
   // instruction q = i*4 + wave (i < LPS) fills rows 16q .. 16q+15; this lane fills (row 16q + lane>>2, chunk lane&3)
   unsigned voff[LPS];
 #pragma unroll
-  for (int i = 0; i < LPS; ++i) {
+  for (int i = 0; i < LPS; ++i) {      // = bf16_dma_offset<4, BBM, GBK>, in place: the helper moves the epilogue's waits (see bf16_epilogue)
     const int row = 16 * (i * 4 + wave) + (lane >> 2);
     const int f = (0x78 >> (((row >> 2) & 3) * 2)) & 3;
     const int c = (lane & 3) ^ f;                           // logical chunk this physical slot must receive
     voff[i] = row < BBM ? ((unsigned)(m0 + row) * (unsigned)lda + c * 8) * 2u
                         : ((unsigned)(n0 + row - BBM) * (unsigned)K + c * 8) * 2u;
   }
-  auto issue = [&](int kt) {
-    unsigned char* base = smem + (kt % RING) * STAGE;
-#pragma unroll
-    for (int i = 0; i < LPS; ++i) {
-      const int q = i * 4 + wave;
-      auto dst = (__attribute__((address_space(3))) void*)(base + q * 1024);
-      if (16 * q < BBM) __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, dst, 16, (int)voff[i], kt * GBK * 2, 0, 0);
-      else __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, dst, 16, (int)voff[i], kt * GBK * 2, 0, 0);
-    }
-  };
+  auto issue = [&](int kt) { bf16_dma_issue<LPS, 4, BBM, GBK>(smem + (kt & 1) * STAGE, a_rsrc, w_rsrc, voff, 0u, kt, wave); };
 
   f32x4 acc[4][2 * TN];
 #pragma unroll
@@ -330,30 +231,15 @@ __global__ __launch_bounds__(256, RING == 2 ? 3 : 2) void gemm_tn_bf16_glds_kern
 #pragma unroll
     for (int j = 0; j < 2 * TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const int KT = K / GBK;
-#pragma unroll
-  for (int s0 = 0; s0 < RING - 1; ++s0)
-    if (s0 < KT) issue(s0);
+  const int KT = K / GBK;                                  // >= 1: K > 0 (entry points) and K % GBK == 0 (launch_bf16)
+  issue(0);
   for (int kt = 0; kt < KT; ++kt) {
-    const int rem = KT - 1 - kt;                           // newer steps already in flight: min(rem, RING - 2)
-    if (RING >= 4 && rem >= 2) wait_vmcnt<2 * LPS>();
-    else if (RING >= 3 && rem >= 1) wait_vmcnt<LPS>();
-    else wait_vmcnt<0>();
-    __builtin_amdgcn_s_barrier();                          // step kt landed for every wave; slot (kt-1)%4 is free
+    wait_vmcnt<0>();                                       // this wave's part of step kt has landed
+    __builtin_amdgcn_s_barrier();                          // ... and every wave's; slot (kt+1)&1 is free
     asm volatile("" ::: "memory");
-    if (kt + RING - 1 < KT) issue(kt + RING - 1);
-    const unsigned char* As = smem + (kt % RING) * STAGE;
-    const unsigned char* Ws = As + BBM * 64;
-    bf16x8 fa[4], fw[2 * TN];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) fa[i] = *reinterpret_cast<const bf16x8*>(As + kswz64(wm * 64 + i * 16 + lc, lg));
-#pragma unroll
-    for (int j = 0; j < 2 * TN; ++j) fw[j] = *reinterpret_cast<const bf16x8*>(Ws + kswz64(wn * 32 * TN + j * 16 + lc, lg));
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 2 * TN; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[j], fa[i], acc[i][j], 0, 0, 0);
+    if (kt + 1 < KT) issue(kt + 1);
+    const unsigned char* As = smem + (kt & 1) * STAGE;
+    bf16_mfma_kstep<4, 2 * TN, GBK>(As, As + BBM * 64, wm * 64, wn * 32 * TN, lc, lg, acc);
   }
   __syncthreads();                                         // every wave is done with the ring before the epilogue reuses it
   bf16_epilogue<TN, ACT, HAS_BIAS, OUT_F32>(acc, smem, bias, Cv, ldc, M, N, aux, m0, n0, wave, lane, aux2);
@@ -377,7 +263,7 @@ int launch_bf16(hipStream_t s, const u16* A, int lda, const u16* W, const float*
 #define PANGU_BGEMM(ACT, HB)                                                                                          \
   do {                                                                                                                \
     if (glds) {                                                                                                       \
-      auto kern = gemm_tn_bf16_glds_kernel<TN, ACT, HB, OUT_F32, 2>;                                                  \
+      auto kern = gemm_tn_bf16_glds_kernel<TN, ACT, HB, OUT_F32>;                                                     \
       PANGU_ENSURE_DYN_LDS(kern, shm);                                                                                \
       hipLaunchKernelGGL(kern, g, blk, shm, s, A, lda, W, bias, C, ldc, M, N, K, m_tiles, n_tiles, aux, aux2);        \
       break;                                                                                                          \
@@ -406,7 +292,7 @@ int launch_bf16(hipStream_t s, const u16* A, int lda, const u16* W, const float*
 }  // namespace
 
 int pangu_linear_ws_bf16(hipStream_t s, const void* A, int lda, const void* W, const float* bias, void* C, int ldc, int M,
-                         int N, int K, int act, void* aux, int out_f32, void* aux2 = nullptr);      // gemm_ws_bf16.hip
+                         int N, int K, int act, void* aux, int out_f32);      // gemm_ws_bf16.hip
 
 extern "C" int pangu_linear_gelu_bwd_bf16(pangu_stream_t stream, const void* A, int lda, const void* W, void* dpre, int ldc,
                                           int M, int N, int K, const void* pre, void* h) {

@@ -8,12 +8,6 @@ namespace pangu_dma {
 constexpr int BM = 128;      // rows of the output tile: 2 wave rows of 64
 constexpr int BK = 16;       // floats per K-step = one 64-byte LDS row
 
-// byte offset of logical 16-B chunk `chunk` of row `row` (64-byte rows, chunk XOR F[(row>>2)&3], F = {0,2,3,1})
-__device__ inline int kswz64(int row, int chunk) {
-  const int f = (0x78 >> (((row >> 2) & 3) * 2)) & 3;
-  return row * 64 + ((chunk ^ f) << 4);
-}
-
 // 2 x WNW waves of 64 x 32 TN: a 128 x 32 TN WNW tile, a ring of two stages of (BM + BN) 64-byte rows
 template <int WNW, int TN>
 struct DmaTile {

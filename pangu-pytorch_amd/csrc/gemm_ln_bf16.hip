@@ -9,30 +9,21 @@
 // segments.  Saves the branch's HBM round trip (write y, read y, read shortcut, write out -> read shortcut, write out):
 // the standalone LN-residual kernel is HBM-bound at ~5 TB/s and was 12 % of the bf16 forward.
 // The statistics are taken on the fp32 accumulators, i.e. BEFORE the bf16 rounding the unfused path applies to y.
-#include "common.h"
+// The main loop / ring addressing (gemm_bf16_loop.h) and the LayerNorm pieces (ln_epilogue_bf16.h) are shared by the two kernels here.
+#include "ln_epilogue_bf16.h"
 
 namespace {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+using namespace pangu_bf16;
 
 constexpr int LBM = 128;
-constexpr int LBK = 64;
-constexpr float LN_EPS = 1e-5f;
-
-__device__ inline unsigned pack2(float a, float b) { return pack_bf16x2(a, b); }
-__device__ inline int swz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }   // byte offset
 
 template <int WNW>
 __global__ __launch_bounds__(128 * WNW, 2) void gemm_ln_residual_bf16_kernel(
     const u16* __restrict__ A, int lda, const u16* __restrict__ W, const float* __restrict__ bias,
     const u16* __restrict__ shortcut, const float* __restrict__ gamma, const float* __restrict__ beta, u16* __restrict__ out,
     int ldo, int M, int K) {
-  constexpr int NT = 128 * WNW;
   constexpr int BN = 96 * WNW;                             // = N
-  constexpr int STAGE = (LBM + BN) * 128;                  // bytes per LDS stage
-  constexpr int NCH = (LBM + BN) * 8 / NT;                 // 16-B chunks staged per thread and K-step
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
   const int m0 = blockIdx.x * LBM;
@@ -40,64 +31,8 @@ __global__ __launch_bounds__(128 * WNW, 2) void gemm_ln_residual_bf16_kernel(
   const int wm = wave / WNW, wn = wave % WNW;
   const int lc = lane & 15, lg = lane >> 4;
 
-  const u16* src[NCH];
-  int dst[NCH];
-  const int kchunk = tid & 7;
-#pragma unroll
-  for (int i = 0; i < NCH; ++i) {
-    const int row = (tid >> 3) + (NT / 8) * i;              // 0 .. LBM+BN-1
-    if (row < LBM) {
-      int r = m0 + row;
-      r = r < M ? r : M - 1;
-      src[i] = A + (size_t)r * lda + kchunk * 8;
-    } else {
-      src[i] = W + (size_t)(row - LBM) * K + kchunk * 8;
-    }
-    dst[i] = (row < LBM ? swz(row, kchunk) : LBM * 128 + swz(row - LBM, kchunk));
-  }
-  const int KT = (K + LBK - 1) / LBK;
-  u32x4 stg[NCH];
-  auto fetch = [&](int kt) {
-    const bool in = kt * LBK + kchunk * 8 < K;             // K % 8 == 0: a chunk is entirely inside or outside
-#pragma unroll
-    for (int i = 0; i < NCH; ++i)
-      stg[i] = in ? *reinterpret_cast<const u32x4*>(src[i] + (size_t)kt * LBK) : u32x4{0u, 0u, 0u, 0u};
-  };
-  auto stash = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) *reinterpret_cast<u32x4*>(smem + buf * STAGE + dst[i]) = stg[i];
-  };
-
   f32x4 acc[4][6];                                         // [m tile 16][n tile 16], lane: 4 consecutive n of row m = lc
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 6; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  fetch(0);
-  stash(0);
-  __syncthreads();
-  for (int kt = 0; kt < KT; ++kt) {
-    const bool more = kt + 1 < KT;
-    if (more) fetch(kt + 1);
-    const unsigned char* As = smem + (kt & 1) * STAGE;
-    const unsigned char* Ws = As + LBM * 128;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      bf16x8 fa[4], fw[6];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) fa[i] = *reinterpret_cast<const bf16x8*>(As + swz(wm * 64 + i * 16 + lc, kk * 4 + lg));
-#pragma unroll
-      for (int j = 0; j < 6; ++j) fw[j] = *reinterpret_cast<const bf16x8*>(Ws + swz(wn * 96 + j * 16 + lc, kk * 4 + lg));
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 6; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[j], fa[i], acc[i][j], 0, 0, 0);   // D[n][m]
-    }
-    if (more) stash((kt + 1) & 1);
-    __syncthreads();
-  }
+  bf16_staged_main_loop<WNW, 6>(smem, A, lda, W, M, BN, K, m0, 0, tid, wave, lc, lg, acc);      // N = BN: no W row is clamped
 
   // ---- epilogue.  lane (lg, lc) of tile (i, j) holds y[m = wm*64 + 16i + lc][n = wn*96 + 16j + 4lg + r], r = 0..3
   constexpr int EP_LD = 96 * 2 + 16;                       // bytes per patch row
@@ -110,12 +45,7 @@ __global__ __launch_bounds__(128 * WNW, 2) void gemm_ln_residual_bf16_kernel(
   const __amdgpu_buffer_rsrc_t s_rsrc = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<u16*>(shortcut), 0, (int)((size_t)M * BN * sizeof(u16)), 0x00020000);
   // shortcut patch [64][96] -> LDS (rows >= M arrive as zeros)
-#pragma unroll
-  for (int it = 0; it < CPR; ++it) {
-    const int f = lane + 64 * it, row = f / CPR, ch = f - row * CPR;
-    const unsigned off = ((unsigned)(wave_m0 + row) * (unsigned)BN + (unsigned)(wave_n0 + ch * 8)) * 2u;
-    *reinterpret_cast<u32x4*>(ep + row * EP_LD + ch * 16) = __builtin_amdgcn_raw_buffer_load_b128(s_rsrc, (int)off, 0, 0);
-  }
+  patch_stage_rows<CPR>(ep, s_rsrc, wave_m0, BN, wave_n0, lane);
   // y = acc + bias (kept in acc), per-row partial statistics of this wave's 96 columns
 #pragma unroll
   for (int j = 0; j < 6; ++j) {
@@ -123,26 +53,7 @@ __global__ __launch_bounds__(128 * WNW, 2) void gemm_ln_residual_bf16_kernel(
 #pragma unroll
     for (int i = 0; i < 4; ++i) acc[i][j] += bv;
   }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    float s = 0.f, q = 0.f;
-#pragma unroll
-    for (int j = 0; j < 6; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        s += acc[i][j][r];
-        q = fmaf(acc[i][j][r], acc[i][j][r], q);
-      }
-    s += __shfl_xor(s, 16, 64);
-    q += __shfl_xor(q, 16, 64);
-    s += __shfl_xor(s, 32, 64);
-    q += __shfl_xor(q, 32, 64);
-    if (lg == 0) {
-      float* st = stats + (((wm * WNW + wn) * 64) + i * 16 + lc) * 2;
-      st[0] = s;
-      st[1] = q;
-    }
-  }
+  ln_stats_partials<WNW>(acc, stats, wm, wn, lc, lg);
   __syncthreads();
   f32x4 gv[6], bt[6];
 #pragma unroll
@@ -150,38 +61,17 @@ __global__ __launch_bounds__(128 * WNW, 2) void gemm_ln_residual_bf16_kernel(
     gv[j] = *reinterpret_cast<const f32x4*>(gamma + wave_n0 + j * 16 + lg * 4);
     bt[j] = *reinterpret_cast<const f32x4*>(beta + wave_n0 + j * 16 + lg * 4);
   }
-  constexpr float INV_C = 1.0f / BN;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    float s = 0.f, q = 0.f;
-#pragma unroll
-    for (int w = 0; w < WNW; ++w) {
-      const float* st = stats + (((wm * WNW + w) * 64) + i * 16 + lc) * 2;
-      s += st[0];
-      q += st[1];
-    }
-    const float mean = s * INV_C;
-    const float rstd = rsqrtf(fmaxf(q * INV_C - mean * mean, 0.f) + LN_EPS);
+    float mean, rstd;
+    ln_row_stats<WNW>(stats, wm, i, lc, mean, rstd);
 #pragma unroll
     for (int j = 0; j < 6; ++j) {
-      unsigned char* slot = ep + (i * 16 + lc) * EP_LD + (j * 16 + lg * 4) * 2;
-      const u32x2 xp = *reinterpret_cast<const u32x2*>(slot);
-      f32x4 v = (acc[i][j] - mean) * rstd * gv[j] + bt[j];
-      v[0] += __builtin_bit_cast(float, xp[0] << 16);
-      v[1] += __builtin_bit_cast(float, xp[0] & 0xFFFF0000u);
-      v[2] += __builtin_bit_cast(float, xp[1] << 16);
-      v[3] += __builtin_bit_cast(float, xp[1] & 0xFFFF0000u);
-      *reinterpret_cast<u32x2*>(slot) = u32x2{pack2(v[0], v[1]), pack2(v[2], v[3])};
+      u32x2* slot = reinterpret_cast<u32x2*>(ep + (i * 16 + lc) * EP_LD + (j * 16 + lg * 4) * 2);
+      *slot = ln_residual_pack(acc[i][j], mean, rstd, gv[j], bt[j], *slot);
     }
     // read back rows 16i .. 16i+15 of the patch: 16 * 12 chunks of 16 B -> whole row segments
-#pragma unroll
-    for (int it = 0; it < 3; ++it) {
-      const int f = lane + 64 * it;
-      const int row = i * 16 + f / CPR, ch = f % CPR;
-      const u32x4 v = *reinterpret_cast<const u32x4*>(ep + row * EP_LD + ch * 16);
-      const unsigned off = ((unsigned)(wave_m0 + row) * (unsigned)ldo + (unsigned)(wave_n0 + ch * 8)) * 2u;
-      __builtin_amdgcn_raw_buffer_store_b128(v, o_rsrc, (int)off, 0, 2);
-    }
+    patch_store_rows<CPR, 2>(ep + i * 16 * EP_LD, o_rsrc, wave_m0 + i * 16, ldo, wave_n0, lane);
   }
 }
 
@@ -201,14 +91,6 @@ __global__ __launch_bounds__(128 * WNW, 2) void gemm_ln_residual_bf16_kernel(
 //     loads and 12 output stores per tile at known positions.
 // LDS: RING x (128 + N) x 64 B ring + 2 WNW x 3328 B patches + 4 KB statistics (N = 384, RING = 3: 127 KB, one 8-wave workgroup
 // per CU; N = 192, RING = 3: 75 KB, two 4-wave workgroups per CU).
-__device__ inline int kswz64(int row, int chunk) {      // 64-byte rows, 4 chunks: F = {0,2,3,1}[(row>>2)&3]
-  const int f = (0x78 >> (((row >> 2) & 3) * 2)) & 3;
-  return row * 64 + ((chunk ^ f) << 4);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
 // DBK = channels per K-step: 32 (64-byte ring rows, swizzle kswz64) or 64 (128-byte rows, swizzle swz: half the barriers, the second
 // half-step's fragment reads can overlap the first's MFMAs; ring of 2 only -- 2 x 64 KB at N = 384).
 // WM = wave rows of 64 tokens: the tile is 64 WM x N (2: 128 rows, the N = 384 form; 4: 256 rows x 192 columns -- one 8-wave workgroup
@@ -221,7 +103,6 @@ __global__ __launch_bounds__(64 * WM * WNW, 2) void gemm_ln_residual_bf16_dma_ke
   static_assert((DBK == 32 && RING == 3) || (DBK == 64 && RING == 2), "ring of three K-steps of 32, or two of 64");
   constexpr int ROWB = DBK * 2;                            // bytes per ring row
   constexpr int RPI = 1024 / ROWB;                         // ring rows per LDS-DMA instruction (1 KB)
-  constexpr int CH = DBK / 8;                              // 16-B chunks per ring row
   constexpr int NW = WM * WNW;                             // waves
   constexpr int TBM = 64 * WM;                             // token rows per tile
   constexpr int BN = 96 * WNW;                             // = N
@@ -255,30 +136,16 @@ __global__ __launch_bounds__(64 * WM * WNW, 2) void gemm_ln_residual_bf16_dma_ke
   const __amdgpu_buffer_rsrc_t s_rsrc = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<u16*>(shortcut), 0, (int)((size_t)M * BN * sizeof(u16)), 0x00020000);
 
-  // DMA instruction q = i * NW + wave fills ring rows RPI q .. RPI q + RPI - 1; this lane fills (row RPI q + lane / CH, physical
-  // chunk lane % CH) with the LOGICAL chunk (lane % CH) ^ F(row) (source-side swizzle).  Rows < 128: A (tile-relative; the tile's byte offset is added
-  // to the VECTOR offset at issue time -- the descriptor's range check sees vector + immediate offsets only, and rows >= M must
-  // arrive as zeros), rows >= 128: W.
+  // ring addressing (gemm_bf16_loop.h): rows < TBM are A, TILE-relative -- the tile's byte offset is added to the vector offset at
+  // issue time -- rows >= TBM are W
   unsigned voff[LPS];
 #pragma unroll
-  for (int i = 0; i < LPS; ++i) {
-    const int row = RPI * (i * NW + wave) + lane / CH;
-    const int f = DBK == 32 ? ((0x78 >> (((row >> 2) & 3) * 2)) & 3) : ((row >> 1) & 7);
-    const int c = (lane % CH) ^ f;
-    voff[i] = row < TBM ? ((unsigned)row * (unsigned)lda + c * 8) * 2u : ((unsigned)(row - TBM) * (unsigned)K + c * 8) * 2u;
-  }
+  for (int i = 0; i < LPS; ++i) voff[i] = bf16_dma_offset<NW, TBM, DBK>(i, wave, lane, 0, 0, lda, K);
   const int KT = K / DBK;
   // global step g = it * KT + kt of this workgroup's it-th tile
   auto issue = [&](int g, int tile, int kt) {
-    unsigned char* base = smem + (g % RING) * STAGE;
     const unsigned a_base = (unsigned)tile * (unsigned)(TBM * 2) * (unsigned)lda;      // < 2^32: checked by the launcher
-#pragma unroll
-    for (int i = 0; i < LPS; ++i) {
-      const int q = i * NW + wave;
-      auto dst = (__attribute__((address_space(3))) void*)(base + q * 1024);
-      if (RPI * q < TBM) __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, dst, 16, (int)(voff[i] + a_base), kt * DBK * 2, 0, 0);
-      else __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, dst, 16, (int)voff[i], kt * DBK * 2, 0, 0);
-    }
+    bf16_dma_issue<LPS, NW, TBM, DBK>(smem + (g % RING) * STAGE, a_rsrc, w_rsrc, voff, a_base, kt, wave);
   };
 
   for (int c = tid; c < BN; c += 64 * NW) {
@@ -335,33 +202,10 @@ __global__ __launch_bounds__(64 * WM * WNW, 2) void gemm_ln_residual_bf16_dma_ke
       if (kt == 0) {
         // shortcut patch [64 rows][96 columns] of this wave, 16-B chunks in the order the output rows leave in (rows >= M: zeros)
 #pragma unroll
-        for (int it = 0; it < NS; ++it) {
-          const int f = lane + 64 * it, row = f / CPR, ch = f - row * CPR;
-          const unsigned off = ((unsigned)(wave_m0 + row) * (unsigned)BN + (unsigned)(wave_n0 + ch * 8)) * 2u;
-          sc[it] = __builtin_amdgcn_raw_buffer_load_b128(s_rsrc, (int)off, 0, 0);
-        }
+        for (int it = 0; it < NS; ++it) sc[it] = patch_load_chunk<CPR>(s_rsrc, wave_m0, BN, wave_n0, lane, it);
       }
       const unsigned char* As = smem + (g % RING) * STAGE;
-      const unsigned char* Ws = As + TBM * ROWB;
-#pragma unroll
-      for (int kk = 0; kk < DBK / 32; ++kk) {
-        bf16x8 fa[4], fw[6];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int row = wm * 64 + i * 16 + lc;
-          fa[i] = *reinterpret_cast<const bf16x8*>(As + (DBK == 32 ? kswz64(row, lg) : swz(row, kk * 4 + lg)));
-        }
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-          const int row = wn * 96 + j * 16 + lc;
-          fw[j] = *reinterpret_cast<const bf16x8*>(Ws + (DBK == 32 ? kswz64(row, lg) : swz(row, kk * 4 + lg)));
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 6; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[j], fa[i], acc[i][j], 0, 0, 0);   // D[n][m]
-      }
+      bf16_mfma_kstep<4, 6, DBK>(As, As + TBM * ROWB, wm * 64, wn * 96, lc, lg, acc);
     }
     first = false;
 
@@ -369,45 +213,15 @@ __global__ __launch_bounds__(64 * WM * WNW, 2) void gemm_ln_residual_bf16_dma_ke
     // (the compiler guards each group's first use of the shortcut registers with vmcnt(9..11): in the in-order queue that is a
     // wait for the OLDEST of the next tile's operand requests from the third group on -- requests issued two K-steps and half an
     // epilogue earlier; forcing the registers "landed" inside the K-loop costs a full vmcnt(0) there instead, which is worse)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float s = 0.f, q = 0.f;
-#pragma unroll
-      for (int j = 0; j < 6; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          s += acc[i][j][r];
-          q = fmaf(acc[i][j][r], acc[i][j][r], q);
-        }
-      s += __shfl_xor(s, 16, 64);
-      q += __shfl_xor(q, 16, 64);
-      s += __shfl_xor(s, 32, 64);
-      q += __shfl_xor(q, 32, 64);
-      if (lg == 0) {
-        float* st = stats + (((wm * WNW + wn) * 64) + i * 16 + lc) * 2;
-        st[0] = s;
-        st[1] = q;
-      }
-    }
+    ln_stats_partials<WNW>(acc, stats, wm, wn, lc, lg);
     // (a raw barrier: __syncthreads() would also wait for the next tile's operand requests -- vmcnt(0); the statistics went
     // through LDS only, and the next tile's statistics are >= KT barriers away)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    constexpr float INV_C = 1.0f / BN;
     float mean_[4], rstd_[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float s = 0.f, q = 0.f;
-#pragma unroll
-      for (int w = 0; w < WNW; ++w) {
-        const float* st = stats + (((wm * WNW + w) * 64) + i * 16 + lc) * 2;
-        s += st[0];
-        q += st[1];
-      }
-      mean_[i] = s * INV_C;
-      rstd_[i] = rsqrtf(fmaxf(q * INV_C - mean_[i] * mean_[i], 0.f) + LN_EPS);
-    }
+    for (int i = 0; i < 4; ++i) ln_row_stats<WNW>(stats, wm, i, lc, mean_[i], rstd_[i]);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                              // the table is dead: the patches may overwrite it
     asm volatile("" ::: "memory");
@@ -422,24 +236,16 @@ __global__ __launch_bounds__(64 * WM * WNW, 2) void gemm_ln_residual_bf16_dma_ke
       }
 #pragma unroll
       for (int j = 0; j < 6; ++j) {
-        unsigned char* slot = ep + lc * EP_LD + (j * 16 + lg * 4) * 2;
-        const u32x2 xp = *reinterpret_cast<const u32x2*>(slot);
+        u32x2* slot = reinterpret_cast<u32x2*>(ep + lc * EP_LD + (j * 16 + lg * 4) * 2);
+        const u32x2 xp = *slot;
         const f32x4 gj = *reinterpret_cast<const f32x4*>(prm + BN + wave_n0 + j * 16 + lg * 4);
         const f32x4 bj = *reinterpret_cast<const f32x4*>(prm + 2 * BN + wave_n0 + j * 16 + lg * 4);
-        f32x4 v = (acc[i][j] - mean) * rstd * gj + bj;
-        v[0] += __builtin_bit_cast(float, xp[0] << 16);
-        v[1] += __builtin_bit_cast(float, xp[0] & 0xFFFF0000u);
-        v[2] += __builtin_bit_cast(float, xp[1] << 16);
-        v[3] += __builtin_bit_cast(float, xp[1] & 0xFFFF0000u);
-        *reinterpret_cast<u32x2*>(slot) = u32x2{pack2(v[0], v[1]), pack2(v[2], v[3])};
+        *slot = ln_residual_pack(acc[i][j], mean, rstd, gj, bj, xp);
       }
+      // (the chunk helper in a loop of this kernel's own: with the loop inside a helper -- patch_store_rows -- the compiler allocates
+      // 6 more registers, and <2, 2, 64, 4> spills three of them inside the K-loop: profiles/gemm_bf16_shared_resources.md)
 #pragma unroll
-      for (int it = 0; it < 3; ++it) {
-        const int f = lane + 64 * it, row = f / CPR, ch = f - row * CPR;
-        const u32x4 v = *reinterpret_cast<const u32x4*>(ep + row * EP_LD + ch * 16);
-        const unsigned off = ((unsigned)(wave_m0 + i * 16 + row) * (unsigned)ldo + (unsigned)(wave_n0 + ch * 8)) * 2u;
-        __builtin_amdgcn_raw_buffer_store_b128(v, o_rsrc, (int)off, 0, 2);
-      }
+      for (int it = 0; it < 3; ++it) patch_store_chunk<CPR, 2>(ep, o_rsrc, wave_m0 + i * 16, ldo, wave_n0, lane, it);
     }
   }
 }

@@ -12,38 +12,36 @@
 //     are re-read from the resident LDS image;
 //   * v_mfma_f32_16x16x32_bf16 with swapped operands, so a lane owns 4 consecutive output columns: float4 bias / GELU,
 //     8-byte packed bf16, then a 16-row LDS patch turns them into whole 16-B row segments for the stores.
-#include "common.h"
+#include "gemm_bf16_loop.h"
 
 namespace {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+using namespace pangu_bf16;
 
 constexpr int WS_WAVES = 8;
 constexpr int WS_BM = 32 * WS_WAVES;          // 256 token rows per workgroup tile
 
-__device__ inline u16 f2bf(float f) { return __builtin_bit_cast(u16, (__bf16)f); }
-__device__ inline unsigned pack2(float a, float b) { return pack_bf16x2(a, b); }
-
-// byte offset of 16-B chunk `chunk` of weight row `row` (row pitch = KMAX*2 bytes, a multiple of 128)
-// Row pitch 384 B (KMAX 192, = 128 mod 256): XOR the low 3 chunk bits with (row>>1)&7; pitch 768 B (KMAX 384, = 0 mod
-// 256): XOR the low 4 chunk bits with row&15.  Either way the 16 rows of a ds_read_b128 lane group (which read chunks
-// c and c^1) land on 16 distinct 16-B slots of the 256-B bank row.
+// byte offset of 16-B chunk `chunk` of weight row `row` (row pitch = KMAX*2 bytes, = 128 mod 256: 384 B at KMAX 192): XOR the low
+// 3 chunk bits with (row>>1)&7, so the 16 rows of a ds_read_b128 lane group (which read chunks c and c^1) land on 16 distinct
+// 16-B slots of the 256-B bank row.  (A pitch of 0 mod 256 -- 768 B at KMAX 384 -- needs the low 4 chunk bits XOR row&15 instead;
+// that arm went with the K = 384 instantiation.)
 template <int KMAX>
 __device__ inline int wswz(int row, int chunk) {
-  if constexpr ((KMAX * 2) % 256 == 0) return row * (KMAX * 2) + ((chunk ^ (row & 15)) << 4);
-  else return row * (KMAX * 2) + ((chunk ^ ((row >> 1) & 7)) << 4);
+  static_assert((KMAX * 2) % 256 == 128, "row pitch = 128 mod 256");
+  return row * (KMAX * 2) + ((chunk ^ ((row >> 1) & 7)) << 4);
 }
 
-template <int BNW, int KMAX, int ACT, bool HAS_BIAS, bool OUT_F32>
+// BNW = columns of the resident weight slice = the largest K it holds (192: the only instantiation; a slice of 96 columns x K = 384
+// lost 20-40 % and an fp32-output patch does not fit next to W: both removed with their template parameters, see the dispatcher)
+template <int BNW, int ACT, bool HAS_BIAS>
 __global__ __launch_bounds__(512, 2) void gemm_ws_bf16_kernel(const u16* __restrict__ A, int lda, const u16* __restrict__ W,
-                                                              const float* __restrict__ bias, void* __restrict__ Cv,
+                                                              const float* __restrict__ bias, u16* __restrict__ C,
                                                               int ldc, int M, int N, int K, int n_slices, int m_tiles,
-                                                              u16* __restrict__ aux, u16* __restrict__ aux2) {
+                                                              u16* __restrict__ aux) {
+  constexpr int KMAX = BNW;
   constexpr int NT = BNW / 16;                 // 16-column tiles per wave row-block
   constexpr int KS = KMAX / 32;                // K-steps of one MFMA (32 k-values)
-  constexpr int ROWB = BNW * (OUT_F32 ? 4 : 2);
+  constexpr int ROWB = BNW * 2;
   constexpr int EP_LD = ROWB + 16;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* Wl = smem;                                   // [BNW][KMAX] bf16, swizzled
@@ -74,7 +72,7 @@ __global__ __launch_bounds__(512, 2) void gemm_ws_bf16_kernel(const u16* __restr
   const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<u16*>(A), 0, (int)(((size_t)(M - 1) * lda + K) * sizeof(u16)), 0x00020000);
   const __amdgpu_buffer_rsrc_t c_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      Cv, 0, (int)(((size_t)(M - 1) * ldc + N) * (OUT_F32 ? 4 : 2)), 0x00020000);
+      C, 0, (int)(((size_t)(M - 1) * ldc + N) * sizeof(u16)), 0x00020000);
   const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(
       aux, 0, aux ? (int)((size_t)M * N * sizeof(u16)) : 0, 0x00020000);
 
@@ -127,21 +125,21 @@ __global__ __launch_bounds__(512, 2) void gemm_ws_bf16_kernel(const u16* __restr
         if (ACT == PANGU_ACT_GELU) {
           if (aux) {
             const unsigned xo = col < N ? ((unsigned)(m_cur + mt * 16 + lc) * (unsigned)N + (unsigned)col) * 2u : 0xFFFFFFFFu;
-            __builtin_amdgcn_raw_buffer_store_b64(u32x2{pack2(v[0], v[1]), pack2(v[2], v[3])}, x_rsrc, (int)xo, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b64(pack_bf16x4(v), x_rsrc, (int)xo, 0, 0);
           }
           v = gelu_erf_lp4(v);
         }
-        if (OUT_F32) *reinterpret_cast<f32x4*>(ep + lc * EP_LD + (j * 16 + lg * 4) * 4) = v;
-        else *reinterpret_cast<u32x2*>(ep + lc * EP_LD + (j * 16 + lg * 4) * 2) = u32x2{pack2(v[0], v[1]), pack2(v[2], v[3])};
+        *reinterpret_cast<u32x2*>(ep + lc * EP_LD + (j * 16 + lg * 4) * 2) = pack_bf16x4(v);
       }
+      // (in place, not patch_store_rows of gemm_bf16_loop.h: with the helper the K <= 192 launches measured +1.1 .. +1.4 %, over the
+      // parent's own spread -- profiles/gemm_bf16_shared_speed.md; this form compiles to the parent's instructions)
 #pragma unroll
       for (int it = 0; it < (16 * CPR + 63) / 64; ++it) {
         const int f = lane + 64 * it, row = f / CPR, ch = f % CPR;
-        const int col = n0 + ch * (OUT_F32 ? 4 : 8);
+        const int col = n0 + ch * 8;
         if (f < 16 * CPR) {
           const u32x4 v = *reinterpret_cast<const u32x4*>(ep + row * EP_LD + ch * 16);
-          const unsigned off = col < N ? ((unsigned)(m_cur + mt * 16 + row) * (unsigned)ldc + (unsigned)col) * (OUT_F32 ? 4u : 2u)
-                                       : 0xFFFFFFFFu;
+          const unsigned off = col < N ? ((unsigned)(m_cur + mt * 16 + row) * (unsigned)ldc + (unsigned)col) * 2u : 0xFFFFFFFFu;
           __builtin_amdgcn_raw_buffer_store_b128(v, c_rsrc, (int)off, 0, 2);
         }
       }
@@ -149,21 +147,21 @@ __global__ __launch_bounds__(512, 2) void gemm_ws_bf16_kernel(const u16* __restr
   }
 }
 
-template <int BNW, int KMAX, bool OUT_F32>
-int launch_ws(hipStream_t s, const u16* A, int lda, const u16* W, const float* bias, void* C, int ldc, int M, int N, int K,
-              int act, u16* aux, u16* aux2) {
+template <int BNW>
+int launch_ws(hipStream_t s, const u16* A, int lda, const u16* W, const float* bias, u16* C, int ldc, int M, int N, int K,
+              int act, u16* aux) {
   const int n_slices = (N + BNW - 1) / BNW;
   const int m_tiles = (M + WS_BM - 1) / WS_BM;
   int per_slice = 256 / n_slices;                       // one persistent workgroup per CU
   if (per_slice < 1) per_slice = 1;
   if (per_slice > m_tiles) per_slice = m_tiles;
   const int grid = per_slice * n_slices;
-  const size_t shm = (size_t)BNW * KMAX * 2 + BNW * 4 + (size_t)WS_WAVES * 16 * (BNW * (OUT_F32 ? 4 : 2) + 16);
+  const size_t shm = (size_t)BNW * BNW * 2 + BNW * 4 + (size_t)WS_WAVES * 16 * (BNW * 2 + 16);
 #define PANGU_WS(ACT, HB)                                                                                             \
   do {                                                                                                                \
-    auto kern = gemm_ws_bf16_kernel<BNW, KMAX, ACT, HB, OUT_F32>;                                                     \
+    auto kern = gemm_ws_bf16_kernel<BNW, ACT, HB>;                                                                    \
     PANGU_ENSURE_DYN_LDS(kern, shm);                                                                                  \
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), shm, s, A, lda, W, bias, C, ldc, M, N, K, n_slices, m_tiles, aux, aux2); \
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), shm, s, A, lda, W, bias, C, ldc, M, N, K, n_slices, m_tiles, aux); \
   } while (0)
   if (act == PANGU_ACT_GELU) {
     if (bias) PANGU_WS(PANGU_ACT_GELU, true); else PANGU_WS(PANGU_ACT_GELU, false);
@@ -179,12 +177,12 @@ int launch_ws(hipStream_t s, const u16* A, int lda, const u16* W, const float* b
 // Internal entry used by pangu_linear_fwd_bf16's dispatcher (same argument meaning); returns PANGU_E_SHAPE when the shape is
 // not one this kernel covers.
 int pangu_linear_ws_bf16(hipStream_t s, const void* A, int lda, const void* W, const float* bias, void* C, int ldc, int M,
-                         int N, int K, int act, void* aux, int out_f32, void* aux2) {
+                         int N, int K, int act, void* aux, int out_f32) {
   // Measured (tools/bench_kernels.py gemm_bf16, MI355X): with K <= 192 a 192-column slice is resident and the kernel beats
   // the tiled one by 5-25 %; with K = 384 only 96 columns fit (activations re-read twice as often) and it LOSES 20-40 %
   // (instantiation removed in round 4), as it does on the GELU-backward epilogue (7-13 %): those stay on the tiled kernel.
   if ((K & 31) || K > 192 || (lda & 7) || (N & 7)) return PANGU_E_SHAPE;
   if (out_f32) return PANGU_E_SHAPE;                        // fp32 patch of a 192-wide slice does not fit next to W
   if (act != PANGU_ACT_NONE && act != PANGU_ACT_GELU) return PANGU_E_SHAPE;
-  return launch_ws<192, 192, false>(s, (const u16*)A, lda, (const u16*)W, bias, C, ldc, M, N, K, act, (u16*)aux, (u16*)aux2);
+  return launch_ws<192>(s, (const u16*)A, lda, (const u16*)W, bias, (u16*)C, ldc, M, N, K, act, (u16*)aux);
 }

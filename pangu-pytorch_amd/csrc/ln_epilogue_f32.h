@@ -5,8 +5,6 @@
 
 namespace pangu_ln {
 
-constexpr float LN_EPS = 1e-5f;
-
 // sum over the 8 lanes that share lane >> 3 (DPP quad_perm x2 + row_half_mirror), result in every lane
 __device__ inline float oct_sum(float v) {
   v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));

@@ -43,21 +43,12 @@
 
 namespace {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-constexpr float LN_EPS = 1e-5f;
-
 constexpr int PD1 = 3;          // fragment-read distance (k-steps ahead of the MFMAs), first product
 constexpr int PD2 = 4;          // the same (row tiles ahead), second product
 constexpr int IGLP = 4;         // VALU instructions placed behind each MFMA of a step (0 = leave it to the scheduler)
 
 __device__ inline float bflo(unsigned u) { return __builtin_bit_cast(float, u << 16); }
 __device__ inline float bfhi(unsigned u) { return __builtin_bit_cast(float, u & 0xFFFF0000u); }
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // GELU for the bf16 hidden activation: x * sigmoid(x (c0 + c1 x^2)) with (c0, c1) fitted to the EXACT erf form the
 // reference uses (nn.GELU(), layers.py:261): max |err| = 2.7e-4 over all x (the degree-6 erf polynomial of the unfused

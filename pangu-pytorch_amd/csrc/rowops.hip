@@ -5,7 +5,6 @@
 
 namespace {
 
-constexpr float LN_EPS = 1e-5f;
 constexpr int ROWS_PER_BLOCK = 4;   // 4 waves of 64
 
 // LayerNorm of one row held as NV float4 per lane (lane i owns float4 i, i+64, ..); C = 4*nvec valid float4.

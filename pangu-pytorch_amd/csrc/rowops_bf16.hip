@@ -7,10 +7,8 @@ namespace {
 typedef unsigned short u16;
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
-constexpr float LN_EPS = 1e-5f;
 constexpr int ROWS_PER_BLOCK = 4;
 
-__device__ inline u16 f2bf(float f) { return __builtin_bit_cast(u16, (__bf16)f); }
 __device__ inline f32x4 ld4(const u16* p) {
   const u32x2 u = *reinterpret_cast<const u32x2*>(p);
   return f32x4{__builtin_bit_cast(float, u[0] << 16), __builtin_bit_cast(float, u[0] & 0xFFFF0000u),

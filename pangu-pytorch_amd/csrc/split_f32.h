@@ -8,7 +8,6 @@
 namespace pangu_split {
 
 using pangu_dma::BK;                             // k-step of 16: one 64-byte fp32 A row, two 8-wide bf16 k-halves
-using pangu_dma::kswz64;
 
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 
