@@ -516,6 +516,36 @@ int pangu_fair_crps_loss_bwd(pangu_stream_t stream, const float* const* members,
  * host code, no stream, returns when the copy is complete. */
 int pangu_host_copy(void* dst, const void* src, long long bytes, int threads);
 
+/* Output side of the forecast loop (data.HostDrain): a field of `planes` planes of `plane_elems` contiguous fp32 values each is
+ * packed on the device to int16 with one (scale, offset) per plane -- ERA5 NetCDF's `scale_factor` / `add_offset` storage -- or
+ * staged as fp32, before the copy engine takes it to page-locked host memory.
+ *   value:      v = src * mul[s] + add[s] in two roundings (multiply, then add: `normBackData`, reference
+ *               era5_data/utils_data.py:324-330) with mul / add fp32 [planes] indexed by SOURCE plane s, both or neither (NULL: v = src);
+ *   addressing: levels = 0: output plane p reads source plane p; levels = L (planes % L == 0): output plane v*L + l reads source
+ *               plane v*L + (L-1-l) -- the reader's level reversal (utils_data.py:117);
+ *   packing:    over the FINITE v of a plane: offset = (max + min) / 2, scale = (max - min) / 65534, scale = 1 when that is 0 (a
+ *               constant plane, an underflowing range) or when the plane has no finite value (then offset = 0);
+ *               q = clamp(rint((v - offset) * (1 / scale)), -32767, 32767); a non-finite v packs to the fill value -32768.
+ *               For finite v, in exact arithmetic on the stored fp32 scale / offset:
+ *                 |q * scale + offset - v| <= 0.5 * scale * (1 + 2^-10) + 4 * 2^-24 * max(|min|, |max|),
+ *               min packs to -32767 and max to +32767.  A plane whose range overflows fp32 is outside the contract.
+ *   outputs:    packed int16 [planes][plane_elems], scale_offset fp32 [planes][2] = (scale, offset), nonfinite int32 [planes] = the
+ *               number of non-finite v; all indexed by OUTPUT plane.
+ * pangu_pack_planes_i16 is two launches on `stream` (per-workgroup min / max / count partials into `workspace`, then quantise; no
+ * atomics, nothing has to be zeroed, bit-identical from run to run); workspace >= pangu_pack_i16_ws_bytes(planes, plane_elems)
+ * bytes (PANGU_E_ARG otherwise), 4-B aligned.  pangu_pack_i16_ws_bytes is host-only and returns PANGU_E_SHAPE for sizes out of range
+ * (planes <= 0, plane_elems <= 0 or >= 2^31, more than 2^31 - 1 workgroups).  pangu_stage_planes_f32: dst[p] = v, fp32, one launch.
+ * 16-B loads and stores run where a plane's base allows it; any plane_elems and any 4-B (src, dst) / 2-B (packed) aligned base work.
+ * pangu_unpack_i16_host is pure host code (no stream): dst = (float)q * scale + offset in fp32 (two roundings), the fill value ->
+ * NaN, split over up to `threads` host threads (contiguous spans; < 1 M values per thread is not split). */
+long long pangu_pack_i16_ws_bytes(int planes, long long plane_elems);
+int pangu_pack_planes_i16(pangu_stream_t stream, const float* src, const float* mul, const float* add, short* packed,
+                          float* scale_offset, int* nonfinite, void* workspace, long long workspace_bytes, int planes,
+                          long long plane_elems, int levels);
+int pangu_stage_planes_f32(pangu_stream_t stream, const float* src, const float* mul, const float* add, float* dst, int planes,
+                           long long plane_elems, int levels);
+int pangu_unpack_i16_host(float* dst, const short* src, const float* scale_offset, int planes, long long plane_elems, int threads);
+
 /* Adam over a whole list of tensors in ONE launch (reference finetune_fully.py:121 torch.optim.Adam, stepped at
  * models/pangu_sample.py:75): p, grad, exp_avg, exp_avg_sq fp32, updated in place with the arithmetic of torch's fused Adam
  * (L2 weight decay added to the gradient, bias corrections, eps outside the root; doubles where that code uses doubles) -- bit

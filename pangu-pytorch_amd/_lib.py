@@ -74,6 +74,10 @@ SIGNATURES = {
     "pangu_fair_crps_loss_fwd": [_P, _P, _P, _I] + [_P] * 7 + [_I] * 7 + [_P] * 4,
     "pangu_fair_crps_loss_bwd": [_P, _P, _P, _I] + [_P] * 8 + [_I] * 7 + [_P] * 4,
     "pangu_host_copy": [_P, _P, _c.c_longlong, _I],
+    "pangu_pack_i16_ws_bytes": [_I, _c.c_longlong],
+    "pangu_pack_planes_i16": [_P, _P, _P, _P, _P, _P, _P, _P, _c.c_longlong, _I, _c.c_longlong, _I],
+    "pangu_stage_planes_f32": [_P, _P, _P, _P, _P, _I, _c.c_longlong, _I],
+    "pangu_unpack_i16_host": [_P, _P, _P, _I, _c.c_longlong, _I],
     "pangu_window_attn_bwd_bf16": [_P] * 10 + [_I] * 6,
     "pangu_ln_residual_bwd_bf16": [_P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _F],
     "pangu_downsample_ln_bwd_bf16": [_P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P],
@@ -95,7 +99,7 @@ SIGNATURES = {
     "pangu_traffic_copy": [_P, _P, _P, _c.c_longlong, _I],
 }
 _RESTYPES = {"pangu_error_string": _c.c_char_p, "pangu_weighted_l1_loss_blocks": _c.c_longlong,
-             "pangu_fair_crps_loss_blocks": _c.c_longlong}
+             "pangu_fair_crps_loss_blocks": _c.c_longlong, "pangu_pack_i16_ws_bytes": _c.c_longlong}
 
 _lib = None
 

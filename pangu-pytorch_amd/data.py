@@ -12,6 +12,11 @@ reference's (unused) DataPrefetcher (era5_data/utils_data.py:16-51) done for bat
   * loaders that can write into a given buffer skip the staging copy altogether (`fill_pinned` protocol below);
   * the level reversal costs nothing: with `fuse_flip=True` the fields stay in file order and the first kernel that reads them
     (patch_embed_gather) / the loss kernel address level 12 - l (`levels_reversed=True` of PanguModel.forward / train.train_step).
+
+`HostDrain` is the mirror image for the OUTPUT side of a forecast loop (the reference pulls every step's de-normalised output to the
+host, models/pangu_sample.py:204-226 and :141-158): a pack (int16 planes with a per-plane scale / offset, ERA5 NetCDF's storage) or
+stage (fp32) kernel on the forecast stream, the device->host copy on a side stream into page-locked buffers allocated once, and a
+worker thread that hands each lead time to a sink; the forecast thread never waits on host I/O unless the ring is full.
 """
 import os
 import queue
@@ -288,3 +293,333 @@ class DevicePrefetcher:
                 "consumer_wait_ms_per_batch": st["consumer_wait_s"] / max(st["batches"], 1) * 1e3,
                 "copy_threads": self.copy_threads, "depth": self.depth, "threaded": self.threaded,
                 "direct_fill": self._filler, "levels_reversed_fused": self.levels_reversed, "static_device_buffers": self.reuse}
+
+
+class DrainedField:
+    """One tensor of a drained item: numpy views into the item's page-locked slot (valid until the item is released).
+
+        packed        int16, shaped like the submitted tensor (mode "int16"), -32768 = non-finite; None in mode "float32"
+        values        float32, shaped like the submitted tensor (mode "float32"); None in mode "int16"
+        scale_offset  (planes, 2) float32 (scale, offset) per (.., H, W) plane; value = packed * scale + offset.  None in "float32"
+        nonfinite     (planes,) int32: non-finite values per plane.  None in "float32" """
+
+    def __init__(self, packed, values, scale_offset, nonfinite, threads):
+        self.packed, self.values, self.scale_offset, self.nonfinite, self._threads = packed, values, scale_offset, nonfinite, threads
+
+    def to_float32(self, out=None):
+        """The field as float32 (a copy that outlives the item; `out`: a C-contiguous float32 array of the same shape to fill)."""
+        import numpy as np
+        src = self.values if self.packed is None else self.packed
+        if out is None:
+            out = np.empty(src.shape, dtype=np.float32)
+        if out.shape != src.shape or out.dtype != np.float32 or not out.flags.c_contiguous:
+            raise ValueError("to_float32: `out` must be a C-contiguous float32 array shaped like the field")
+        if self.packed is None:
+            np.copyto(out, src)
+            return out
+        from . import _lib
+        planes = self.scale_offset.shape[0]
+        _lib.check(_lib.load().pangu_unpack_i16_host(out.ctypes.data, src.ctypes.data, self.scale_offset.ctypes.data, planes,
+                                                     src.size // planes, int(self._threads)), "unpack_i16_host")
+        return out
+
+
+class DrainedItem:
+    """What one `HostDrain.submit` delivers: `fields` (one DrainedField per submitted tensor) and `tag`.  Valid until `release()`;
+    `get()` of the next item releases this one unless `keep()` was called (then the caller releases it)."""
+
+    def __init__(self, drain, slot, tag, fields):
+        self._drain, self._slot, self.tag, self.fields, self._kept = drain, slot, tag, fields, False
+
+    def to_float32(self):
+        return [f.to_float32() for f in self.fields]
+
+    def keep(self):
+        self._kept = True
+        return self
+
+    def release(self):
+        if self._slot is not None:
+            slot, self._slot = self._slot, None
+            self.fields = []
+            self._drain._free_slot(slot)
+
+
+class HostDrain:
+    """Deliver device fields to the host without stalling the loop that produces them.
+
+        drain = HostDrain(device, mode="int16", sink=write_one_lead_time)
+        for k in range(steps): ...; drain.submit([upper, surface], tag=k)
+        drain.close()
+
+    mode          "int16": each (.., H, W) plane is packed on the device (pangu_pack_planes_i16: per-plane scale / offset, half the
+                  bytes over the link); "float32": staged unpacked (pangu_stage_planes_f32).
+    depth         items that may be in flight behind the producer; the ring has depth + 1 slots (device staging + page-locked host
+                  buffers), allocated once for the shapes of the first submit.  A full ring blocks `submit` (back-pressure).
+    stats_last    the 4-tuple of rollout.norm_back (s_mean (1,4,1,1), s_std, u_mean (1,5,13,1,1), u_std): the submitted tensors are
+                  NORMALISED model outputs -- 5-D ones take the upper-air pair, 4-D ones the surface pair -- and are de-normalised
+                  by the kernel.  None: the fields are physical already.
+    flip_levels   reverse the level axis (dim -3) of 5-D tensors, by addressing.
+    sink          callable(item) run on a worker thread for every item, in order; the item is released when it returns.  An
+                  exception ends the sink's service (later items are dropped) and is re-raised by the next submit() or close().
+                  None: fetch items with get() / iteration -- at least once every depth + 1 submits, or from another thread: a
+                  full ring blocks submit until an item is released.
+    copy_threads  host threads of DrainedField.to_float32 (default_copy_threads()).
+
+    submit() works on the CURRENT stream and does not synchronise the host: the kernel reads the tensors in stream order, so they
+    may be overwritten as soon as submit returns."""
+
+    def __init__(self, device, mode="int16", depth=2, stats_last=None, flip_levels=False, sink=None, copy_threads=None):
+        if mode not in ("int16", "float32"):
+            raise ValueError(f"HostDrain: mode must be 'int16' or 'float32', not {mode!r}")
+        self.device, self.mode = torch.device(device), mode
+        self.depth = max(1, int(depth))
+        self.stats_last, self.flip = stats_last, bool(flip_levels)
+        self.sink = sink
+        self.copy_threads = int(copy_threads) if copy_threads else default_copy_threads()
+        self.stream = torch.cuda.Stream(device=self.device, priority=-1)     # (high priority: the copy must not queue behind kernels)
+        self._nslots = self.depth + 1
+        self._spec = None                      # per tensor: (shape, planes, plane_elems, levels, mul, add)
+        self._dev = None                       # per slot, per tensor: dict of device staging tensors
+        self._pin = None                       # per slot, per tensor: dict of page-locked host tensors
+        self._free = [True] * self._nslots
+        self._cv = threading.Condition()
+        self._next = 0
+        self._q = queue.Queue()                # (slot, tag, event) in submit order
+        self._pending = 0                      # submitted, not yet fetched by get()
+        self._last = None                      # the item get() handed out last
+        self._error, self._failed = None, False
+        self._closed = False
+        self._thread = None
+        self.stats = {"bytes": 0, "items": 0, "producer_wait_s": 0.0, "d2h_events": []}
+        if sink is not None:
+            self._thread = threading.Thread(target=self._worker, name="pangu-drain", daemon=True)
+            self._thread.start()
+
+    # ---- ring
+    def _free_slot(self, slot):
+        with self._cv:
+            self._free[slot] = True
+            self._cv.notify_all()
+
+    def _take_slot(self):
+        slot = self._next
+        with self._cv:
+            if not self._free[slot]:
+                t0 = time.perf_counter()
+                while not self._free[slot]:
+                    self._cv.wait(timeout=0.5)
+                    if self._thread is not None and not self._thread.is_alive() and not self._free[slot]:
+                        raise RuntimeError("HostDrain: the sink thread ended with items outstanding")
+                self.stats["producer_wait_s"] += time.perf_counter() - t0
+            self._free[slot] = False
+        self._next = (slot + 1) % self._nslots
+        return slot
+
+    def _plane_stats(self, t):
+        """(mul, add) per SOURCE plane of tensor t, or (None, None)."""
+        if self.stats_last is None:
+            return None, None
+        s_mean, s_std, u_mean, u_std = self.stats_last
+        if t.dim() == 5:
+            mean, std = u_mean, u_std
+        elif t.dim() == 4:
+            mean, std = s_mean, s_std
+        else:
+            raise ValueError("HostDrain: stats_last serves 5-D (B,5,13,H,W) and 4-D (B,4,H,W) tensors only")
+        lead = tuple(t.shape[:-2]) + (1, 1)
+        expand = lambda v: v.to(device=self.device, dtype=torch.float32).expand(lead).contiguous().view(-1)
+        return expand(std), expand(mean)
+
+    def _allocate(self, tensors):
+        spec, int16 = [], self.mode == "int16"
+        from . import _lib
+        for t in tensors:
+            if t.dim() < 2:
+                raise ValueError("HostDrain: tensors are (..., H, W)")
+            elems = t.shape[-1] * t.shape[-2]
+            planes = t.numel() // max(elems, 1)
+            if planes <= 0 or elems <= 0:
+                raise ValueError("HostDrain: empty tensor")
+            levels = t.shape[-3] if (self.flip and t.dim() == 5) else 0
+            mul, add = self._plane_stats(t)
+            ws = _lib.load().pangu_pack_i16_ws_bytes(planes, elems) if int16 else 0
+            if ws < 0:
+                _lib.check(int(ws), "pack_i16_ws_bytes")
+            spec.append((tuple(t.shape), planes, elems, int(levels), mul, add, int(ws)))
+        dev, pin = [], []
+        for _ in range(self._nslots):
+            d, h = [], []
+            for shape, planes, elems, _, _, _, ws in spec:
+                if int16:
+                    d.append({"data": torch.empty(shape, dtype=torch.int16, device=self.device),
+                              "so": torch.empty((planes, 2), dtype=torch.float32, device=self.device),
+                              "nf": torch.empty((planes,), dtype=torch.int32, device=self.device),
+                              "ws": torch.empty((ws + 3) // 4, dtype=torch.float32, device=self.device)})
+                    h.append({"data": torch.empty(shape, dtype=torch.int16, pin_memory=True),
+                              "so": torch.empty((planes, 2), dtype=torch.float32, pin_memory=True),
+                              "nf": torch.empty((planes,), dtype=torch.int32, pin_memory=True)})
+                else:
+                    d.append({"data": torch.empty(shape, dtype=torch.float32, device=self.device)})
+                    h.append({"data": torch.empty(shape, dtype=torch.float32, pin_memory=True)})
+            dev.append(d)
+            pin.append(h)
+        self._spec, self._dev, self._pin = spec, dev, pin
+
+    # ---- producer
+    def submit(self, tensors, tag=None):
+        """Queue `tensors` (a list of contiguous fp32 CUDA tensors (..., H, W), the same shapes on every call) for delivery."""
+        if self._closed:
+            raise RuntimeError("HostDrain: submit after close")
+        self._raise_pending()
+        tensors = list(tensors)
+        for t in tensors:
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+                raise ValueError("HostDrain.submit: contiguous float32 CUDA tensors only")
+        if self._spec is None:
+            with torch.cuda.device(self.device):
+                self._allocate(tensors)
+        if [tuple(t.shape) for t in tensors] != [sp[0] for sp in self._spec]:
+            raise ValueError("HostDrain.submit: the shapes differ from those of the first submit")
+        slot = self._take_slot()
+        self._raise_pending()
+        from . import _lib
+        lib = _lib.load()
+        int16 = self.mode == "int16"
+        nbytes = 0
+        with torch.cuda.device(self.device):
+            cur = torch.cuda.current_stream(self.device)
+            for t, (_, planes, elems, levels, mul, add, ws), d in zip(tensors, self._spec, self._dev[slot]):
+                pm, pa = (mul.data_ptr(), add.data_ptr()) if mul is not None else (None, None)
+                if int16:
+                    _lib.check(lib.pangu_pack_planes_i16(cur.cuda_stream, t.data_ptr(), pm, pa, d["data"].data_ptr(),
+                                                         d["so"].data_ptr(), d["nf"].data_ptr(), d["ws"].data_ptr(), ws, planes, elems,
+                                                         levels), "pack_planes_i16")
+                else:
+                    _lib.check(lib.pangu_stage_planes_f32(cur.cuda_stream, t.data_ptr(), pm, pa, d["data"].data_ptr(), planes, elems,
+                                                          levels), "stage_planes_f32")
+            ready = torch.cuda.Event()
+            ready.record(cur)
+            self.stream.wait_event(ready)
+            with torch.cuda.stream(self.stream):
+                e0 = torch.cuda.Event(enable_timing=True)
+                e0.record(self.stream)
+                for d, h in zip(self._dev[slot], self._pin[slot]):
+                    for k, buf in h.items():
+                        buf.copy_(d[k], non_blocking=True)
+                        nbytes += buf.numel() * buf.element_size()
+                ev = torch.cuda.Event(enable_timing=True)
+                ev.record(self.stream)
+        st = self.stats
+        st["bytes"] += nbytes
+        st["items"] += 1
+        st["d2h_events"].append((e0, ev, nbytes))
+        del st["d2h_events"][:-16]
+        self._pending += 1
+        self._q.put((slot, tag, ev))
+
+    # ---- consumer
+    def _item(self, slot, tag, ev):
+        ev.synchronize()
+        fields = []
+        for h in self._pin[slot]:
+            if self.mode == "int16":
+                fields.append(DrainedField(h["data"].numpy(), None, h["so"].numpy(), h["nf"].numpy(), self.copy_threads))
+            else:
+                fields.append(DrainedField(None, h["data"].numpy(), None, None, self.copy_threads))
+        return DrainedItem(self, slot, tag, fields)
+
+    def get(self):
+        """The next item in submit order (blocks until its copy has landed), or None when nothing is outstanding.  Releases the item
+        handed out before unless it was kept.  Not available with a sink."""
+        if self._thread is not None:
+            raise RuntimeError("HostDrain.get: items go to the sink")
+        if self._last is not None and not self._last._kept:
+            self._last.release()
+        self._last = None
+        if self._pending == 0:
+            return None
+        slot, tag, ev = self._q.get()
+        self._pending -= 1
+        self._last = self._item(slot, tag, ev)
+        return self._last
+
+    def __iter__(self):
+        while True:
+            item = self.get()
+            if item is None:
+                return
+            yield item
+
+    def _worker(self):
+        while True:
+            job = self._q.get()
+            if job is _END:
+                return
+            slot, tag, ev = job
+            item = None
+            try:
+                ev.synchronize()
+                if self._failed:                    # after an error: drop the item, the ring keeps turning so that submit never hangs
+                    self._free_slot(slot)
+                    continue
+                item = self._item(slot, tag, ev)
+                try:
+                    self.sink(item)
+                finally:
+                    item.release()
+            except BaseException as e:              # delivered to the producer: the next submit() or close() re-raises it
+                self._failed = True
+                if self._error is None:
+                    self._error = e
+                if item is None:
+                    self._free_slot(slot)
+
+    def _raise_pending(self):
+        if self._error is not None:
+            e, self._error = self._error, None
+            self._closed = True
+            self._stop_worker()
+            raise e
+
+    def _stop_worker(self):
+        if self._thread is not None and self._thread.is_alive():
+            self._q.put(_END)
+            self._thread.join()
+
+    def close(self):
+        """Deliver what is queued to the sink, join the worker and re-raise its exception, if any.  Without a sink: wait for the copies
+        in flight; items not fetched are dropped."""
+        if not self._closed:
+            self._closed = True
+            self._stop_worker()
+            if self._thread is None:
+                self.stream.synchronize()
+        self._raise_pending()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self.close()
+        else:                                       # do not mask the caller's exception
+            try:
+                self.close()
+            except BaseException:
+                pass
+        return False
+
+    def summary(self):
+        """Rates so far (call after close() or a synchronize): device->host GB/s over the last items, producer wait per item."""
+        st = self.stats
+        ms = b = 0.0
+        for e0, e1, nbytes in st["d2h_events"]:
+            if e1.query():
+                ms += e0.elapsed_time(e1)
+                b += nbytes
+        return {"items": st["items"], "bytes_per_item": st["bytes"] / max(st["items"], 1),
+                "d2h_GBps": b / (ms * 1e-3) / 1e9 if ms > 0 else None,
+                "d2h_ms_per_item": ms / max(len(st["d2h_events"]), 1),
+                "producer_wait_ms_per_item": st["producer_wait_s"] / max(st["items"], 1) * 1e3,
+                "mode": self.mode, "depth": self.depth, "sink": self.sink is not None}

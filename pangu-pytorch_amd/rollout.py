@@ -70,23 +70,32 @@ class GraphedStep:
         return self.out, self.out_surface
 
 
-def rollout(model, inp, inp_surface, statistics, maps, const_h, stats_last, steps=7, graph=True, keep=False):
+def rollout(model, inp, inp_surface, statistics, maps, const_h, stats_last, steps=7, graph=True, keep=False, drain=None):
     """`steps` chained forwards. Returns the last step's physical-unit fields (and, with keep=True, a list of the
-    normalised outputs of every step, cloned)."""
+    normalised outputs of every step, cloned).
+
+    drain: a data.HostDrain (built WITHOUT stats_last: it is handed physical fields).  After every step the step's physical-unit
+    fields are submitted to it with the step index as the tag -- the forecast of every lead time reaches the host while the next
+    steps run.  The pack / stage launches follow each graph replay on the same stream (they are not part of the captured graph)
+    and read the static input buffers the scatter-denorm has just written; the returned values are unchanged."""
     history = []
     with torch.no_grad():
         if graph:
             g = GraphedStep(model, inp, inp_surface, statistics, maps, const_h, stats_last, feed_back=True)
-            for _ in range(steps):
+            for k in range(steps):
                 out, out_s = g.step()
                 if keep:
                     history.append((out.clone(), out_s.clone()))
+                if drain is not None:
+                    drain.submit([g.inp, g.inp_surface], tag=k)
             up, sf = g.inp.clone(), g.inp_surface.clone()
         else:
             up, sf = inp, inp_surface
-            for _ in range(steps):
+            for k in range(steps):
                 out, out_s = model(up, sf, statistics, maps, const_h)
                 if keep:
                     history.append((out.clone(), out_s.clone()))
                 up, sf = norm_back(out, out_s, stats_last)
+                if drain is not None:
+                    drain.submit([up, sf], tag=k)
     return (up, sf, history) if keep else (up, sf)
