@@ -345,6 +345,25 @@ int pangu_ensemble_stats_f32(pangu_stream_t stream, const float* members, long l
                              const float* clim, const float* lat_weight, float* out, float* mean_out, float* std_out,
                              float* workspace, long long workspace_bytes, int planes, int H, int W);
 
+/* Ensemble reliability of members [E][planes][H][W] (member stride in elements, a multiple of 4), 2 <= E <= 128, 0 <= T <= 4,
+ * W % 4 == 0, in one streaming pass (csrc/reliability.hip pins the definitions).  Per grid point of plane p:
+ *   rank = #{x_i < y} + floor(u * (#{x_i == y} + 1) / 2^32), u a hash of (seed, first_plane + p, h*W + w): ties broken uniformly;
+ *   k_t  = #{x_i > thresholds[t][p]} (strict), o_t = (y > thresholds[t][p]).
+ * counts [planes][1 + 2T][E + 1] (uint32): table 0 the verification rank histogram, table 1 + 2t the number of points N_t per
+ * k_t, table 2 + 2t the number of those with the event observed, O_t.  freq, same shape: each point weighted by lat_weight[h]
+ * (H values) and divided by H*W.  prob [T][planes][H][W] (may be NULL; must be NULL with T == 0) receives k_t / E.  target y
+ * [planes][H][W] may be NULL (forecast mode; needs T > 0): table 0 and every O_t are then zero.  thresholds [T][planes] in the
+ * members' units (NULL iff T == 0); +inf is an event that never happens.  Non-finite values are NOT detected: a comparison with
+ * NaN is false.  workspace >= planes * ceil(H / 4) * (1 + 2T) * (E + 1) * 8 bytes.  Integer counts through per-slab partials
+ * and one fixed-order reduce launch, no floating-point atomics: counts are exact, freq is bit-identical from run to run.
+ * PANGU_E_NULL: a required pointer, prob with T == 0, or neither target nor thresholds; PANGU_E_SHAPE: E, T, W % 4, first_plane < 0,
+ * a non-positive size, H*W >= 2^31, a member stride that is short or no multiple of 4, (E - 1) * stride + planes*H*W > 2^40;
+ * PANGU_E_ARG: a workspace that is too small, or members / target / counts / freq / prob / workspace not 16-B aligned. */
+int pangu_ensemble_reliability_f32(pangu_stream_t stream, const float* members, long long member_stride, int E,
+                                   const float* target, const float* thresholds, int T, const float* lat_weight,
+                                   unsigned int seed, int first_plane, unsigned int* counts, float* freq, float* prob,
+                                   void* workspace, long long workspace_bytes, int planes, int H, int W);
+
 /* ---- bf16 variants (BASELINE configs[2], [4]) --------------------------------------------------------------
  * Activations and weight shadows are bf16 (raw uint16 bit patterns); biases, LayerNorm parameters, softmax and all
  * accumulation stay fp32.  Same semantics and layouts as the fp32 entry points above. */

@@ -48,6 +48,8 @@ SIGNATURES = {
     "pangu_lat_weighted_sums": [_P, _P, _P, _P, _P, _I, _I, _I],
     "pangu_ensemble_perturb_f32": [_P, _P, _c.c_longlong, _P, _c.c_longlong, _I, _I, _I, _I, _P, _P, _P, _c.c_uint, _I, _I, _F, _I],
     "pangu_ensemble_stats_f32": [_P, _P, _c.c_longlong, _I, _P, _P, _P, _P, _P, _P, _P, _c.c_longlong, _I, _I, _I],
+    "pangu_ensemble_reliability_f32": [_P, _P, _c.c_longlong, _I, _P, _P, _I, _P, _c.c_uint, _I, _P, _P, _P, _P, _c.c_longlong, _I, _I,
+                                       _I],
     "pangu_linear_fwd_bf16": [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I],
     "pangu_window_attn_fwd_bf16": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I],
     "pangu_window_attn_qkv_fwd_bf16": [_P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I],

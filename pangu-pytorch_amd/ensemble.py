@@ -182,11 +182,28 @@ class EnsembleRollout:
         su, ss = score.ensemble_scores(self.upper, self.surface, None, None, self.stats_last, want_fields=True)
         return (su["mean"], ss["mean"]), (su["std"], ss["std"])
 
+    def reliability(self, target, target_surface, thresholds=None, seed=0):
+        """score.ensemble_reliability of the current state against one target: (upper, surface) ReliabilityTables (rank
+        histogram, and the reliability tables of the events x > thresholds)."""
+        return score.ensemble_reliability(self.upper, self.surface, target, target_surface, thresholds=thresholds, seed=seed)
+
+    def exceedance(self, thresholds):
+        """(prob_upper (T,5,13,H,W), prob_surface (T,4,H,W)): the share of members above each threshold at every grid point
+        of the current state (forecast mode, no target); fields a data.HostDrain can ship like those of mean_std()."""
+        ru, rs = score.ensemble_reliability(self.upper, self.surface, None, None, thresholds=thresholds, want_fields=True)
+        return ru.prob, rs.prob
+
 
 def ensemble_rollout(model, inp, inp_surface, statistics, maps, const_h, stats_last, members, amplitude, steps=7, seed=0,
-                     chunk=None, targets=None, **perturb_kw):
+                     chunk=None, targets=None, reliability=None, thresholds=None, **perturb_kw):
     """`steps` steps of an EnsembleRollout.  Returns the final member state (upper, surface); with targets (a list of
-    (target, target_surface) per step) also the list of per-step score dicts."""
+    (target, target_surface) per step) also the list of per-step score dicts.  With reliability (a score.ReliabilityAccumulator
+    of at least `steps` leads; needs targets) step k's reliability tables against targets[k], for the events x > thresholds,
+    are added to it at lead k (rank ties broken with `seed`); the return value is unchanged."""
+    if reliability is not None and targets is None:
+        raise ValueError("ensemble_rollout: reliability needs targets")
+    if reliability is None and thresholds is not None:
+        raise ValueError("ensemble_rollout: thresholds are used only with reliability")
     with torch.no_grad():
         ens = EnsembleRollout(model, inp, inp_surface, statistics, maps, const_h, stats_last, members, amplitude, seed=seed,
                               chunk=chunk, **perturb_kw)
@@ -195,5 +212,7 @@ def ensemble_rollout(model, inp, inp_surface, statistics, maps, const_h, stats_l
             ens.step()
             if targets is not None:
                 history.append(ens.scores(*targets[k]))
+            if reliability is not None:
+                reliability.add(k, *ens.reliability(*targets[k], thresholds=thresholds, seed=seed))
         up, sf = ens.state()
     return (up, sf, history) if targets is not None else (up, sf)

@@ -103,3 +103,183 @@ def ensemble_scores(upper, surface, target_upper, target_surface, stats_last, wa
         su.update(mean=mu, std=sdu)
         ss.update(mean=ms, std=sds)
     return su, ss
+
+
+# ---- ensemble reliability: verification rank histogram, reliability tables of threshold events, exceedance probabilities ------
+
+RELIABILITY_MAX_T = 4      # csrc/reliability.hip
+
+
+def reliability_workspace_bytes(planes, H, E, T):
+    """Workspace of pangu_ensemble_reliability_f32 (include/pangu_hip.h): per (plane, slab of 4 rows) one uint32 count and one
+    float partial for each of the (1 + 2T) * (E + 1) bins."""
+    return planes * ((H + 3) // 4) * (1 + 2 * T) * (E + 1) * 8
+
+
+class ReliabilityTables:
+    """The tables of one ensemble_reliability call, or a pool of `cases` of them (ReliabilityAccumulator), for planes shaped
+    `rank_counts.shape[:-1]` ((5, 13) or (4,)):
+      rank_counts / rank_freq          (..., E+1)     points per verification rank (Talagrand histogram),
+      event_counts / event_freq        (T, ..., E+1)  points at which k of the E members exceed threshold t (N_t),
+      observed_counts / observed_freq  (T, ..., E+1)  those of them at which the target exceeds it too (O_t),
+      prob                             (T, ..., H, W) k / E per grid point, or None.
+    *_counts are int64 point counts; *_freq weight each point by its latitude weight and divide by H*W, so rank_freq and each N_t
+    sum to about `cases` per plane.  The derived quantities are torch ops on these small tables (float64) and work on any device."""
+
+    def __init__(self, E, T, rank_counts, rank_freq, event_counts, event_freq, observed_counts, observed_freq, prob=None, cases=1):
+        self.E, self.T, self.cases = int(E), int(T), cases
+        self.rank_counts, self.rank_freq = rank_counts, rank_freq
+        self.event_counts, self.event_freq = event_counts, event_freq
+        self.observed_counts, self.observed_freq = observed_counts, observed_freq
+        self.prob = prob
+
+    @classmethod
+    def from_raw(cls, counts, freq, E, T, plane_shape, prob=None):
+        """From the kernel's layout: counts / freq (planes, 1 + 2T, E+1), prob (T, planes, H, W) or None."""
+        ps = tuple(plane_shape)
+        rank = lambda a: a[:, 0].reshape(ps + (E + 1,))
+        tabs = lambda a, first: a[:, first::2].transpose(0, 1).reshape((T,) + ps + (E + 1,))
+        counts = counts.to(torch.int64)
+        if prob is not None:
+            prob = prob.reshape((T,) + ps + tuple(prob.shape[-2:]))
+        return cls(E, T, rank(counts), rank(freq), tabs(counts, 1), tabs(freq, 1), tabs(counts, 2), tabs(freq, 2), prob)
+
+    def _p(self):
+        return torch.arange(self.E + 1, dtype=torch.float64, device=self.rank_freq.device) / self.E
+
+    def brier(self):
+        """Latitude-weighted Brier score per (t, plane), (T, ...): mean of (k/E - o)^2 = sum_k [N_k (k/E)^2 - 2 O_k (k/E) + O_k]."""
+        p, n, o = self._p(), self.event_freq.double(), self.observed_freq.double()
+        return (n * p * p - 2.0 * o * p + o).sum(-1) / self.cases
+
+    def reliability_curve(self):
+        """(forecast probability k/E (E+1,), observed frequency O_k / N_k (T, ..., E+1; NaN where no point forecast k/E),
+        forecast share N_k (T, ..., E+1; sums to about 1))."""
+        n, o = self.event_freq.double(), self.observed_freq.double()
+        return self._p(), o / n, n / self.cases
+
+    def rank_frequencies(self):
+        """The weighted rank histogram normalised to sum 1 per plane (..., E+1): flat at 1 / (E+1) for a calibrated ensemble."""
+        f = self.rank_freq.double()
+        return f / f.sum(-1, keepdim=True)
+
+
+def spread_skill_ratio(scores, E):
+    """sqrt((E+1)/E) * spread / rmse_mean of an ensemble_scores dict: 1 where the spread matches the error of the ensemble mean
+    (the factor accounts for the finite ensemble), below 1 for an under-dispersive ensemble."""
+    return ((E + 1.0) / E) ** 0.5 * scores["spread"] / scores["rmse_mean"]
+
+
+def _check_thresholds(thresholds, who):
+    if thresholds is None:
+        return None, None, 0
+    tu, ts = thresholds
+    if tu.dim() != 3 or tuple(tu.shape[1:]) != (5, 13) or ts.dim() != 2 or ts.shape[1] != 4 or ts.shape[0] != tu.shape[0]:
+        raise ValueError(f"{who}: thresholds must be a pair of tensors (T, 5, 13) and (T, 4)")
+    if tu.shape[0] > RELIABILITY_MAX_T:
+        raise ValueError(f"{who}: at most {RELIABILITY_MAX_T} thresholds, got {tu.shape[0]}")
+    return tu, ts, int(tu.shape[0])
+
+
+def _reliability(x, target, thr, T, seed, first_plane, want_fields, what):
+    """One pangu_ensemble_reliability_f32 call over x (E, *plane_shape, H, W); thr (T, *plane_shape) or None."""
+    E, H, W = x.shape[0], x.shape[-2], x.shape[-1]
+    pshape = tuple(x.shape[1:-2])
+    planes = x[0].numel() // (H * W)
+    _chk(x, what)
+    dev = x.device
+    if target is not None:
+        target = target.reshape(x.shape[1:])
+        _chk(target, what + " target")
+    if T:
+        thr = thr.to(device=dev, dtype=torch.float32).reshape(T, planes).contiguous()
+    counts = torch.empty((planes, 1 + 2 * T, E + 1), dtype=torch.int32, device=dev)      # the entry's uint32, all < 2^31
+    freq = torch.empty((planes, 1 + 2 * T, E + 1), dtype=torch.float32, device=dev)
+    prob = torch.empty((T, planes, H, W), dtype=torch.float32, device=dev) if want_fields and T else None
+    ws = torch.empty(reliability_workspace_bytes(planes, H, E, T), dtype=torch.uint8, device=dev)
+    w = latitude_weights(H, dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    _lib.check(_lib.load().pangu_ensemble_reliability_f32(
+        _stream(x), x.data_ptr(), x[0].numel(), E, ptr(target), ptr(thr) if T else None, T, w.data_ptr(), int(seed) & 0xFFFFFFFF,
+        first_plane, counts.data_ptr(), freq.data_ptr(), ptr(prob), ws.data_ptr(), ws.numel(), planes, H, W),
+        "ensemble_reliability_f32")
+    return ReliabilityTables.from_raw(counts, freq, E, T, pshape, prob)
+
+
+def ensemble_reliability(upper, surface, target_upper, target_surface, thresholds=None, seed=0, want_fields=False):
+    """Reliability tables of E members upper (E,5,13,H,W) / surface (E,4,H,W) against one target ((1,)5,13,H,W / (1,)4,H,W),
+    one HIP pass per tensor (pangu_ensemble_reliability_f32, definitions pinned in csrc/reliability.hip), no host sync.
+
+    thresholds: None, or a pair of tensors (T, 5, 13) and (T, 4) in physical units, T <= 4, for the events x > threshold; +inf
+    means "no event on this plane".  Device tensors avoid an upload.  seed breaks ties between members and the target in the
+    rank (uniformly; the surface planes hash as planes 65..68, the numbering of ensemble.perturb_).  Targets may be None
+    (forecast mode, needs thresholds): the rank and observed tables are then zero.  want_fields=True adds the exceedance
+    probabilities k / E as .prob.  Returns (upper_result, surface_result), two ReliabilityTables."""
+    who = "ensemble_reliability"
+    E = upper.shape[0]
+    if upper.dim() != 5 or surface.dim() != 4 or surface.shape[0] != E:
+        raise ValueError(f"{who}: expected upper (E,5,13,H,W) and surface (E,4,H,W)")
+    if not 2 <= E <= 128:
+        raise ValueError(f"{who}: 2 <= E <= 128 members, got {E}")
+    if upper.shape[-1] % 4:
+        raise ValueError(f"{who}: W % 4 != 0")
+    if (target_upper is None) != (target_surface is None):
+        raise ValueError(f"{who}: give both targets or neither")
+    thr_u, thr_s, T = _check_thresholds(thresholds, who)
+    if T == 0 and target_upper is None:
+        raise ValueError(f"{who}: nothing to compute without a target and without thresholds")
+    ru = _reliability(upper, target_upper, thr_u, T, seed, 0, want_fields, "ensemble upper")
+    rs = _reliability(surface, target_surface, thr_s, T, seed, 65, want_fields, "ensemble surface")
+    return ru, rs
+
+
+class ReliabilityAccumulator:
+    """Pools ReliabilityTables over cases, per lead: the tables add exactly (counts in int64, frequencies in float64, on the
+    tables' device, no host sync).  leads: the number of leads (0 .. leads-1).  One rank histogram from one case says little;
+    this and spread_skill_ratio are the instruments for calibrating the perturbation amplitude."""
+
+    _FIELDS = ("rank_counts", "rank_freq", "event_counts", "event_freq", "observed_counts", "observed_freq")
+
+    def __init__(self, leads):
+        self.leads = int(leads)
+        if self.leads < 1:
+            raise ValueError("ReliabilityAccumulator: leads must be >= 1")
+        self._pool = [None] * self.leads
+        self.E = self.T = None
+
+    def add(self, lead, upper_result, surface_result):
+        if not 0 <= lead < self.leads:
+            raise IndexError(f"lead {lead} outside 0..{self.leads - 1}")
+        for r in (upper_result, surface_result):
+            if self.E is None:
+                self.E, self.T = r.E, r.T
+            if (r.E, r.T) != (self.E, self.T):
+                raise ValueError(f"ReliabilityAccumulator: tables of E = {r.E}, T = {r.T} added to a pool of E = {self.E}, "
+                                 f"T = {self.T}")
+        wide = lambda t: t.to(torch.int64 if not t.is_floating_point() else torch.float64)
+        if self._pool[lead] is None:
+            self._pool[lead] = tuple(ReliabilityTables(r.E, r.T, *(wide(getattr(r, f)).clone() for f in self._FIELDS), cases=r.cases)
+                                     for r in (upper_result, surface_result))
+            return
+        for pooled, r in zip(self._pool[lead], (upper_result, surface_result)):
+            for f in self._FIELDS:
+                getattr(pooled, f).add_(wide(getattr(r, f)))
+            pooled.cases += r.cases
+
+    def cases(self, lead):
+        return 0 if self._pool[lead] is None else self._pool[lead][0].cases
+
+    def tables(self, lead):
+        """(upper, surface) pooled ReliabilityTables of a lead."""
+        if self._pool[lead] is None:
+            raise ValueError(f"ReliabilityAccumulator: nothing added at lead {lead}")
+        return self._pool[lead]
+
+    def brier(self, lead):
+        return tuple(t.brier() for t in self.tables(lead))
+
+    def reliability_curve(self, lead):
+        return tuple(t.reliability_curve() for t in self.tables(lead))
+
+    def rank_frequencies(self, lead):
+        return tuple(t.rank_frequencies() for t in self.tables(lead))

@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """Ensemble measurements (ensemble section):
 
-  python tools/bench_ensemble.py [--reps 10] [--steps 3] [--members 10,50] [--skip-rollout]
+  python tools/bench_ensemble.py [--reps 10] [--steps 3] [--members 10,50] [--skip-kernels] [--skip-reliability] [--skip-rollout]
 
 1. stats: score.ensemble_scores on the full grid at E = 50 and 100, with and without the mean / std fields, against the HBM
    floor (E + 1) * 286.6 MB (+ 2 * 286.6 MB with fields) / 6.29 TB/s.
 2. perturb: ensemble.perturb_ at E = 50 against the floor 2 * E * 286.6 MB / 6.29 TB/s.
-3. rollout: EnsembleRollout (scores at every step) against rollout.GraphedStep B = 1, timed alternately in one process, per
+3. reliability: score.ensemble_reliability at E = 50 and 100, T = 0 and 4, with and without the probability fields, against the
+   floor (E + 1) * 286.6 MB (+ T * 286.6 MB of fields) / 6.29 TB/s.
+4. rollout: EnsembleRollout (scores at every step) against rollout.GraphedStep B = 1, timed alternately in one process, per
    member-step, fp32 and bf16, with the peak memory of each.
 Prints one JSON line per section."""
 import argparse
@@ -63,6 +65,29 @@ def kernels(P, reps):
             ms = _time(lambda: P.ensemble.perturb_(up, sf, sl, 0.01, 1, control=False), reps)
             floor = 2 * E * MEMBER_BYTES / HBM * 1e3
             rows.append({"kernel": "perturb", "E": E, "octaves": 3, "period": 12, "ms": round(ms, 3), "hbm_floor_ms": round(floor, 3),
+                         "x_floor": round(ms / floor, 2), "target_x_floor": 1.5})
+        del up, sf
+        torch.cuda.empty_cache()
+    return rows
+
+
+def reliability(P, reps):
+    """score.ensemble_reliability (verification mode) on the full grid: T = 0 (rank histogram only) and T = 4, with and without
+    the probability fields, against (E + 1) member reads (+ T field writes) at the HBM rate.  Target: the streaming bar, 1.5x."""
+    g = torch.Generator(device="cuda").manual_seed(0)
+    tu = torch.randn((5, 13, H, W), generator=g, device="cuda")
+    ts = torch.randn((4, H, W), generator=g, device="cuda")
+    # events of probability about 0.5, 0.16, 0.02 and 0.001 for standard normal members
+    levels = torch.tensor([0.0, 1.0, 2.0, 3.0], device="cuda")
+    thr = (levels.view(4, 1, 1).expand(4, 5, 13).contiguous(), levels.view(4, 1).expand(4, 4).contiguous())
+    rows = []
+    for E in (50, 100):
+        up = torch.randn((E, 5, 13, H, W), generator=g, device="cuda")
+        sf = torch.randn((E, 4, H, W), generator=g, device="cuda")
+        for T, fields in ((0, False), (4, False), (4, True)):
+            ms = _time(lambda: P.score.ensemble_reliability(up, sf, tu, ts, thr if T else None, seed=1, want_fields=fields), reps)
+            floor = (E + 1 + T * fields) * MEMBER_BYTES / HBM * 1e3
+            rows.append({"kernel": "reliability", "E": E, "T": T, "prob": fields, "ms": round(ms, 3), "hbm_floor_ms": round(floor, 3),
                          "x_floor": round(ms / floor, 2), "target_x_floor": 1.5})
         del up, sf
         torch.cuda.empty_cache()
@@ -133,12 +158,15 @@ def main():
     ap.add_argument("--members", default="10,50")
     ap.add_argument("--skip-rollout", action="store_true")
     ap.add_argument("--skip-kernels", action="store_true")
+    ap.add_argument("--skip-reliability", action="store_true")
     a = ap.parse_args()
     import pangu_pytorch_amd as P
     P._lib.load()
     with torch.no_grad():
         if not a.skip_kernels:
             print(json.dumps({"section": "kernels", "rows": kernels(P, a.reps)}), flush=True)
+        if not a.skip_reliability:
+            print(json.dumps({"section": "reliability", "rows": reliability(P, a.reps)}), flush=True)
         if not a.skip_rollout:
             for row in rollout(P, [int(x) for x in a.members.split(",")], a.steps):
                 print(json.dumps(row), flush=True)
