@@ -364,6 +364,32 @@ int pangu_ensemble_reliability_f32(pangu_stream_t stream, const float* members, 
                                    unsigned int seed, int first_plane, unsigned int* counts, float* freq, float* prob,
                                    void* workspace, long long workspace_bytes, int planes, int H, int W);
 
+/* Ensemble quantile fields and quantile scores of members [E][planes][H][W] (member stride in elements), 2 <= E <= 128,
+ * 1 <= Q <= 8 levels, W % 4 == 0, in one streaming pass (csrc/quantile.hip pins the definitions).  levels: Q HOST doubles in
+ * [0, 1].  Per level, in double: h = q * (E - 1), lo = floor(h), frac = (float)(h - lo).  Per grid point, with x_(0) <= ... <=
+ * x_(E-1) the RAW member values sorted:
+ *   frac == 0:  x_(lo), a pure selection (q = 0, q = 1, the median of an odd E: a member's bits, also beside +-inf members);
+ *   otherwise:  fmin(fmax(fmaf(frac, x_(lo+1) - x_(lo), x_(lo)), x_(lo)), x_(lo+1)): numpy's "linear" method clamped into its
+ *               bracket, so the fields are monotone in q at every point.
+ * A point where any member is NaN gets NaN in every field, contributes nothing to the scores and counts, and is counted in
+ * nonfinite [planes] (uint32, required).  fields [Q][planes][H][W] may be NULL when only scores are wanted.  With target y
+ * [planes][H][W] (then lat_weight [H], pinball, coverage_count and coverage_freq are required; all three [Q][planes]):
+ *   pinball        = sum w_h rho_q(y - x_q) / (H*W),  rho_q(u) = u * (q - (u < 0 ? 1 : 0))   (integrates over q to CRPS / 2);
+ *   coverage_count = #{points : y <= x_q} (uint32), against the very fp32 value written to fields;
+ *   coverage_freq  = the same points weighted by lat_weight[h], divided by H*W (near q for a calibrated ensemble).
+ * Without a target the three score outputs are not written (they may be NULL) and fields is required.  workspace >=
+ * pangu_ensemble_quantiles_ws_bytes(planes, H, Q) = planes * ceil(H / 4) * (3Q + 1) * 4 bytes (host-only; PANGU_E_SHAPE for sizes
+ * out of range), 4-B aligned.  Per-slab partials and one fixed-order reduce launch (slabs added in double), no atomics: every
+ * output is bit-identical from run to run.  Two launches on `stream`, no host sync; everything is checked before the first.
+ * PANGU_E_NULL: a required pointer, or neither fields nor target; PANGU_E_SHAPE: E, Q, W % 4, a non-positive size, H*W >= 2^31,
+ * W >= 2^22, a short member stride, (E - 1) * stride + planes*H*W or Q*planes*H*W > 2^40; PANGU_E_ARG: a level outside [0, 1] or
+ * NaN, a workspace that is too small or misaligned. */
+long long pangu_ensemble_quantiles_ws_bytes(int planes, int H, int Q);
+int pangu_ensemble_quantiles_f32(pangu_stream_t stream, const float* members, long long member_stride, int E,
+                                 const double* levels, int Q, const float* target, const float* lat_weight, float* fields,
+                                 float* pinball, unsigned int* coverage_count, float* coverage_freq, unsigned int* nonfinite,
+                                 void* workspace, long long workspace_bytes, int planes, int H, int W);
+
 /* ---- bf16 variants (BASELINE configs[2], [4]) --------------------------------------------------------------
  * Activations and weight shadows are bf16 (raw uint16 bit patterns); biases, LayerNorm parameters, softmax and all
  * accumulation stay fp32.  Same semantics and layouts as the fp32 entry points above. */

@@ -31,6 +31,7 @@
 // weighted sum cancels little.  Each workgroup writes its six partial sums to a workspace and one launch adds them per plane
 // in slab order: no atomics, bit-identical from run to run.
 #include "common.h"
+#include "bitonic_sort.h"
 
 namespace {
 
@@ -154,27 +155,7 @@ constexpr int ES_ROWS = 4;          // rows per workgroup (one slab)
 constexpr int ES_THREADS = 256;
 constexpr int ES_PART = 8;          // floats per slab partial (6 used)
 
-// one stage (k, j) of the bitonic network, then the next; all indices compile-time
-template <int P, int K, int J>
-__device__ __forceinline__ void bitonic_stage(float (&v)[P]) {
-#pragma unroll
-  for (int i = 0; i < P; ++i) {
-    constexpr int j = J;
-    const int l = i ^ j;
-    if (l > i) {
-      const float a = v[i], b = v[l];
-      if ((i & K) == 0) { v[i] = fminf(a, b); v[l] = fmaxf(a, b); }
-      else { v[i] = fmaxf(a, b); v[l] = fminf(a, b); }
-    }
-  }
-  if constexpr (J > 1) bitonic_stage<P, K, J / 2>(v);
-  else if constexpr (K < P) bitonic_stage<P, 2 * K, K>(v);
-}
-
-template <int P>
-__device__ __forceinline__ void bitonic_sort(float (&v)[P]) {
-  bitonic_stage<P, 2, 1>(v);
-}
+// (bitonic_sort<P>: bitonic_sort.h)
 
 template <int P>
 __global__ __launch_bounds__(ES_THREADS) void ensemble_stats_kernel(const float* __restrict__ x, long long stride, int E,

@@ -193,17 +193,77 @@ class EnsembleRollout:
         ru, rs = score.ensemble_reliability(self.upper, self.surface, None, None, thresholds=thresholds, want_fields=True)
         return ru.prob, rs.prob
 
+    def quantiles(self, q):
+        """(fields_upper (Q,5,13,H,W), fields_surface (Q,4,H,W)): the quantile fields of the current state at the levels q
+        (score.ensemble_quantiles; forecast mode, no target)."""
+        ru, rs = score.ensemble_quantiles(self.upper, self.surface, q)
+        return ru.fields, rs.fields
+
+    def quantile_scores(self, target, target_surface, q):
+        """(upper, surface) score.QuantileResult of the current state against one target: pinball score and coverage per level,
+        without the fields."""
+        return score.ensemble_quantiles(self.upper, self.surface, q, target, target_surface, want_fields=False)
+
+    @staticmethod
+    def product_names(mean_std=True, quantiles=None, thresholds=None):
+        """The names of the tensors products() returns for the same arguments, in its order."""
+        names = ["mean_upper", "mean_surface", "std_upper", "std_surface"] if mean_std else []
+        if quantiles is not None:
+            names += ["quantiles_upper", "quantiles_surface"]
+        if thresholds is not None:
+            names += ["exceedance_upper", "exceedance_surface"]
+        if not names:
+            raise ValueError("EnsembleRollout.products: nothing requested")
+        return names
+
+    def products(self, mean_std=True, quantiles=None, thresholds=None):
+        """The forecast products of the current state as an ordered list of contiguous fp32 tensors, physical units: mean upper,
+        mean surface, std upper, std surface (mean_std), the quantile fields (Q,5,13,H,W), (Q,4,H,W) at the levels `quantiles`,
+        the exceedance probabilities (T,5,13,H,W), (T,4,H,W) of `thresholds` (see exceedance) -- only the requested ones.  The
+        list is what a data.HostDrain built without stats_last accepts, with the same shapes every step; product_names gives the
+        matching names."""
+        self.product_names(mean_std, quantiles, thresholds)
+        out = []
+        if mean_std:
+            (mu, ms), (su, ss) = self.mean_std()
+            out += [mu, ms, su, ss]
+        if quantiles is not None:
+            out += list(self.quantiles(quantiles))
+        if thresholds is not None:
+            out += list(self.exceedance(thresholds))
+        return out
+
 
 def ensemble_rollout(model, inp, inp_surface, statistics, maps, const_h, stats_last, members, amplitude, steps=7, seed=0,
-                     chunk=None, targets=None, reliability=None, thresholds=None, **perturb_kw):
+                     chunk=None, targets=None, reliability=None, thresholds=None, drain=None, products=None, quantile_levels=None,
+                     **perturb_kw):
     """`steps` steps of an EnsembleRollout.  Returns the final member state (upper, surface); with targets (a list of
     (target, target_surface) per step) also the list of per-step score dicts.  With reliability (a score.ReliabilityAccumulator
     of at least `steps` leads; needs targets) step k's reliability tables against targets[k], for the events x > thresholds,
-    are added to it at lead k (rank ties broken with `seed`); the return value is unchanged."""
+    are added to it at lead k (rank ties broken with `seed`); the return value is unchanged.
+
+    drain: a data.HostDrain (built WITHOUT stats_last: the products are physical already).  After every step the step's
+    EnsembleRollout.products(**products) (products: a dict of its arguments, default the mean and std) are submitted with tag =
+    the step index; the pack launches follow the replays on the same stream, with no host synchronisation here.
+    quantile_levels (needs targets): step k's history entry becomes (upper_scores, surface_scores, upper_quantiles,
+    surface_quantiles), the last two the score.QuantileResult of quantile_scores against targets[k]."""
     if reliability is not None and targets is None:
         raise ValueError("ensemble_rollout: reliability needs targets")
     if reliability is None and thresholds is not None:
         raise ValueError("ensemble_rollout: thresholds are used only with reliability")
+    if products is not None and drain is None:
+        raise ValueError("ensemble_rollout: products are delivered through a drain")
+    if drain is not None and getattr(drain, "stats_last", None) is not None:
+        raise ValueError("ensemble_rollout: the drain must be built without stats_last (the products are physical already)")
+    if quantile_levels is not None and targets is None:
+        raise ValueError("ensemble_rollout: quantile_levels needs targets")
+    if quantile_levels is not None:
+        quantile_levels = score._check_levels(quantile_levels, "ensemble_rollout")
+    product_kw = dict(products or {})
+    if drain is not None:
+        EnsembleRollout.product_names(**product_kw)
+        if product_kw.get("quantiles") is not None:
+            score._check_levels(product_kw["quantiles"], "ensemble_rollout")
     with torch.no_grad():
         ens = EnsembleRollout(model, inp, inp_surface, statistics, maps, const_h, stats_last, members, amplitude, seed=seed,
                               chunk=chunk, **perturb_kw)
@@ -211,8 +271,13 @@ def ensemble_rollout(model, inp, inp_surface, statistics, maps, const_h, stats_l
         for k in range(steps):
             ens.step()
             if targets is not None:
-                history.append(ens.scores(*targets[k]))
+                entry = ens.scores(*targets[k])
+                if quantile_levels is not None:
+                    entry = entry + ens.quantile_scores(*targets[k], quantile_levels)
+                history.append(entry)
             if reliability is not None:
                 reliability.add(k, *ens.reliability(*targets[k], thresholds=thresholds, seed=seed))
+            if drain is not None:
+                drain.submit(ens.products(**product_kw), tag=k)
         up, sf = ens.state()
     return (up, sf, history) if targets is not None else (up, sf)

@@ -283,3 +283,120 @@ class ReliabilityAccumulator:
 
     def rank_frequencies(self, lead):
         return tuple(t.rank_frequencies() for t in self.tables(lead))
+
+
+# ---- ensemble quantile fields, the quantile (pinball) score and quantile coverage ----------------------------------------------
+
+QUANTILES_MAX_Q = 8      # csrc/quantile.hip
+
+
+def quantiles_workspace_bytes(planes, H, Q):
+    """Workspace of pangu_ensemble_quantiles_f32 (include/pangu_hip.h): per (plane, slab of 4 rows) 3Q + 1 32-bit words."""
+    return planes * ((H + 3) // 4) * (3 * Q + 1) * 4
+
+
+def _check_levels(q, who):
+    try:
+        levels = [float(v) for v in q]
+    except TypeError:
+        raise ValueError(f"{who}: q must be a sequence of 1..{QUANTILES_MAX_Q} levels in [0, 1]") from None
+    if not 1 <= len(levels) <= QUANTILES_MAX_Q:
+        raise ValueError(f"{who}: 1 <= Q <= {QUANTILES_MAX_Q} quantile levels, got {len(levels)}")
+    for v in levels:
+        if not 0.0 <= v <= 1.0:      # NaN included
+            raise ValueError(f"{who}: quantile levels must lie in [0, 1], got {v}")
+    return tuple(levels)
+
+
+class QuantileResult:
+    """The outputs of one ensemble_quantiles call for planes shaped `plane_shape` ((5, 13) or (4,)):
+      q                the Q levels (a tuple of floats),
+      fields           (Q, ..., H, W) quantile fields, or None,
+      pinball          (Q, ...) latitude-weighted quantile score, mean of rho_q(y - x_q); None without targets,
+      coverage_counts  (Q, ...) int64 points with y <= x_q; None without targets,
+      coverage_freq    (Q, ...) the same points weighted by latitude over H*W (near q when calibrated); None without targets,
+      nonfinite        (...) int64 points per plane left out because a member is NaN (their fields are NaN).
+    The definitions are pinned in csrc/quantile.hip."""
+
+    def __init__(self, q, fields, pinball, coverage_counts, coverage_freq, nonfinite):
+        self.q = tuple(q)
+        self.fields, self.pinball = fields, pinball
+        self.coverage_counts, self.coverage_freq, self.nonfinite = coverage_counts, coverage_freq, nonfinite
+
+    def interval(self, lo_index, hi_index):
+        """The central interval between levels q[lo_index] <= q[hi_index] as a dict of per-plane tensors (float64):
+          nominal   q[hi] - q[lo] (a float),
+          coverage  coverage_freq[hi] - coverage_freq[lo]: the weighted share of points with x_lo < y <= x_hi (needs targets),
+          width     the latitude-weighted mean of fields[hi] - fields[lo] (needs fields; points with a NaN member make it NaN).
+        Entries whose inputs are missing are None."""
+        Q = len(self.q)
+        if not (0 <= lo_index < Q and 0 <= hi_index < Q):
+            raise IndexError(f"QuantileResult.interval: level indices within 0..{Q - 1}")
+        if self.q[lo_index] > self.q[hi_index]:
+            raise ValueError("QuantileResult.interval: q[lo_index] must not exceed q[hi_index]")
+        out = {"nominal": self.q[hi_index] - self.q[lo_index], "coverage": None, "width": None}
+        if self.coverage_freq is not None:
+            out["coverage"] = self.coverage_freq[hi_index].double() - self.coverage_freq[lo_index].double()
+        if self.fields is not None:
+            d = self.fields[hi_index] - self.fields[lo_index]
+            w = latitude_weights(d.shape[-2], d.device).double()
+            out["width"] = (d.double() * w[:, None]).mean(dim=(-2, -1))
+        return out
+
+
+def _quantiles(x, target, levels, want_fields, what):
+    """One pangu_ensemble_quantiles_f32 call over x (E, *plane_shape, H, W)."""
+    import ctypes
+    E, H, W = x.shape[0], x.shape[-2], x.shape[-1]
+    pshape = tuple(x.shape[1:-2])
+    planes = x[0].numel() // (H * W)
+    Q = len(levels)
+    _chk(x, what)
+    dev = x.device
+    if target is not None:
+        target = target.reshape(x.shape[1:])
+        _chk(target, what + " target")
+    fields = torch.empty((Q, planes, H, W), dtype=torch.float32, device=dev) if want_fields else None
+    nonfinite = torch.empty((planes,), dtype=torch.int32, device=dev)      # the entry's uint32, all < 2^31
+    pin = cov = cnt = w = None
+    if target is not None:
+        pin = torch.empty((Q, planes), dtype=torch.float32, device=dev)
+        cov = torch.empty((Q, planes), dtype=torch.float32, device=dev)
+        cnt = torch.empty((Q, planes), dtype=torch.int32, device=dev)
+        w = latitude_weights(H, dev)
+    ws = torch.empty(quantiles_workspace_bytes(planes, H, Q), dtype=torch.uint8, device=dev)
+    lv = (ctypes.c_double * Q)(*levels)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    _lib.check(_lib.load().pangu_ensemble_quantiles_f32(
+        _stream(x), x.data_ptr(), x[0].numel(), E, ctypes.addressof(lv), Q, ptr(target), ptr(w), ptr(fields), ptr(pin), ptr(cnt),
+        ptr(cov), nonfinite.data_ptr(), ws.data_ptr(), ws.numel(), planes, H, W), "ensemble_quantiles_f32")
+    shaped = lambda t: None if t is None else t.reshape((Q,) + pshape)
+    return QuantileResult(levels, None if fields is None else fields.reshape((Q,) + pshape + (H, W)), shaped(pin),
+                          None if cnt is None else shaped(cnt.to(torch.int64)), shaped(cov),
+                          nonfinite.to(torch.int64).reshape(pshape))
+
+
+def ensemble_quantiles(upper, surface, q, target_upper=None, target_surface=None, want_fields=True):
+    """Quantile fields of E members upper (E,5,13,H,W) / surface (E,4,H,W) at the levels q (a sequence of 1..8 floats in [0, 1]),
+    and with one target ((1,)5,13,H,W / (1,)4,H,W) their quantile (pinball) score and coverage; one HIP pass per tensor
+    (pangu_ensemble_quantiles_f32, definitions pinned in csrc/quantile.hip: numpy's "linear" method clamped into its bracket,
+    exact member values where q * (E - 1) is an integer), no host sync.
+
+    want_fields=False skips the (Q, ..., H, W) fields (scores only; needs targets).  Returns (upper_result, surface_result), two
+    QuantileResult."""
+    who = "ensemble_quantiles"
+    E = upper.shape[0]
+    if upper.dim() != 5 or surface.dim() != 4 or surface.shape[0] != E:
+        raise ValueError(f"{who}: expected upper (E,5,13,H,W) and surface (E,4,H,W)")
+    if not 2 <= E <= 128:
+        raise ValueError(f"{who}: 2 <= E <= 128 members, got {E}")
+    if upper.shape[-1] % 4:
+        raise ValueError(f"{who}: W % 4 != 0")
+    if (target_upper is None) != (target_surface is None):
+        raise ValueError(f"{who}: give both targets or neither")
+    levels = _check_levels(q, who)
+    if not want_fields and target_upper is None:
+        raise ValueError(f"{who}: nothing to compute without fields and without a target")
+    ru = _quantiles(upper, target_upper, levels, want_fields, "ensemble upper")
+    rs = _quantiles(surface, target_surface, levels, want_fields, "ensemble surface")
+    return ru, rs

@@ -1,14 +1,18 @@
 #!/usr/bin/env python3
 """Ensemble measurements (ensemble section):
 
-  python tools/bench_ensemble.py [--reps 10] [--steps 3] [--members 10,50] [--skip-kernels] [--skip-reliability] [--skip-rollout]
+  python tools/bench_ensemble.py [--reps 10] [--steps 3] [--members 10,50] [--skip-kernels] [--skip-reliability] [--skip-quantiles]
+                                 [--skip-rollout]
 
 1. stats: score.ensemble_scores on the full grid at E = 50 and 100, with and without the mean / std fields, against the HBM
    floor (E + 1) * 286.6 MB (+ 2 * 286.6 MB with fields) / 6.29 TB/s.
 2. perturb: ensemble.perturb_ at E = 50 against the floor 2 * E * 286.6 MB / 6.29 TB/s.
 3. reliability: score.ensemble_reliability at E = 50 and 100, T = 0 and 4, with and without the probability fields, against the
    floor (E + 1) * 286.6 MB (+ T * 286.6 MB of fields) / 6.29 TB/s.
-4. rollout: EnsembleRollout (scores at every step) against rollout.GraphedStep B = 1, timed alternately in one process, per
+4. quantiles: score.ensemble_quantiles at E = 50 and 100, Q = 3 (0.1, 0.5, 0.9): fields only, scores only and both, against the
+   floor (E (+ 1 with a target) + Q with fields) * 286.6 MB / 6.29 TB/s, and against score.ensemble_scores with targets at the same
+   E in the same process (the kernel that runs the same sorting network): fields only should be no slower than that.
+5. rollout: EnsembleRollout (scores at every step) against rollout.GraphedStep B = 1, timed alternately in one process, per
    member-step, fp32 and bf16, with the peak memory of each.
 Prints one JSON line per section."""
 import argparse
@@ -94,6 +98,31 @@ def reliability(P, reps):
     return rows
 
 
+def quantiles(P, reps):
+    """score.ensemble_quantiles on the full grid, Q = 3 levels (0.1, 0.5, 0.9: all interpolated at E = 50 and 100).  The aim is
+    fields only no slower than score.ensemble_scores with targets on the same members, timed next to it."""
+    g = torch.Generator(device="cuda").manual_seed(0)
+    sl = _stats_last(g)
+    tu = torch.randn((5, 13, H, W), generator=g, device="cuda")
+    ts = torch.randn((4, H, W), generator=g, device="cuda")
+    q = (0.1, 0.5, 0.9)
+    rows = []
+    for E in (50, 100):
+        up = torch.randn((E, 5, 13, H, W), generator=g, device="cuda")
+        sf = torch.randn((E, 4, H, W), generator=g, device="cuda")
+        stats_ms = _time(lambda: P.score.ensemble_scores(up, sf, tu, ts, sl), reps)
+        for mode, tgt, fields in (("fields", False, True), ("scores", True, False), ("both", True, True)):
+            args = (tu, ts) if tgt else (None, None)
+            ms = _time(lambda: P.score.ensemble_quantiles(up, sf, q, *args, want_fields=fields), reps)
+            floor = (E + tgt + len(q) * fields) * MEMBER_BYTES / HBM * 1e3
+            rows.append({"kernel": "quantiles", "E": E, "Q": len(q), "mode": mode, "ms": round(ms, 3), "hbm_floor_ms": round(floor, 3),
+                         "x_floor": round(ms / floor, 2), "stats_with_targets_ms": round(stats_ms, 3),
+                         "x_stats": round(ms / stats_ms, 3), "target_x_stats": 1.0 if mode == "fields" else None})
+        del up, sf
+        torch.cuda.empty_cache()
+    return rows
+
+
 def rollout(P, members, steps):
     import cases
     import synth
@@ -159,6 +188,7 @@ def main():
     ap.add_argument("--skip-rollout", action="store_true")
     ap.add_argument("--skip-kernels", action="store_true")
     ap.add_argument("--skip-reliability", action="store_true")
+    ap.add_argument("--skip-quantiles", action="store_true")
     a = ap.parse_args()
     import pangu_pytorch_amd as P
     P._lib.load()
@@ -167,6 +197,8 @@ def main():
             print(json.dumps({"section": "kernels", "rows": kernels(P, a.reps)}), flush=True)
         if not a.skip_reliability:
             print(json.dumps({"section": "reliability", "rows": reliability(P, a.reps)}), flush=True)
+        if not a.skip_quantiles:
+            print(json.dumps({"section": "quantiles", "rows": quantiles(P, a.reps)}), flush=True)
         if not a.skip_rollout:
             for row in rollout(P, [int(x) for x in a.members.split(",")], a.steps):
                 print(json.dumps(row), flush=True)
