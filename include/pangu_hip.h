@@ -390,6 +390,31 @@ int pangu_ensemble_quantiles_f32(pangu_stream_t stream, const float* members, lo
                                  float* pinball, unsigned int* coverage_count, float* coverage_freq, unsigned int* nonfinite,
                                  void* workspace, long long workspace_bytes, int planes, int H, int W);
 
+/* Zonal power spectra of fields [N][planes][H][W] (item stride in elements, a multiple of 4), averaged over 1 <= B <= 4 latitude
+ * bands band_weight [B][H], for the wavenumbers 0..K, 1 <= K <= W/2; W % 4 == 0, W >= 8 (csrc/spectrum.hip pins the definitions).
+ * Per row, in fp32: d = fields - minus (one rounding; minus [planes][H][W] may be NULL: d = fields), pivot = d[0], a = d - pivot
+ * (a constant changes only wavenumber 0; the pivot takes the large offset of geopotential or temperature out of every
+ * accumulation at no extra pass), X_k = sum_j a[j] exp(-2 pi i jk / W), and
+ *   P_0 = (pivot + Re X_0 / W)^2,   P_k = c_k (Re X_k^2 + Im X_k^2) / W^2 for 1 <= k <= K,   c_k = 2 except c_{W/2} = 1,
+ * so that with K = W/2 sum_k P_k is the row's mean square (Parseval).  out [N][B][planes][K + 1] = sum_h band_weight[b][h] * P_k;
+ * a row of weight exactly 0 adds nothing to its band.  Non-finite values are NOT detected: a NaN in a row makes every
+ * wavenumber of that (item, plane) NaN in the bands whose weight for the row is non-zero (an infinity: NaN or infinite), and
+ * nothing else.
+ * basis_cos / basis_sin [W/2 + 1][K + 1]: cos / sin(2 pi ((j k) mod W) / W), float64 rounded once (the caller builds and keeps
+ * them; score.spectrum_basis).  The transform is a folded real DFT (e[j] = a[j] + a[W - j], o[j] = a[j] - a[W - j]: half the
+ * reduction length) on the f32-input MFMA with fp32 accumulation.  workspace >= pangu_zonal_spectrum_ws_bytes(N, planes, H, B, K)
+ * = N * planes * ceil(H / 128) * B * (K + 1) * 4 bytes (host-only; PANGU_E_SHAPE for sizes out of range), 4-B aligned: per-row-tile
+ * partials and one fixed-order reduce launch (tiles added in double), no atomics: every output is bit-identical from run to run,
+ * and a column's value does not depend on K, N or the stride.  Two launches on `stream`, no host sync; everything is checked
+ * before the first.
+ * PANGU_E_NULL: a required pointer (all but minus); PANGU_E_SHAPE: N < 1, B outside 1..4, K outside 1..W/2, W % 4 != 0, W < 8,
+ * W >= 2^15, a non-positive size, H*W >= 2^31, an item stride that is short or no multiple of 4, (N - 1) * stride + planes*H*W
+ * > 2^40; PANGU_E_ARG: a workspace that is too small, or fields / minus / out / the basis tables not 16-B aligned. */
+long long pangu_zonal_spectrum_ws_bytes(int N, int planes, int H, int B, int K);
+int pangu_zonal_spectrum_f32(pangu_stream_t stream, const float* fields, long long item_stride, int N, const float* minus,
+                             const float* band_weight, int B, const float* basis_cos, const float* basis_sin, int K,
+                             float* out, void* workspace, long long workspace_bytes, int planes, int H, int W);
+
 /* ---- bf16 variants (BASELINE configs[2], [4]) --------------------------------------------------------------
  * Activations and weight shadows are bf16 (raw uint16 bit patterns); biases, LayerNorm parameters, softmax and all
  * accumulation stay fp32.  Same semantics and layouts as the fp32 entry points above. */

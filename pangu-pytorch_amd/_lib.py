@@ -52,6 +52,8 @@ SIGNATURES = {
                                        _I],
     "pangu_ensemble_quantiles_ws_bytes": [_I, _I, _I],
     "pangu_ensemble_quantiles_f32": [_P, _P, _c.c_longlong, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _c.c_longlong, _I, _I, _I],
+    "pangu_zonal_spectrum_ws_bytes": [_I, _I, _I, _I, _I],
+    "pangu_zonal_spectrum_f32": [_P, _P, _c.c_longlong, _I, _P, _P, _I, _P, _P, _I, _P, _P, _c.c_longlong, _I, _I, _I],
     "pangu_linear_fwd_bf16": [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I],
     "pangu_window_attn_fwd_bf16": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I],
     "pangu_window_attn_qkv_fwd_bf16": [_P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I],
@@ -104,7 +106,7 @@ SIGNATURES = {
 }
 _RESTYPES = {"pangu_error_string": _c.c_char_p, "pangu_weighted_l1_loss_blocks": _c.c_longlong,
              "pangu_fair_crps_loss_blocks": _c.c_longlong, "pangu_pack_i16_ws_bytes": _c.c_longlong,
-             "pangu_ensemble_quantiles_ws_bytes": _c.c_longlong}
+             "pangu_ensemble_quantiles_ws_bytes": _c.c_longlong, "pangu_zonal_spectrum_ws_bytes": _c.c_longlong}
 
 _lib = None
 

@@ -204,6 +204,28 @@ class EnsembleRollout:
         without the fields."""
         return score.ensemble_quantiles(self.upper, self.surface, q, target, target_surface, want_fields=False)
 
+    def spectra(self, target=None, target_surface=None, bands=None, kmax=None):
+        """Zonal power spectra of the current state (score.zonal_spectrum; bands and kmax as there): a dict of (upper, surface)
+        score.SpectrumResult pairs with N = 1,
+          "members"  the member spectra averaged over the members,
+          "mean"     the spectrum of the ensemble mean of mean_std(),
+        and with one target ((1,)5,13,H,W / (1,)4,H,W) also
+          "target"   the target's spectrum,
+          "error"    the spectrum of mean - target.
+        members / mean at small scales is the spectral face of the spread: the mean cannot carry more anomaly power than the
+        members do on average."""
+        if (target is None) != (target_surface is None):
+            raise ValueError("EnsembleRollout.spectra: give both targets or neither")
+        kw = dict(bands=bands, kmax=kmax)
+        out = {"members": tuple(r.mean_over_items() for r in score.zonal_spectrum(self.upper, self.surface, **kw))}
+        (mu, ms), _ = self.mean_std()
+        mu, ms = mu.unsqueeze(0), ms.unsqueeze(0)
+        out["mean"] = score.zonal_spectrum(mu, ms, **kw)
+        if target is not None:
+            out["target"] = score.zonal_spectrum(target.reshape(mu.shape), target_surface.reshape(ms.shape), **kw)
+            out["error"] = score.zonal_spectrum(mu, ms, target, target_surface, **kw)
+        return out
+
     @staticmethod
     def product_names(mean_std=True, quantiles=None, thresholds=None):
         """The names of the tensors products() returns for the same arguments, in its order."""

@@ -400,3 +400,183 @@ def ensemble_quantiles(upper, surface, q, target_upper=None, target_surface=None
     ru = _quantiles(upper, target_upper, levels, want_fields, "ensemble upper")
     rs = _quantiles(surface, target_surface, levels, want_fields, "ensemble surface")
     return ru, rs
+
+
+# ---- zonal power spectra: power per zonal wavenumber along each latitude circle, averaged over latitude bands -------------------
+
+SPECTRUM_MAX_B = 4                    # csrc/spectrum.hip
+SPECTRUM_WS_LIMIT = 256 << 20         # bytes of workspace per launch: zonal_spectrum splits N above it
+
+_BASIS = {}                           # (W, K, device) -> (cos, sin) fp32 device tensors
+_BAND_WEIGHTS = {}                    # (H, bands, device) -> the (B, H) weights of named bands, as zonal_spectrum uses them
+
+
+def spectrum_basis(W, K):
+    """The two basis tables of pangu_zonal_spectrum_f32 as float64 numpy arrays (W/2 + 1, K + 1): cos and sin of
+    2 pi r / W with r = (j k) mod W taken in integers, so the argument never exceeds 2 pi; exact 0 and +-1 where the angle is
+    a multiple of pi / 2.  The kernel reads them rounded once to fp32."""
+    import numpy as np
+    if W < 8 or W % 4 or not 1 <= K <= W // 2:
+        raise ValueError(f"spectrum_basis: W % 4 == 0, W >= 8 and 1 <= K <= W/2, got W = {W}, K = {K}")
+    j = np.arange(W // 2 + 1, dtype=np.int64)[:, None]
+    k = np.arange(K + 1, dtype=np.int64)[None, :]
+    r = (j * k) % W
+    ang = 2.0 * np.pi * r.astype(np.float64) / W
+    c, s = np.cos(ang), np.sin(ang)
+    quarter = (4 * r) % W == 0
+    q = (4 * r) // W                 # the quadrant where the angle is a multiple of pi / 2
+    c[quarter] = np.array([1.0, 0.0, -1.0, 0.0])[q[quarter]]
+    s[quarter] = np.array([0.0, 1.0, 0.0, -1.0])[q[quarter]]
+    return c, s
+
+
+def _device_basis(W, K, device):
+    key = (W, K, str(device))
+    if key not in _BASIS:
+        c, s = spectrum_basis(W, K)
+        up = lambda a: torch.from_numpy(a).to(torch.float32).to(device).contiguous()      # float64 -> fp32: the one rounding
+        _BASIS[key] = (up(c), up(s))
+    return _BASIS[key]
+
+
+def spectrum_band_weights(H, bands=None, device=None):
+    """(B, H) fp32 band weights for zonal_spectrum.  bands: a sequence of up to 4 (lat_south, lat_north) pairs in degrees on the
+    grid lat_j = 90 - j * 180 / (H - 1) (both ends included); default: the one global band (-90, 90).  Each row is
+    latitude_weights(H) restricted to the band and normalised to sum 1, so the global row is latitude_weights(H) / H and, with
+    kmax = W/2, the global spectrum sums over k to the sum w p^2 / (H W) of pangu_lat_weighted_sums."""
+    bands = [(-90.0, 90.0)] if bands is None else list(bands)
+    if not 1 <= len(bands) <= SPECTRUM_MAX_B:
+        raise ValueError(f"spectrum_band_weights: 1 <= B <= {SPECTRUM_MAX_B} bands, got {len(bands)}")
+    device = torch.device("cpu") if device is None else device
+    w = latitude_weights(H, device).double()
+    lat = 90.0 - torch.arange(H, device=device, dtype=torch.float64) * 180.0 / float(H - 1)
+    rows = []
+    for band in bands:
+        try:
+            south, north = (float(v) for v in band)
+        except (TypeError, ValueError):
+            raise ValueError("spectrum_band_weights: a band is a (lat_south, lat_north) pair") from None
+        if not south <= north:      # NaN included
+            raise ValueError(f"spectrum_band_weights: lat_south <= lat_north, got ({south}, {north})")
+        inside = (lat >= south) & (lat <= north)
+        row = torch.where(inside, w, torch.zeros_like(w))
+        total = float(row.sum())
+        if not bool(inside.any()) or not total > 0.0:
+            raise ValueError(f"spectrum_band_weights: the band ({south}, {north}) holds no latitude row of weight")
+        rows.append(row / total)
+    return torch.stack(rows).to(torch.float32).contiguous()
+
+
+class SpectrumResult:
+    """The zonal power spectra of one zonal_spectrum call for planes shaped (5, 13) or (4,):
+      power  (N, B, ..., K + 1) band-averaged power per wavenumber, on the device; fp32 from the kernel, float64 after
+             mean_over_items,
+      k      the wavenumbers 0..K (int64),
+      bands  what the call was given: None (global), the (lat_south, lat_north) pairs, or the (B, H) weight tensor.
+    The definitions are pinned in csrc/spectrum.hip.  The derived quantities are torch ops on these small tables (float64) and
+    work on any device."""
+
+    def __init__(self, power, k, bands):
+        self.power, self.k, self.bands = power, k, bands
+
+    def variance(self):
+        """(N, B, ...) anomaly power: the sum over k >= 1, in float64."""
+        return self.power[..., 1:].double().sum(-1)
+
+    def mean_over_items(self):
+        """A result with N = 1: the items' spectra added in float64 and divided by N."""
+        return SpectrumResult(self.power.double().mean(dim=0, keepdim=True), self.k, self.bands)
+
+    def ratio(self, reference):
+        """power / reference.power in float64 (a reference with N = 1 serves every item)."""
+        return self.power.double() / reference.power.double()
+
+    def effective_resolution(self, reference, threshold=0.5):
+        """Per (item, band, plane) the smallest k >= 1 from which ratio(reference) stays below `threshold` up to K, K + 1 where
+        the ratio at K is not below it (int64): from which scale on this forecast is blurred."""
+        below = (self.ratio(reference)[..., 1:] < threshold).to(torch.int64)
+        tail = torch.flip(torch.cumprod(torch.flip(below, dims=(-1,)), dim=-1), dims=(-1,))      # 1 where all of k..K are below
+        return below.shape[-1] + 1 - tail.sum(-1)
+
+
+def _spectrum(x, minus, bw, K, bands, what):
+    """pangu_zonal_spectrum_f32 over x (N, *plane_shape, H, W), N split so that the workspace stays under SPECTRUM_WS_LIMIT."""
+    N, H, W = x.shape[0], x.shape[-2], x.shape[-1]
+    pshape = tuple(x.shape[1:-2])
+    item = x[0].numel()
+    planes = item // (H * W)
+    B = bw.shape[0]
+    dev = x.device
+    if not x.is_cuda:
+        raise RuntimeError(f"{what}: the Pangu HIP path needs tensors on an MI355X device (got {dev}); there is no CPU fallback")
+    if x.dtype != torch.float32:
+        raise RuntimeError(f"{what}: expected float32, got {x.dtype}")
+    stride = x.stride(0) if N > 1 else item
+    if not x[0].is_contiguous() or stride < item or stride % 4:
+        raise RuntimeError(f"{what}: expected contiguous items with an item stride that is a multiple of 4")
+    if minus is not None:
+        minus = minus.reshape(x.shape[1:])
+        _chk(minus, what + " minus")
+    cos_t, sin_t = _device_basis(W, K, dev)
+    lib = _lib.load()
+    per_item = lib.pangu_zonal_spectrum_ws_bytes(1, planes, H, B, K)
+    if per_item < 0:
+        _lib.check(per_item, "zonal_spectrum_ws_bytes")
+    step = max(1, min(N, SPECTRUM_WS_LIMIT // per_item))
+    ws = torch.empty(step * per_item, dtype=torch.uint8, device=dev)
+    outs = []
+    for n0 in range(0, N, step):
+        n = min(step, N - n0)
+        out = torch.empty((n, B, planes, K + 1), dtype=torch.float32, device=dev)
+        _lib.check(lib.pangu_zonal_spectrum_f32(
+            _stream(x), x[n0].data_ptr(), stride, n, None if minus is None else minus.data_ptr(), bw.data_ptr(), B,
+            cos_t.data_ptr(), sin_t.data_ptr(), K, out.data_ptr(), ws.data_ptr(), ws.numel(), planes, H, W), "zonal_spectrum_f32")
+        outs.append(out)
+    power = outs[0] if len(outs) == 1 else torch.cat(outs)
+    return SpectrumResult(power.reshape((N, B) + pshape + (K + 1,)), torch.arange(K + 1, device=dev), bands)
+
+
+def zonal_spectrum(upper, surface, minus_upper=None, minus_surface=None, bands=None, kmax=None):
+    """Zonal power spectra of N states upper (N,5,13,H,W) / surface (N,4,H,W), N >= 1 (items may be strided: members of a
+    larger buffer), optionally of their difference to one state minus_upper ((1,)5,13,H,W) / minus_surface ((1,)4,H,W), per
+    latitude band and wavenumber 0..kmax (default W/2); one HIP pass per tensor (pangu_zonal_spectrum_f32, definitions pinned in
+    csrc/spectrum.hip: a pivot-subtracted folded real DFT on the f32-input MFMA), no host sync once the basis tables of
+    (W, kmax, device) are cached.
+
+    bands: None (the global band), a sequence of up to 4 (lat_south, lat_north) pairs (spectrum_band_weights), or a (B, H) fp32
+    tensor of explicit row weights.  Returns (upper_result, surface_result), two SpectrumResult."""
+    who = "zonal_spectrum"
+    if upper.dim() != 5 or surface.dim() != 4 or surface.shape[0] != upper.shape[0] or upper.shape[0] < 1:
+        raise ValueError(f"{who}: expected upper (N,5,13,H,W) and surface (N,4,H,W), N >= 1")
+    H, W = upper.shape[-2], upper.shape[-1]
+    if tuple(surface.shape[-2:]) != (H, W):
+        raise ValueError(f"{who}: upper and surface on different grids")
+    if W % 4 or W < 8:
+        raise ValueError(f"{who}: W % 4 == 0 and W >= 8, got {W}")
+    if (minus_upper is None) != (minus_surface is None):
+        raise ValueError(f"{who}: give both minus tensors or neither")
+    if minus_upper is not None and (minus_upper.numel() != upper[0].numel() or minus_surface.numel() != surface[0].numel()):
+        raise ValueError(f"{who}: minus tensors must be one state, ((1,)5,13,H,W) and ((1,)4,H,W)")
+    K = W // 2 if kmax is None else int(kmax)
+    if not 1 <= K <= W // 2:
+        raise ValueError(f"{who}: 1 <= kmax <= W/2 = {W // 2}, got {kmax}")
+    if isinstance(bands, torch.Tensor):
+        if bands.dim() != 2 or bands.shape[1] != H or not 1 <= bands.shape[0] <= SPECTRUM_MAX_B:
+            raise ValueError(f"{who}: band weights must be (B, H) with 1 <= B <= {SPECTRUM_MAX_B}")
+        bw = bands.to(device=upper.device, dtype=torch.float32).contiguous()
+    else:
+        bands = None if bands is None else list(bands)
+        try:
+            key = (H, None if bands is None else tuple((float(s), float(n)) for s, n in bands), str(upper.device))
+        except (TypeError, ValueError):
+            key = None                        # not pairs of numbers: spectrum_band_weights says what is wrong
+        if key not in _BAND_WEIGHTS:          # a dozen small torch launches otherwise, a fifth of one state's transform
+            bw = spectrum_band_weights(H, bands, upper.device)
+            if key is None:
+                raise ValueError(f"{who}: bands must be (lat_south, lat_north) pairs")
+            _BAND_WEIGHTS[key] = bw
+        bw = _BAND_WEIGHTS[key]
+        bands = key[1]
+    ru = _spectrum(upper, minus_upper, bw, K, bands, "spectrum upper")
+    rs = _spectrum(surface, minus_surface, bw, K, bands, "spectrum surface")
+    return ru, rs
