@@ -616,6 +616,27 @@ int pangu_stage_planes_f32(pangu_stream_t stream, const float* src, const float*
                            long long plane_elems, int levels);
 int pangu_unpack_i16_host(float* dst, const short* src, const float* scale_offset, int planes, long long plane_elems, int threads);
 
+/* First-order conservative remapping of `planes` planes [H_in][W_in] to a coarser grid [H_out][W_out] of the same family (latitudes
+ * 90 - j * 180 / (H - 1), poles included; longitudes i * 360 / W), one launch on `stream`, no workspace, no atomics, bit-identical
+ * from run to run:
+ *   dst[p][J][I] = sum_s lon_w[I][s] * ( sum_t lat_w[J][t] * v[q][lat_start[J] + t][(lon_start[I] + s) mod W_in] ),
+ * with v = src * mul[q] + add[q] in two roundings, mul / add fp32 [planes] indexed by SOURCE plane q, both or neither (NULL: v =
+ * src), and q = p (levels = 0) or the level-reversed plane (levels = L), exactly as for pangu_stage_planes_f32.  Each sum is taken
+ * in fp32 in tap order: the first product, then one fma per further tap, latitude first; a row of one tap of weight 1 returns its
+ * input bit for bit.  Non-finite values are not masked: they propagate to every output cell whose stencil holds one.
+ *   lat_start / lat_count int32 [H_out], lat_w fp32 [H_out][lat_taps] (zero-padded); lon_start / lon_count int32 [W_out], lon_w
+ *   fp32 [W_out][lon_taps]; device memory, built by score.regrid_plan.
+ * The tables are TRUSTED (the caller's contract, not checked): 1 <= lat_count[J] <= lat_taps, 0 <= lat_start[J] and lat_start[J] +
+ * lat_count[J] <= H_in; 1 <= lon_count[I] <= lon_taps, -W_in < lon_start[I] < W_in (read modulo W_in).
+ * Planes whose rows are 16-B aligned (W_in % 4 == 0 and a 16-B aligned plane base) are read with 16-B loads, others with 4-B loads.
+ * Checked before the launch -- PANGU_E_NULL: a NULL pointer (mul and add: one without the other); PANGU_E_SHAPE: a non-positive
+ * size, H_out > H_in, W_out > W_in, lat_taps or lon_taps outside 1..16, levels < 0 or planes % levels != 0, W_in > 16384 (one row
+ * is staged in LDS), H_in * W_in >= 2^31, planes * H_out >= 2^31; PANGU_E_ARG: src or dst not 4-B aligned. */
+int pangu_regrid_planes_f32(pangu_stream_t stream, const float* src, const float* mul, const float* add, float* dst, int planes,
+                            int H_in, int W_in, int H_out, int W_out, const int* lat_start, const int* lat_count,
+                            const float* lat_w, int lat_taps, const int* lon_start, const int* lon_count, const float* lon_w,
+                            int lon_taps, int levels);
+
 /* Adam over a whole list of tensors in ONE launch (reference finetune_fully.py:121 torch.optim.Adam, stepped at
  * models/pangu_sample.py:75): p, grad, exp_avg, exp_avg_sq fp32, updated in place with the arithmetic of torch's fused Adam
  * (L2 weight decay added to the gradient, bias corrections, eps outside the root; doubles where that code uses doubles) -- bit

@@ -84,6 +84,7 @@ SIGNATURES = {
     "pangu_pack_planes_i16": [_P, _P, _P, _P, _P, _P, _P, _P, _c.c_longlong, _I, _c.c_longlong, _I],
     "pangu_stage_planes_f32": [_P, _P, _P, _P, _P, _I, _c.c_longlong, _I],
     "pangu_unpack_i16_host": [_P, _P, _P, _I, _c.c_longlong, _I],
+    "pangu_regrid_planes_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _I],
     "pangu_window_attn_bwd_bf16": [_P] * 10 + [_I] * 6,
     "pangu_ln_residual_bwd_bf16": [_P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _F],
     "pangu_downsample_ln_bwd_bf16": [_P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P],

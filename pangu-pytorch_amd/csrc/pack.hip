@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "common.h"
+#include "plane_value.h"      // pk_value, pk_src_plane
 
 namespace {
 
@@ -34,16 +35,6 @@ constexpr int PK_FILL = -32768;
 typedef short i16x8 __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ bool pk_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-
-// v = x * mul + add in two roundings, rollout.norm_back's arithmetic.  hipcc contracts a product and a sum into one v_fma_f32 by
-// default (even __fadd_rn(__fmul_rn(..))): contraction is switched off for these two operations.
-template <bool AFFINE>
-__device__ __forceinline__ float pk_value(float x, float m, float a) {
-#pragma clang fp contract(off)
-  if (!AFFINE) return x;
-  const float p = x * m;
-  return p + a;
-}
 
 // Where the 16-B groups of one plane lie.  `head` values come before the first group, `groups` whole groups of VEC follow, the rest
 // is the tail; `vec_src`: the source is 16-B aligned at the first group.
@@ -99,13 +90,6 @@ __device__ __forceinline__ MinMaxCount pk_block_fold(MinMaxCount r, unsigned* sm
     t.bad += sm[2 * NW + i];
   }
   return t;
-}
-
-// output plane -> source plane: with `levels` = L the level index inside each variable is reversed
-__device__ __forceinline__ int pk_src_plane(int p, int levels) {
-  if (levels <= 1) return p;
-  const int v = p / levels, l = p - v * levels;
-  return v * levels + (levels - 1 - l);
 }
 
 // the 8 values of one group: two 16-B loads, or eight scalar ones for a misaligned source

@@ -172,9 +172,17 @@ class EnsembleRollout:
         """The live member state (upper (E,5,13,H,W), surface (E,4,H,W)), physical units; clone it to keep a step."""
         return self.upper, self.surface
 
-    def scores(self, target, target_surface):
-        """score.ensemble_scores of the current state against one target."""
-        return score.ensemble_scores(self.upper, self.surface, target, target_surface, self.stats_last)
+    def scores(self, target, target_surface, regrid=None):
+        """score.ensemble_scores of the current state against one target.  regrid: a score.RegridPlan or an (H_out, W_out) pair:
+        the members and the target are first remapped conservatively to that coarser grid (score.regrid_fields) and scored
+        there, e.g. (121, 240) for WeatherBench-style 1.5 degree scores."""
+        upper, surface = self.upper, self.surface
+        if regrid is not None:
+            upper, surface = score.regrid_fields(upper, surface, regrid)
+            target, target_surface = score.regrid_fields(target.reshape((1,) + tuple(self.upper.shape[1:])).contiguous(),
+                                                         target_surface.reshape((1,) + tuple(self.surface.shape[1:])).contiguous(),
+                                                         regrid)
+        return score.ensemble_scores(upper, surface, target, target_surface, self.stats_last)
 
     def mean_std(self):
         """((mean_upper, mean_surface), (std_upper, std_surface)): ensemble mean and the square root of the unbiased
@@ -266,7 +274,8 @@ def ensemble_rollout(model, inp, inp_surface, statistics, maps, const_h, stats_l
 
     drain: a data.HostDrain (built WITHOUT stats_last: the products are physical already).  After every step the step's
     EnsembleRollout.products(**products) (products: a dict of its arguments, default the mean and std) are submitted with tag =
-    the step index; the pack launches follow the replays on the same stream, with no host synchronisation here.
+    the step index; the pack launches follow the replays on the same stream, with no host synchronisation here.  A drain built
+    with regrid=(H_out, W_out) delivers the products on that coarser grid (remapped on the device), with no change here.
     quantile_levels (needs targets): step k's history entry becomes (upper_scores, surface_scores, upper_quantiles,
     surface_quantiles), the last two the score.QuantileResult of quantile_scores against targets[k]."""
     if reliability is not None and targets is None:

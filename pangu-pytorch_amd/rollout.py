@@ -77,7 +77,9 @@ def rollout(model, inp, inp_surface, statistics, maps, const_h, stats_last, step
     drain: a data.HostDrain (built WITHOUT stats_last: it is handed physical fields).  After every step the step's physical-unit
     fields are submitted to it with the step index as the tag -- the forecast of every lead time reaches the host while the next
     steps run.  The pack / stage launches follow each graph replay on the same stream (they are not part of the captured graph)
-    and read the static input buffers the scatter-denorm has just written; the returned values are unchanged."""
+    and read the static input buffers the scatter-denorm has just written; the returned values are unchanged.  A drain built
+    with regrid=(H_out, W_out) (or a score.RegridPlan) delivers every lead time on that coarser grid, e.g. (121, 240) for 1.5
+    degrees: the remap runs on the device and 36x fewer bytes cross the link; nothing else changes here."""
     history = []
     with torch.no_grad():
         if graph:

@@ -580,3 +580,226 @@ def zonal_spectrum(upper, surface, minus_upper=None, minus_surface=None, bands=N
     ru = _spectrum(upper, minus_upper, bw, K, bands, "spectrum upper")
     rs = _spectrum(surface, minus_surface, bw, K, bands, "spectrum surface")
     return ru, rs
+
+
+# ---- conservative regridding to a coarser lat-lon grid of the same family ---------------------------------------------------------
+
+REGRID_MAX_TAPS = 16                  # csrc/regrid.hip
+REGRID_DROP = 1e-12                   # an overlap below this share of the output cell is a coinciding edge, not a tap
+
+
+def _band(dense, who):
+    """Band tables of the rows of `dense` (n_out, columns), whose non-zeros are contiguous: start / count int32 (n_out,), weights
+    fp32 (n_out, T) zero-padded, T the largest count."""
+    import numpy as np
+    nz = dense > 0.0
+    start = nz.argmax(axis=1).astype(np.int32)
+    last = dense.shape[1] - 1 - nz[:, ::-1].argmax(axis=1)
+    count = (last - start + 1).astype(np.int32)
+    T = int(count.max())
+    if T > REGRID_MAX_TAPS:
+        raise ValueError(f"regrid_plan: {who} needs {T} taps per output cell, the kernel serves at most {REGRID_MAX_TAPS}")
+    w = np.zeros((dense.shape[0], T), np.float32)
+    for r in range(dense.shape[0]):
+        w[r, :count[r]] = dense[r, start[r]:start[r] + count[r]]
+    return start, count, w
+
+
+class RegridPlan:
+    """The first-order conservative remap of regrid_plan: per axis `*_start`, `*_count` (int32 per output index; lon_start may be
+    negative, longitudes are read modulo W_in) and `*_weights` (fp32 (n_out, T), zero-padded), as pangu_regrid_planes_f32 reads
+    them, and the float64 matrices they were rounded from (dense()).  The device copies of the tables are cached per device."""
+
+    def __init__(self, H_in, W_in, H_out, W_out, r_lat, r_lon, lat, lon):
+        self.H_in, self.W_in, self.H_out, self.W_out = H_in, W_in, H_out, W_out
+        self._dense = (r_lat, r_lon)
+        self.lat_start, self.lat_count, self.lat_weights = lat
+        self.lon_start, self.lon_count, self.lon_weights = lon
+        self._dev = {}
+
+    @property
+    def lat_taps(self):
+        return self.lat_weights.shape[1]
+
+    @property
+    def lon_taps(self):
+        return self.lon_weights.shape[1]
+
+    @property
+    def in_grid(self):
+        return (self.H_in, self.W_in)
+
+    @property
+    def out_grid(self):
+        return (self.H_out, self.W_out)
+
+    def dense(self):
+        """(R_lat (H_out, H_in), R_lon (W_out, W_in)) in float64: out = R_lat @ x @ R_lon.T per plane."""
+        return self._dense
+
+    def _device_tables(self, device):
+        key = str(device)
+        if key not in self._dev:
+            up = lambda a: torch.from_numpy(a).to(device).contiguous()
+            self._dev[key] = tuple(up(a) for a in (self.lat_start, self.lat_count, self.lat_weights, self.lon_start,
+                                                   self.lon_count, self.lon_weights))
+        return self._dev[key]
+
+
+def regrid_plan(H_in, W_in, H_out, W_out):
+    """The conservative remap from the grid (H_in, W_in) to the coarser (H_out, W_out), both of the project's family: latitudes
+    lat_j = 90 - j * 180 / (H - 1) with the poles, longitudes lon_i = i * 360 / W.  Cell j spans lat_j +- 90 / (H - 1) clipped to
+    [-90, 90] (the polar rows are half-height caps), cell i spans (i +- 1/2) * 360 / W, periodic.  In float64:
+      R_lat[J, j]  the overlap of output cell J with input cell j in sin(latitude), divided by the row sum,
+      R_lon[I, i]  the overlap in longitude divided by the output cell's width,
+    overlaps below 1e-12 of the output cell dropped.  Rows sum to 1 and area_out^T R = area_in^T (area means are preserved).  The
+    cell edges are compared as integers (in units of 90 / ((H_in - 1)(H_out - 1)) degrees and 180 / (W_in W_out) degrees), so edges
+    that coincide give exactly no overlap.  Returns a RegridPlan; the same grid in and out gives the identity (one tap of weight 1)."""
+    import numpy as np
+    H_in, W_in, H_out, W_out = int(H_in), int(W_in), int(H_out), int(W_out)
+    if not 2 <= H_out <= H_in:
+        raise ValueError(f"regrid_plan: 2 <= H_out <= H_in, got H_in = {H_in}, H_out = {H_out} (no refinement, poles included)")
+    if not 1 <= W_out <= W_in:
+        raise ValueError(f"regrid_plan: 1 <= W_out <= W_in, got W_in = {W_in}, W_out = {W_out} (no refinement)")
+    # latitude: colatitude of the edges as integers m, angle = pi * m / (2 M), M = (H_in - 1)(H_out - 1)
+    M = (H_in - 1) * (H_out - 1)
+
+    def edges(H, other):
+        k = np.arange(H + 1, dtype=np.int64)
+        return np.clip((2 * k - 1) * (other - 1), 0, 2 * M)
+
+    e_in, e_out = edges(H_in, H_out), edges(H_out, H_in)
+    top = np.maximum(e_out[:-1, None], e_in[None, :-1])              # the northern edge of the overlap (smaller colatitude)
+    bot = np.minimum(e_out[1:, None], e_in[None, 1:])
+    s = lambda m: np.cos(np.pi * m.astype(np.float64) / (2.0 * M))   # sin(latitude)
+    ov = np.where(bot > top, s(top) - s(np.maximum(bot, top)), 0.0)
+    cell = (s(e_out[:-1]) - s(e_out[1:]))[:, None]
+    ov[ov < REGRID_DROP * cell] = 0.0
+    r_lat = ov / ov.sum(axis=1, keepdims=True)
+    lat = _band(r_lat, "latitude")
+    # longitude: edges in units of 180 / (W_in W_out) degrees, output cell I = [(2I - 1) W_in, (2I + 1) W_in]
+    i0 = np.arange(W_out, dtype=np.int64)
+    lo, hi = (2 * i0 - 1) * W_in, (2 * i0 + 1) * W_in
+    first = -((-(lo - W_out)) // (2 * W_out)) - 1                    # ceil((lo - W_out) / (2 W_out)) - 1: one cell of margin
+    span = int((2 * W_in) // (2 * W_out)) + 4
+    i = first[:, None] + np.arange(span, dtype=np.int64)[None, :]    # unwrapped input cells
+    o = np.minimum(hi[:, None], (2 * i + 1) * W_out) - np.maximum(lo[:, None], (2 * i - 1) * W_out)
+    wl = np.where(o > 0, o, 0).astype(np.float64) / (2.0 * W_in)
+    wl[wl < REGRID_DROP] = 0.0
+    start, count, w = _band(wl, "longitude")
+    lon_start = (first + start).astype(np.int32)
+    lon_start = np.where(lon_start >= W_in, lon_start - W_in, lon_start).astype(np.int32)
+    r_lon = np.zeros((W_out, W_in), np.float64)
+    for r in range(W_out):
+        for t in range(count[r]):
+            r_lon[r, (first[r] + start[r] + t) % W_in] += wl[r, start[r] + t]
+    return RegridPlan(H_in, W_in, H_out, W_out, r_lat, r_lon, lat, (lon_start, count, w))
+
+
+def _as_plan(plan, H_in, W_in, who):
+    """A RegridPlan, or an (H_out, W_out) pair from which the plan for the grid (H_in, W_in) is built."""
+    if not isinstance(plan, RegridPlan):
+        try:
+            H_out, W_out = (int(v) for v in plan)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: regrid is a score.RegridPlan or an (H_out, W_out) pair") from None
+        key = (H_in, W_in, H_out, W_out)
+        if key not in _PLANS:
+            _PLANS[key] = regrid_plan(*key)
+        plan = _PLANS[key]
+    if plan.in_grid != (H_in, W_in):
+        raise ValueError(f"{who}: the plan regrids {plan.in_grid} fields, got one on {(H_in, W_in)}")
+    return plan
+
+
+_PLANS = {}                           # (H_in, W_in, H_out, W_out) -> the plan built from an (H_out, W_out) pair
+
+
+def _regrid_launch(stream, src_ptr, mul, add, dst_ptr, planes, plan, levels, device):
+    """pangu_regrid_planes_f32 with the plan's device tables; mul / add device tensors or None."""
+    ls, lc, lw, os_, oc, ow = plan._device_tables(device)
+    _lib.check(_lib.load().pangu_regrid_planes_f32(
+        stream, src_ptr, None if mul is None else mul.data_ptr(), None if add is None else add.data_ptr(), dst_ptr, planes,
+        plan.H_in, plan.W_in, plan.H_out, plan.W_out, ls.data_ptr(), lc.data_ptr(), lw.data_ptr(), plan.lat_taps, os_.data_ptr(),
+        oc.data_ptr(), ow.data_ptr(), plan.lon_taps, levels), "regrid_planes_f32")
+
+
+def regrid(x, plan, mul=None, add=None, flip_levels=False, out=None):
+    """x (.., H_in, W_in), a contiguous fp32 CUDA tensor, remapped conservatively to (.., H_out, W_out) by `plan`
+    (regrid_plan), one HIP launch on the current stream (pangu_regrid_planes_f32), no host sync.  mul / add: fp32 tensors with one
+    value per plane of x, both or neither: the remap is taken of x * mul + add (two roundings).  flip_levels reverses dim -3 by
+    addressing (mul / add stay indexed by the plane of x).  out: the fp32 result tensor to write.  Non-finite values propagate to
+    every output cell they touch."""
+    who = "regrid"
+    if not isinstance(plan, RegridPlan):
+        raise ValueError(f"{who}: plan must be a score.RegridPlan")
+    if not (torch.is_tensor(x) and x.dim() >= 2 and x.dtype == torch.float32 and x.is_contiguous()):
+        raise ValueError(f"{who}: x must be a contiguous float32 tensor (.., H, W)")
+    if not x.is_cuda:
+        raise RuntimeError(f"{who}: the Pangu HIP path needs tensors on an MI355X device (got {x.device}); there is no CPU fallback")
+    if tuple(x.shape[-2:]) != plan.in_grid:
+        raise ValueError(f"{who}: the plan regrids {plan.in_grid} fields, got one on {tuple(x.shape[-2:])}")
+    planes = x.numel() // (plan.H_in * plan.W_in)
+    if planes < 1:
+        raise ValueError(f"{who}: empty tensor")
+    if (mul is None) != (add is None):
+        raise ValueError(f"{who}: give both mul and add or neither")
+    if mul is not None:
+        for name, t in (("mul", mul), ("add", add)):
+            if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.numel() == planes):
+                raise ValueError(f"{who}: {name} must be a float32 tensor of {planes} values, one per plane")
+        mul = mul.to(x.device).contiguous().view(-1)
+        add = add.to(x.device).contiguous().view(-1)
+    levels = 0
+    if flip_levels:
+        if x.dim() < 3:
+            raise ValueError(f"{who}: flip_levels needs a level axis (dim -3)")
+        levels = x.shape[-3]
+    shape = tuple(x.shape[:-2]) + plan.out_grid
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif not (torch.is_tensor(out) and out.dtype == torch.float32 and out.is_contiguous() and out.device == x.device
+              and tuple(out.shape) == shape):
+        raise ValueError(f"{who}: out must be a contiguous float32 tensor {shape} on {x.device}")
+    _regrid_launch(_stream(x), x.data_ptr(), mul, add, out.data_ptr(), planes, plan, levels, x.device)
+    return out
+
+
+def plane_affine(t, stats_last, device):
+    """(mul, add) per plane of a NORMALISED model output t, flat fp32 device tensors: t * mul + add is rollout.norm_back.  stats_last
+    = (s_mean (1,4,1,1), s_std, u_mean (1,5,13,1,1), u_std); 5-D tensors take the upper-air pair, 4-D ones the surface pair."""
+    s_mean, s_std, u_mean, u_std = stats_last
+    if t.dim() == 5:
+        mean, std = u_mean, u_std
+    elif t.dim() == 4:
+        mean, std = s_mean, s_std
+    else:
+        raise ValueError("stats_last serves 5-D (B,5,13,H,W) and 4-D (B,4,H,W) tensors only")
+    lead = tuple(t.shape[:-2]) + (1, 1)
+    expand = lambda v: v.to(device=device, dtype=torch.float32).expand(lead).contiguous().view(-1)
+    return expand(std), expand(mean)
+
+
+def regrid_fields(upper, surface, plan, stats_last=None):
+    """(upper, surface) on the plan's coarse grid: upper (B,5,13,H,W) and surface (B,4,H,W) through regrid(), two launches.  With
+    stats_last (the 4-tuple of rollout.norm_back) the inputs are NORMALISED model outputs and the de-normalisation is folded into
+    the pass.  plan: a RegridPlan or an (H_out, W_out) pair.  The results feed the scores as they are, e.g. WeatherBench-style
+    1.5 degree scores of a forecast and of an ensemble:
+
+        plan = score.regrid_plan(721, 1440, 121, 240)
+        up, sf = score.regrid_fields(out_upper, out_surface, plan, stats_last)       # normalised model outputs
+        tu, ts = score.regrid_fields(target_upper, target_surface, plan)             # physical targets
+        rmse = score.weighted_rmse_channels(up, tu)                                  # (B, 5, 13)
+        eu, es = score.regrid_fields(ens.upper, ens.surface, plan)                   # E members
+        su, ss = score.ensemble_scores(eu, es, tu, ts, stats_last)
+        qu, qs = score.ensemble_quantiles(eu, es, (0.1, 0.5, 0.9), tu, ts)"""
+    if upper.dim() != 5 or surface.dim() != 4:
+        raise ValueError("regrid_fields: expected upper (B,5,13,H,W) and surface (B,4,H,W)")
+    if tuple(upper.shape[-2:]) != tuple(surface.shape[-2:]):
+        raise ValueError("regrid_fields: upper and surface on different grids")
+    plan = _as_plan(plan, upper.shape[-2], upper.shape[-1], "regrid_fields")
+    out = []
+    for t in (upper, surface):
+        mul, add = (None, None) if stats_last is None else plane_affine(t, stats_last, t.device)
+        out.append(regrid(t, plan, mul, add))
+    return tuple(out)
