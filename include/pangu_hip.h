@@ -637,6 +637,34 @@ int pangu_regrid_planes_f32(pangu_stream_t stream, const float* src, const float
                             const float* lat_w, int lat_taps, const int* lon_start, const int* lon_count, const float* lon_w,
                             int lon_taps, int levels);
 
+/* Regional scorecard sums of a deterministic forecast: every latitude-weighted sum behind bias, MAE, RMSE, ACC (uncentred and
+ * centred), forecast activity and wind-vector RMSE, for 1 <= R <= 8 regions, in one streaming pass over pred and target
+ * [planes][H][W] fp32 in physical units (csrc/scorecard.hip pins the definitions).  W % 4 == 0.
+ *   target_levels = L > 1: target plane v*L + l is read at v*L + (L-1-l), the level reversal of pangu_regrid_planes_f32 (planes % L
+ *                   == 0); 0 or 1: no reversal;
+ *   clim_kind     0: no climatology, c = 0 (clim is not read); 1: one scalar per plane, clim [planes]; 2: a field, clim
+ *                   [planes][H][W], indexed like pred;
+ *   region_bits   [H][W] bytes shared by all planes: bit r of a point's byte says that the point belongs to region r < R (higher
+ *                   bits are ignored); NULL: one region that holds every point (R must be 1);
+ *   sums          [planes][R][10] doubles.  With d = p - t, a = p - c, b = t - c (one fp32 rounding each) and w = lat_weight[h], over
+ *                   the points of the region:
+ *                     [0] sum w     [1] sum w d    [2] sum w |d|    [3] sum w d^2    [4] sum w a
+ *                     [5] sum w b   [6] sum w a b  [7] sum w a^2    [8] sum w b^2    [9] the number of points.
+ * Membership is a select, never a product with 0: a non-finite value at a point reaches the sums of exactly the regions that hold
+ * the point; an empty region gives ten zeros.  Each (plane, slab of 32 rows) writes its fp32 partials (the count as an integer) to
+ * workspace, >= pangu_scorecard_ws_bytes(planes, H, R) = planes * ceil(H / 32) * R * 40 bytes (host-only; PANGU_E_SHAPE for sizes out
+ * of range); one reduce launch adds the slabs in slab order in double.  No atomics: every output is bit-identical from run to run,
+ * and a plane's sums do not depend on which other planes are in the launch.  Two launches on `stream`, no host sync; everything is
+ * checked before the first.
+ * PANGU_E_NULL: a required pointer (pred, target, lat_weight, sums, workspace), clim with clim_kind != 0, region_bits == NULL with
+ * R != 1; PANGU_E_SHAPE: W % 4, a non-positive size, H*W >= 2^31, R outside 1..8, target_levels < 0 or planes % target_levels != 0,
+ * planes * ceil(H / 32) >= 2^31; PANGU_E_ARG: clim_kind outside 0..2, a workspace that is too small, or a pointer that misses its
+ * alignment: 16 B for pred, target, a clim field and the workspace, 8 B for sums, 4 B for region_bits, lat_weight and clim scalars. */
+long long pangu_scorecard_ws_bytes(int planes, int H, int R);
+int pangu_scorecard_sums_f32(pangu_stream_t stream, const float* pred, const float* target, int target_levels, const float* clim,
+                             int clim_kind, const float* lat_weight, const unsigned char* region_bits, int R, double* sums,
+                             void* workspace, long long workspace_bytes, int planes, int H, int W);
+
 /* Adam over a whole list of tensors in ONE launch (reference finetune_fully.py:121 torch.optim.Adam, stepped at
  * models/pangu_sample.py:75): p, grad, exp_avg, exp_avg_sq fp32, updated in place with the arithmetic of torch's fused Adam
  * (L2 weight decay added to the gradient, bias corrections, eps outside the root; doubles where that code uses doubles) -- bit

@@ -70,7 +70,8 @@ class GraphedStep:
         return self.out, self.out_surface
 
 
-def rollout(model, inp, inp_surface, statistics, maps, const_h, stats_last, steps=7, graph=True, keep=False, drain=None):
+def rollout(model, inp, inp_surface, statistics, maps, const_h, stats_last, steps=7, graph=True, keep=False, drain=None,
+            scorecard=None, targets=None):
     """`steps` chained forwards. Returns the last step's physical-unit fields (and, with keep=True, a list of the
     normalised outputs of every step, cloned).
 
@@ -79,7 +80,24 @@ def rollout(model, inp, inp_surface, statistics, maps, const_h, stats_last, step
     steps run.  The pack / stage launches follow each graph replay on the same stream (they are not part of the captured graph)
     and read the static input buffers the scatter-denorm has just written; the returned values are unchanged.  A drain built
     with regrid=(H_out, W_out) (or a score.RegridPlan) delivers every lead time on that coarser grid, e.g. (121, 240) for 1.5
-    degrees: the remap runs on the device and 36x fewer bytes cross the link; nothing else changes here."""
+    degrees: the remap runs on the device and 36x fewer bytes cross the link; nothing else changes here.
+
+    scorecard: a score.ScoreAccumulator with at least `steps` leads, and targets: a sequence of `steps` entries, each a pair
+    (target_upper, target_surface) of device tensors in physical units or None (no analysis for that lead).  After step k the
+    step's physical-unit fields are scored against targets[k] and pooled at lead k (scorecard.score): two launches per tensor
+    that follow the graph replay on the same stream, outside the captured graph, while the host goes on to the next step; no
+    host sync, and the returned values are unchanged."""
+    if (scorecard is None) != (targets is None):
+        raise ValueError("rollout: scorecard and targets go together (a score.ScoreAccumulator and one target pair or None per step)")
+    if scorecard is not None:
+        targets = list(targets)
+        if len(targets) != steps:
+            raise ValueError(f"rollout: {len(targets)} targets for {steps} steps")
+        if scorecard.leads < steps:
+            raise ValueError(f"rollout: the scorecard holds {scorecard.leads} leads, the rollout makes {steps} steps")
+        for t in targets:
+            if t is not None and len(t) != 2:
+                raise ValueError("rollout: a target is a pair (target_upper, target_surface) or None")
     history = []
     with torch.no_grad():
         if graph:
@@ -90,6 +108,8 @@ def rollout(model, inp, inp_surface, statistics, maps, const_h, stats_last, step
                     history.append((out.clone(), out_s.clone()))
                 if drain is not None:
                     drain.submit([g.inp, g.inp_surface], tag=k)
+                if scorecard is not None and targets[k] is not None:
+                    scorecard.score(k, g.inp, g.inp_surface, *targets[k])
             up, sf = g.inp.clone(), g.inp_surface.clone()
         else:
             up, sf = inp, inp_surface
@@ -100,4 +120,6 @@ def rollout(model, inp, inp_surface, statistics, maps, const_h, stats_last, step
                 up, sf = norm_back(out, out_s, stats_last)
                 if drain is not None:
                     drain.submit([up, sf], tag=k)
+                if scorecard is not None and targets[k] is not None:
+                    scorecard.score(k, up, sf, *targets[k])
     return (up, sf, history) if keep else (up, sf)

@@ -803,3 +803,371 @@ def regrid_fields(upper, surface, plan, stats_last=None):
         mul, add = (None, None) if stats_last is None else plane_affine(t, stats_last, t.device)
         out.append(regrid(t, plan, mul, add))
     return tuple(out)
+
+
+# ---- regional scorecard of a deterministic forecast: bias, MAE, RMSE, ACC, activity per (plane, region) ---------------------------
+
+SCORECARD_MAX_R = 8                   # csrc/scorecard.hip
+SCORECARD_SUMS = 10
+
+# name -> ((lat_south, lat_north), (lon_west, lon_east)) in degrees; latitude ends closed, longitude half-open and wrapping
+REGION_PRESETS = {
+    "global": ((-90.0, 90.0), (0.0, 360.0)),
+    "nh_extratropics": ((20.0, 90.0), (0.0, 360.0)),
+    "tropics": ((-20.0, 20.0), (0.0, 360.0)),
+    "sh_extratropics": ((-90.0, -20.0), (0.0, 360.0)),
+    "arctic": ((65.0, 90.0), (0.0, 360.0)),
+    "antarctic": ((-90.0, -65.0), (0.0, 360.0)),
+    "europe": ((35.0, 75.0), (-12.5, 42.5)),
+    "north_america": ((25.0, 60.0), (-120.0, -75.0)),
+    "north_atlantic": ((25.0, 65.0), (-70.0, -10.0)),
+    "north_pacific": ((25.0, 60.0), (145.0, -130.0)),
+    "east_asia": ((25.0, 60.0), (102.5, 150.0)),
+    "ausnz": ((-45.0, -12.5), (120.0, 175.0)),
+}
+
+_SCORECARD_WEIGHTS = {}               # (H, device) -> latitude_weights(H, device)
+_REGION_PLANS = {}                    # (H, W, regions, device) -> RegionPlan, for region sets without a mask tensor
+
+
+class RegionPlan:
+    """The regions of one scorecard on one grid: `names` (a tuple), `bits` (the uint8 (H, W) device tensor that
+    pangu_scorecard_sums_f32 reads: bit r of a point's byte says that the point lies in region r), R = len(names) and
+    `everywhere` (the plan is one region of every point: the entry is then called without a mask)."""
+
+    def __init__(self, names, bits, everywhere=False):
+        self.names, self.bits = tuple(names), bits
+        self.R = len(self.names)
+        self.H, self.W = int(bits.shape[0]), int(bits.shape[1])
+        self.everywhere = bool(everywhere) and self.R == 1      # one region of every point: the kernel needs no mask
+
+
+def _region_box(H, W, lat, lon, who):
+    """bool numpy (H, W): rows with lat[0] <= 90 - 180 j / (H - 1) <= lat[1], columns with (360 i / W - lon[0]) mod 360 below the
+    box's width (lon[1] - lon[0] taken into (0, 360]: a box may cross the date line or the prime meridian)."""
+    import numpy as np
+    try:
+        (south, north), (west, east) = (float(v) for v in lat), (float(v) for v in lon)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: lat and lon are (lo, hi) pairs in degrees") from None
+    if not south <= north:      # NaN included
+        raise ValueError(f"{who}: lat_lo <= lat_hi, got ({south}, {north})")
+    rows = 90.0 - 180.0 * np.arange(H, dtype=np.float64) / float(max(H - 1, 1))
+    cols = 360.0 * np.arange(W, dtype=np.float64) / float(W)
+    width = east - west
+    if not abs(width) <= 360.0:      # NaN included
+        raise ValueError(f"{who}: a longitude range spans at most 360 degrees, got ({west}, {east})")
+    if width <= 0.0:
+        width += 360.0
+    in_row = (rows >= south) & (rows <= north)
+    in_col = np.mod(cols - west, 360.0) < width
+    return in_row[:, None] & in_col[None, :]
+
+
+def region_bits(H, W, regions=None, device=None):
+    """The RegionPlan of up to 8 named regions on the grid (H, W): latitudes 90 - 180 j / (H - 1), longitudes 360 i / W.
+
+    regions: an ordered mapping name -> a preset name (REGION_PRESETS) or dict(lat=(lo, hi), lon=(lo, hi), mask=None); None gives
+    {"global": "global"}.  lat: both ends closed (default (-90, 90)); lon: half-open and wrapping, (lon - lo) mod 360 < hi - lo with
+    the width taken into (0, 360] (default (0, 360): every column); mask: a bool (H, W) tensor that is ANDed in, e.g. land_mask >
+    0.5.  Regions may overlap.  Plans without a mask tensor are cached per (H, W, regions, device)."""
+    import numpy as np
+    who = "region_bits"
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError(f"{who}: a positive grid size, got ({H}, {W})")
+    device = torch.device("cpu") if device is None else torch.device(device)
+    regions = {"global": "global"} if regions is None else regions
+    if not hasattr(regions, "items"):
+        raise ValueError(f"{who}: regions is a mapping from a name to a preset name or a dict(lat=, lon=, mask=)")
+    if not 1 <= len(regions) <= SCORECARD_MAX_R:
+        raise ValueError(f"{who}: 1 <= R <= {SCORECARD_MAX_R} regions, got {len(regions)}")
+    specs, key = [], []
+    for name, spec in regions.items():
+        if isinstance(spec, str):
+            if spec not in REGION_PRESETS:
+                raise ValueError(f"{who}: no preset region {spec!r}; presets: {', '.join(REGION_PRESETS)}")
+            lat, lon = REGION_PRESETS[spec]
+            mask = None
+        elif isinstance(spec, dict):
+            unknown = set(spec) - {"lat", "lon", "mask"}
+            if unknown:
+                raise ValueError(f"{who}: region {name!r} has unknown keys {sorted(unknown)}")
+            lat, lon, mask = spec.get("lat", (-90.0, 90.0)), spec.get("lon", (0.0, 360.0)), spec.get("mask")
+        else:
+            raise ValueError(f"{who}: region {name!r} is a preset name or a dict(lat=, lon=, mask=)")
+        if mask is not None and not (torch.is_tensor(mask) and mask.dtype == torch.bool and tuple(mask.shape) == (H, W)):
+            raise ValueError(f"{who}: the mask of region {name!r} must be a bool tensor ({H}, {W})")
+        specs.append((name, lat, lon, mask))
+        if key is not None and mask is None:
+            try:
+                key.append((name, tuple(float(v) for v in lat), tuple(float(v) for v in lon)))
+            except (TypeError, ValueError):
+                key = None                    # _region_box says what is wrong
+        else:
+            key = None
+    key = None if key is None else (H, W, tuple(key), str(device))
+    if key is not None and key in _REGION_PLANS:
+        return _REGION_PLANS[key]
+    bits = np.zeros((H, W), np.uint8)
+    for r, (name, lat, lon, mask) in enumerate(specs):
+        inside = _region_box(H, W, lat, lon, f"{who}: region {name!r}")
+        if mask is not None:
+            inside = inside & mask.detach().cpu().numpy()
+        bits |= (inside.astype(np.uint8) << r).astype(np.uint8)
+    plan = RegionPlan([s[0] for s in specs], torch.from_numpy(bits).to(device).contiguous(), everywhere=bool((bits == 1).all()))
+    if key is not None:
+        _REGION_PLANS[key] = plan
+    return plan
+
+
+class ScoreSums:
+    """The ten sums of pangu_scorecard_sums_f32 per (plane, region), of one deterministic_scores call or of a pool of `cases`
+    of them (ScoreAccumulator): `sums` float64 (..., R, 10) on the device, the planes shaped (.., 5, 13) or (.., 4); `names` the
+    regions.  With d = pred - target, a = pred - clim, b = target - clim and the latitude weight w, over a region's points:
+      [0] sum w   [1] sum w d   [2] sum w |d|   [3] sum w d^2   [4] sum w a   [5] sum w b   [6] sum w a b   [7] sum w a^2
+      [8] sum w b^2   [9] the number of points.
+    The derived quantities are torch float64 ops on this small table, shaped (..., R), and work on any device.  They are
+    normalised by the region's own sum of weights; for the global region that is H * W up to the rounding of the weights."""
+
+    def __init__(self, sums, names, cases=1):
+        self.sums, self.names, self.cases = sums, tuple(names), cases
+        if sums.shape[-1] != SCORECARD_SUMS or sums.shape[-2] != len(self.names):
+            raise ValueError("ScoreSums: sums must be (..., R, 10) with one name per region")
+
+    def _s(self, k):
+        return self.sums[..., k].double()
+
+    @property
+    def bias(self):
+        return self._s(1) / self._s(0)
+
+    @property
+    def mae(self):
+        return self._s(2) / self._s(0)
+
+    @property
+    def mse(self):
+        return self._s(3) / self._s(0)
+
+    @property
+    def rmse(self):
+        return torch.sqrt(self.mse)
+
+    @property
+    def acc(self):
+        """Uncentred anomaly correlation, the reference's (era5_data/score.py:123-135) and WeatherBench 2's form."""
+        return self._s(6) / torch.sqrt(self._s(7) * self._s(8))
+
+    @property
+    def acc_centred(self):
+        """The anomaly correlation with the region's weighted mean anomalies removed from all three moments."""
+        ma, mb = self._s(4) / self._s(0), self._s(5) / self._s(0)
+        cov = self._s(6) / self._s(0) - ma * mb
+        return cov / torch.sqrt((self._s(7) / self._s(0) - ma * ma) * (self._s(8) / self._s(0) - mb * mb))
+
+    @property
+    def activity_forecast(self):
+        """Standard deviation of the forecast anomaly over the region: falls below activity_target where a forecast is blurred."""
+        m = self._s(4) / self._s(0)
+        return torch.sqrt(self._s(7) / self._s(0) - m * m)
+
+    @property
+    def activity_target(self):
+        m = self._s(5) / self._s(0)
+        return torch.sqrt(self._s(8) / self._s(0) - m * m)
+
+    @property
+    def counts(self):
+        return self.sums[..., 9].to(torch.int64)
+
+    def wind_rmse(self):
+        """sqrt((sum w du^2 + sum w dv^2) / sum w): of variables 3 and 4 of an upper-air table (.., 5, 13, R, 10), per level
+        (.., 13, R), or of variables 1 and 2 of a surface table (.., 4, R, 10), (.., R)."""
+        s = self.sums
+        if s.dim() >= 4 and tuple(s.shape[-4:-2]) == (5, 13):
+            u, v = s[..., 3, :, :, :].double(), s[..., 4, :, :, :].double()
+        elif s.dim() >= 3 and s.shape[-3] == 4:
+            u, v = s[..., 1, :, :].double(), s[..., 2, :, :].double()
+        else:
+            raise ValueError("ScoreSums.wind_rmse: needs a table of planes (.., 5, 13) or (.., 4)")
+        return torch.sqrt((u[..., 3] + v[..., 3]) / u[..., 0])
+
+    def skill(self, reference):
+        """1 - rmse / reference.rmse against the ScoreSums of a persistence or climatology forecast of the same targets."""
+        if self.names != reference.names:
+            raise ValueError(f"ScoreSums.skill: regions {self.names} against {reference.names}")
+        return 1.0 - self.rmse / reference.rmse
+
+    def region(self, name):
+        """The table of one region, as a ScoreSums with R = 1."""
+        if name not in self.names:
+            raise KeyError(f"ScoreSums.region: no region {name!r} among {self.names}")
+        i = self.names.index(name)
+        return ScoreSums(self.sums[..., i:i + 1, :], (name,), self.cases)
+
+
+def scorecard_workspace_bytes(planes, H, R):
+    """Workspace of pangu_scorecard_sums_f32 (include/pangu_hip.h): per (plane, slab of 32 rows, region) ten 32-bit words."""
+    return planes * ((H + 31) // 32) * R * SCORECARD_SUMS * 4
+
+
+def _scorecard(pred, target, target_levels, clim, clim_kind, plan, what):
+    """pangu_scorecard_sums_f32 over pred / target (cases.., *plane_shape, H, W); clim: None, a flat fp32 tensor with one value per
+    plane of one case, or a field shaped like one case.  Returns the float64 (cases.., *plane_shape, R, 10) sums."""
+    H, W = pred.shape[-2], pred.shape[-1]
+    if target.shape != pred.shape:
+        raise ValueError(f"{what}: the target is {tuple(target.shape)}, the forecast {tuple(pred.shape)}")
+    if (plan.H, plan.W) != (H, W) or plan.bits.device != pred.device:
+        raise ValueError(f"{what}: the region plan is for a {(plan.H, plan.W)} grid on {plan.bits.device}, the fields are "
+                         f"{(H, W)} on {pred.device}")
+    planes = pred.numel() // (H * W)
+    R = plan.R
+    stream = _stream(pred)
+    p_ptr, t_ptr = _chk(pred, what), _chk(target, what + " target")
+    dev = pred.device
+    sums = torch.empty(tuple(pred.shape[:-2]) + (R, SCORECARD_SUMS), dtype=torch.float64, device=dev)
+    if (H, str(dev)) not in _SCORECARD_WEIGHTS:      # half a dozen small torch launches otherwise, per tensor and lead
+        _SCORECARD_WEIGHTS[(H, str(dev))] = latitude_weights(H, dev)
+    w = _SCORECARD_WEIGHTS[(H, str(dev))]
+    lib = _lib.load()
+
+    def launch(first, n, clim_ptr):
+        ws = torch.empty(scorecard_workspace_bytes(n, H, R), dtype=torch.uint8, device=dev)
+        _lib.check(lib.pangu_scorecard_sums_f32(
+            stream, p_ptr + 4 * first * H * W, t_ptr + 4 * first * H * W, target_levels, clim_ptr, clim_kind, w.data_ptr(),
+            None if plan.everywhere else plan.bits.data_ptr(), R, sums.data_ptr() + 8 * first * R * SCORECARD_SUMS, ws.data_ptr(), ws.numel(), n, H, W),
+            "scorecard_sums_f32")
+
+    if clim_kind == 0:
+        launch(0, planes, None)
+    elif clim_kind == 1:
+        per_case = clim.numel()
+        c = clim.to(device=dev, dtype=torch.float32).reshape(-1).repeat(planes // per_case).contiguous()
+        launch(0, planes, c.data_ptr())
+    else:
+        per_case = clim.numel() // (H * W)      # the field serves every case: one launch per case, none of them copies it
+        c_ptr = _chk(clim, what + " climatology")
+        for first in range(0, planes, per_case):
+            launch(first, per_case, c_ptr)
+    return sums
+
+
+def deterministic_scores(upper, surface, target_upper, target_surface, regions=None, clim=None, target_levels_reversed=False):
+    """The regional scorecard sums of forecasts upper (.., 5, 13, H, W) / surface (.., 4, H, W) against targets of the same shapes,
+    all fp32 in physical units (what rollout() holds after a step); leading dimensions are separate cases.  One HIP pass per tensor
+    (pangu_scorecard_sums_f32, definitions pinned in csrc/scorecard.hip), no host sync, bit-identical from run to run.
+
+    regions: None (the global region), a mapping as for region_bits, or a RegionPlan.  clim: None (anomalies are the fields
+    themselves), stats_last (s_mean, s_std, u_mean, u_std: the means serve as one climatological value per plane, as
+    ensemble_scores uses them), or a pair (clim_upper, clim_surface) of fields shaped like one case (a day-of-year climatology;
+    with several cases one launch per case).  target_levels_reversed: the upper-air target is stored with its level axis reversed.
+    Returns (upper_sums, surface_sums), two ScoreSums with sums (.., 5, 13, R, 10) and (.., 4, R, 10)."""
+    who = "deterministic_scores"
+    if upper.dim() < 4 or surface.dim() < 3 or tuple(upper.shape[-4:-2]) != (5, 13) or surface.shape[-3] != 4:
+        raise ValueError(f"{who}: expected upper (.., 5, 13, H, W) and surface (.., 4, H, W)")
+    if tuple(upper.shape[:-4]) != tuple(surface.shape[:-3]) or tuple(upper.shape[-2:]) != tuple(surface.shape[-2:]):
+        raise ValueError(f"{who}: upper and surface disagree in their cases or grids")
+    H, W = upper.shape[-2], upper.shape[-1]
+    if W % 4:
+        raise ValueError(f"{who}: W % 4 != 0")
+    if target_upper is None or target_surface is None:
+        raise ValueError(f"{who}: both targets are required")
+    if target_upper.numel() != upper.numel() or target_surface.numel() != surface.numel():
+        raise ValueError(f"{who}: the targets must hold one value per forecast value, got {tuple(target_upper.shape)} and "
+                         f"{tuple(target_surface.shape)} for {tuple(upper.shape)} and {tuple(surface.shape)}")
+    plan = regions if isinstance(regions, RegionPlan) else region_bits(H, W, regions, upper.device)
+    cu = cs = None
+    kind = 0
+    if clim is not None:
+        clim = tuple(clim)
+        if len(clim) == 4:
+            kind, cs, cu = 1, clim[0], clim[2]
+            if cu.numel() != 65 or cs.numel() != 4:
+                raise ValueError(f"{who}: stats_last means must hold 5 x 13 and 4 values")
+        elif len(clim) == 2:
+            kind, (cu, cs) = 2, clim
+            if cu.numel() != 65 * H * W or cs.numel() != 4 * H * W:
+                raise ValueError(f"{who}: climatology fields must be shaped like one case, (5, 13, H, W) and (4, H, W)")
+        else:
+            raise ValueError(f"{who}: clim is None, stats_last or a pair of fields")
+    su = _scorecard(upper, target_upper.reshape(upper.shape), 13 if target_levels_reversed else 0, cu, kind, plan, "scorecard upper")
+    ss = _scorecard(surface, target_surface.reshape(surface.shape), 0, cs, kind, plan, "scorecard surface")
+    return ScoreSums(su, plan.names), ScoreSums(ss, plan.names)
+
+
+SCORECARD_METRICS = ("bias", "mae", "rmse", "acc", "acc_centred", "activity_forecast", "activity_target")
+
+
+class ScoreAccumulator:
+    """Pools ScoreSums over cases, per lead: the float64 sums are added on their device (no host sync), so pooled scores are the
+    scores over all cases' points.  leads: the number of leads (0 .. leads-1); regions, clim and
+    target_levels_reversed as for deterministic_scores, which score() calls.  The twin of ReliabilityAccumulator, and what
+    rollout(scorecard=) feeds."""
+
+    def __init__(self, leads, regions=None, clim=None, target_levels_reversed=False):
+        self.leads = int(leads)
+        if self.leads < 1:
+            raise ValueError("ScoreAccumulator: leads must be >= 1")
+        self.regions, self.clim, self.target_levels_reversed = regions, clim, bool(target_levels_reversed)
+        self._plans = {}
+        self._pool = [None] * self.leads
+        self.names = None
+
+    def _check_lead(self, lead):
+        if not 0 <= lead < self.leads:
+            raise IndexError(f"lead {lead} outside 0..{self.leads - 1}")
+
+    def score(self, lead, upper, surface, target_upper, target_surface):
+        """deterministic_scores of these fields, pooled at `lead`; returns the two ScoreSums of this call."""
+        self._check_lead(lead)
+        plan = self.regions
+        if not isinstance(plan, RegionPlan):
+            key = (upper.shape[-2], upper.shape[-1], str(upper.device))
+            if key not in self._plans:
+                self._plans[key] = region_bits(key[0], key[1], self.regions, upper.device)
+            plan = self._plans[key]
+        su, ss = deterministic_scores(upper, surface, target_upper, target_surface, plan, self.clim, self.target_levels_reversed)
+        self.add(lead, su, ss)
+        return su, ss
+
+    def add(self, lead, upper_sums, surface_sums):
+        """Pools sums computed elsewhere; leading case dimensions are summed, each counting `cases` per entry."""
+        self._check_lead(lead)
+        for s in (upper_sums, surface_sums):
+            if self.names is None:
+                self.names = s.names
+            if s.names != self.names:
+                raise ValueError(f"ScoreAccumulator: sums of the regions {s.names} added to a pool of {self.names}")
+        flat_u = upper_sums.sums.double().reshape((-1,) + tuple(upper_sums.sums.shape[-4:]))
+        flat_s = surface_sums.sums.double().reshape((-1,) + tuple(surface_sums.sums.shape[-3:]))
+        if flat_u.shape[0] != flat_s.shape[0]:
+            raise ValueError("ScoreAccumulator: upper and surface sums of different numbers of cases")
+        n = flat_u.shape[0] * upper_sums.cases
+        if self._pool[lead] is None:
+            self._pool[lead] = (ScoreSums(flat_u.sum(0), self.names, n), ScoreSums(flat_s.sum(0), self.names, n))
+            return
+        for pooled, flat in zip(self._pool[lead], (flat_u, flat_s)):
+            pooled.sums.add_(flat.sum(0))
+            pooled.cases += n
+
+    def cases(self, lead):
+        self._check_lead(lead)
+        return 0 if self._pool[lead] is None else self._pool[lead][0].cases
+
+    def sums(self, lead):
+        """(upper, surface) pooled ScoreSums of a lead, sums (5, 13, R, 10) and (4, R, 10)."""
+        self._check_lead(lead)
+        if self._pool[lead] is None:
+            raise ValueError(f"ScoreAccumulator: nothing scored at lead {lead}")
+        return self._pool[lead]
+
+    def table(self, lead, metrics=SCORECARD_METRICS):
+        """The scorecard of a lead on the host: {"regions": names, "cases": n, metric: float64 numpy (69, R), ...}, the 65
+        upper-air planes (variable-major) followed by the 4 surface planes.  One device-to-host copy: the only sync."""
+        up, sf = self.sums(lead)
+        rows = [torch.cat((getattr(up, m).reshape(65, -1), getattr(sf, m).reshape(4, -1))) for m in metrics]
+        host = torch.stack(rows).cpu().numpy()
+        out = {"regions": self.names, "cases": up.cases}
+        out.update({m: host[i] for i, m in enumerate(metrics)})
+        return out
