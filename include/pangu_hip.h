@@ -665,6 +665,38 @@ int pangu_scorecard_sums_f32(pangu_stream_t stream, const float* pred, const flo
                              int clim_kind, const float* lat_weight, const unsigned char* region_bits, int R, double* sums,
                              void* workspace, long long workspace_bytes, int planes, int H, int W);
 
+/* Event verification of a deterministic forecast: the contingency table of the events pred > thr / target > thr and the sums of the
+ * Fractions Skill Score over square neighbourhoods, in one streaming pass over pred and target [planes][H][W] fp32 in physical units
+ * (csrc/events.hip pins the definitions).
+ *   Events      f = pred > thresholds[t][p], o = target > thresholds[t][p], strict; thresholds [T][planes], 1 <= T <= 4.  +inf is an
+ *               event that never happens; a comparison with NaN is false (non-finite values are not detected).
+ *   target_levels  as for pangu_scorecard_sums_f32: L > 1 reads target plane v*L + l at v*L + (L-1-l) (planes % L == 0).
+ *   Domain      a point is in the domain iff domain_bits ([H][W] bytes, e.g. a scorecard region mask) is NULL or bit domain_bit
+ *               (0..7) of its byte is set.  The domain selects CENTRE points only: every grid point feeds neighbourhood counts.
+ *   counts      [T][planes][4] over domain points: hits (f and o), false alarms (f, not o), misses (o, not f), correct negatives:
+ *               exact integers.  wsums [T][planes][4]: the same with every point weighted by lat_weight[h], in double.
+ *   radii       HOST memory, 1 <= N <= 4 strictly increasing values, 0 <= r <= 32 and 2r+1 <= W.  Radius r is the (2r+1) x (2r+1) box
+ *               of grid points around (h, w): columns wrap modulo W, rows outside 0..H-1 are absent, rows_h = min(h+r, H-1) -
+ *               max(h-r, 0) + 1, n_h = rows_h (2r+1); cf(h,w), co(h,w) are the integer numbers of f and o events in the box.
+ *   fss         [T][planes][N][2] = { sum_h s_h A_h, sum_h s_h B_h }, s_h = (double)lat_weight[h] / ((double)n_h n_h), A_h = sum over
+ *               domain points w of (cf - co)^2, B_h = sum over domain points w of (cf^2 + co^2), exact 64-bit integer row sums.
+ *               FSS = 1 - fss[0] / fss[1]; at r = 0, fss[0] = false alarms + misses and fss[1] = 2 hits + false alarms + misses,
+ *               weighted.
+ * Each (plane, row) writes its integers to workspace, >= pangu_event_scores_ws_bytes(planes, H, T, N) = planes * H * (1 + 3T + 2TN)
+ * * 8 bytes (host-only; PANGU_E_SHAPE for sizes out of range); a second launch applies the weights in double in a fixed order.  No
+ * atomics: every output is bit-identical from run to run and does not depend on which other planes, thresholds or radii are in
+ * the call.  Two launches on `stream`, no host sync; everything is checked before the first.
+ * PANGU_E_NULL: pred, target, thresholds, radii, lat_weight, counts, wsums, fss or workspace; PANGU_E_SHAPE: a non-positive size,
+ * W % 4, W > 4096, H*W >= 2^31, T or N outside 1..4, a radius outside 0..32, not above its predecessor or with 2r+1 > W,
+ * target_levels < 0 or planes % target_levels != 0, planes * ceil(H / 32) >= 2^31; PANGU_E_ARG: domain_bit outside 0..7, a workspace
+ * that is too small, or a pointer that misses its alignment: 16 B for pred, target and the workspace, 8 B for counts, wsums and fss,
+ * 4 B for thresholds, lat_weight and domain_bits. */
+long long pangu_event_scores_ws_bytes(int planes, int H, int T, int N);
+int pangu_event_scores_f32(pangu_stream_t stream, const float* pred, const float* target, int target_levels,
+                           const float* thresholds, int T, const int* radii, int N, const float* lat_weight,
+                           const unsigned char* domain_bits, int domain_bit, unsigned long long* counts, double* wsums, double* fss,
+                           void* workspace, long long workspace_bytes, int planes, int H, int W);
+
 /* Adam over a whole list of tensors in ONE launch (reference finetune_fully.py:121 torch.optim.Adam, stepped at
  * models/pangu_sample.py:75): p, grad, exp_avg, exp_avg_sq fp32, updated in place with the arithmetic of torch's fused Adam
  * (L2 weight decay added to the gradient, bias corrections, eps outside the root; doubles where that code uses doubles) -- bit

@@ -71,7 +71,7 @@ class GraphedStep:
 
 
 def rollout(model, inp, inp_surface, statistics, maps, const_h, stats_last, steps=7, graph=True, keep=False, drain=None,
-            scorecard=None, targets=None):
+            scorecard=None, targets=None, events=None):
     """`steps` chained forwards. Returns the last step's physical-unit fields (and, with keep=True, a list of the
     normalised outputs of every step, cloned).
 
@@ -86,15 +86,22 @@ def rollout(model, inp, inp_surface, statistics, maps, const_h, stats_last, step
     (target_upper, target_surface) of device tensors in physical units or None (no analysis for that lead).  After step k the
     step's physical-unit fields are scored against targets[k] and pooled at lead k (scorecard.score): two launches per tensor
     that follow the graph replay on the same stream, outside the captured graph, while the host goes on to the next step; no
-    host sync, and the returned values are unchanged."""
-    if (scorecard is None) != (targets is None):
+    host sync, and the returned values are unchanged.
+
+    events: a score.EventAccumulator with at least `steps` leads, scored against the same `targets` at the same place
+    (events.score: contingency tables and Fractions Skill Score sums, two more launches per tensor), with or without a scorecard."""
+    if (scorecard is not None and targets is None) or (targets is not None and scorecard is None and events is None):
         raise ValueError("rollout: scorecard and targets go together (a score.ScoreAccumulator and one target pair or None per step)")
-    if scorecard is not None:
+    if events is not None and targets is None:
+        raise ValueError("rollout: events needs targets (a score.EventAccumulator and one target pair or None per step)")
+    if targets is not None:
         targets = list(targets)
         if len(targets) != steps:
             raise ValueError(f"rollout: {len(targets)} targets for {steps} steps")
-        if scorecard.leads < steps:
+        if scorecard is not None and scorecard.leads < steps:
             raise ValueError(f"rollout: the scorecard holds {scorecard.leads} leads, the rollout makes {steps} steps")
+        if events is not None and events.leads < steps:
+            raise ValueError(f"rollout: the event accumulator holds {events.leads} leads, the rollout makes {steps} steps")
         for t in targets:
             if t is not None and len(t) != 2:
                 raise ValueError("rollout: a target is a pair (target_upper, target_surface) or None")
@@ -110,6 +117,8 @@ def rollout(model, inp, inp_surface, statistics, maps, const_h, stats_last, step
                     drain.submit([g.inp, g.inp_surface], tag=k)
                 if scorecard is not None and targets[k] is not None:
                     scorecard.score(k, g.inp, g.inp_surface, *targets[k])
+                if events is not None and targets[k] is not None:
+                    events.score(k, g.inp, g.inp_surface, *targets[k])
             up, sf = g.inp.clone(), g.inp_surface.clone()
         else:
             up, sf = inp, inp_surface
@@ -122,4 +131,6 @@ def rollout(model, inp, inp_surface, statistics, maps, const_h, stats_last, step
                     drain.submit([up, sf], tag=k)
                 if scorecard is not None and targets[k] is not None:
                     scorecard.score(k, up, sf, *targets[k])
+                if events is not None and targets[k] is not None:
+                    events.score(k, up, sf, *targets[k])
     return (up, sf, history) if keep else (up, sf)

@@ -1171,3 +1171,286 @@ class ScoreAccumulator:
         out = {"regions": self.names, "cases": up.cases}
         out.update({m: host[i] for i, m in enumerate(metrics)})
         return out
+
+
+# ---- event verification of deterministic forecasts: contingency scores and the Fractions Skill Score (csrc/events.hip)
+
+EVENT_MAX_T = 4                       # csrc/events.hip
+EVENT_MAX_N = 4
+EVENT_MAX_RADIUS = 32
+EVENT_MAX_W = 4096
+EVENT_SLAB_ROWS = 32                  # EV_ROWS: the rows one workgroup owns
+
+
+def event_scores_workspace_bytes(planes, H, T, N):
+    """Workspace of pangu_event_scores_f32 (include/pangu_hip.h): per (plane, row) 1 + 3 T + 2 T N 64-bit integers."""
+    return planes * H * (1 + 3 * T + 2 * T * N) * 8
+
+
+def _ratio(num, den):
+    """num / den in float64, NaN where den == 0."""
+    num, den = num.double(), den.double()
+    return torch.where(den == 0, torch.full_like(den, float("nan")), num / torch.where(den == 0, torch.ones_like(den), den))
+
+
+def _check_radii(radii, W, who):
+    try:
+        radii = tuple(int(r) for r in radii)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: radii is a sequence of integers") from None
+    if not 1 <= len(radii) <= EVENT_MAX_N:
+        raise ValueError(f"{who}: 1 <= N <= {EVENT_MAX_N} radii, got {len(radii)}")
+    for i, r in enumerate(radii):
+        if not 0 <= r <= EVENT_MAX_RADIUS:
+            raise ValueError(f"{who}: 0 <= radius <= {EVENT_MAX_RADIUS}, got {r}")
+        if i and r <= radii[i - 1]:
+            raise ValueError(f"{who}: radii must be strictly increasing, got {radii}")
+        if W is not None and 2 * r + 1 > W:
+            raise ValueError(f"{who}: the box of radius {r} is wider than the {W} columns")
+    return radii
+
+
+class EventScores:
+    """The raw event sums of pangu_event_scores_f32 for T thresholds and N radii, of one event_scores call or of a pool of `cases`
+    of them (EventAccumulator), the planes shaped (.., 5, 13) or (.., 4):
+      counts    int64 (.., T, planes.., 4): hits, false alarms, misses, correct negatives over the domain's points;
+      wsums     float64, the same four with every point weighted by its latitude weight;
+      fss_sums  float64 (.., T, planes.., N, 2): numerator and denominator of the Fractions Skill Score per radius;
+      radii     the N box radii in grid points.
+    The derived scores are float64 torch ops on these small tables, on their device and without a sync; a score whose denominator
+    is 0 is NaN."""
+
+    def __init__(self, counts, wsums, fss_sums, radii, cases=1):
+        self.counts, self.wsums, self.fss_sums, self.radii, self.cases = counts, wsums, fss_sums, tuple(int(r) for r in radii), cases
+        if counts.shape[-1] != 4 or tuple(wsums.shape) != tuple(counts.shape):
+            raise ValueError("EventScores: counts and wsums must be (..., 4) of one shape")
+        if tuple(fss_sums.shape) != tuple(counts.shape[:-1]) + (len(self.radii), 2):
+            raise ValueError("EventScores: fss_sums must be (..., N, 2) over the planes of counts, with one radius per N")
+
+    def _w(self, k):
+        return self.wsums[..., k].double()
+
+    def pod(self):
+        """Probability of detection (hit rate): hits / (hits + misses)."""
+        return _ratio(self._w(0), self._w(0) + self._w(2))
+
+    def far(self):
+        """False alarm ratio: false alarms / (hits + false alarms)."""
+        return _ratio(self._w(1), self._w(0) + self._w(1))
+
+    def csi(self):
+        """Critical success index (threat score): hits / (hits + false alarms + misses)."""
+        return _ratio(self._w(0), self._w(0) + self._w(1) + self._w(2))
+
+    def frequency_bias(self):
+        """(hits + false alarms) / (hits + misses): forecast events per observed event."""
+        return _ratio(self._w(0) + self._w(1), self._w(0) + self._w(2))
+
+    def ets(self):
+        """Equitable threat score: (hits - r) / (hits + false alarms + misses - r) with the hits of a random forecast of the same
+        frequencies, r = (hits + false alarms)(hits + misses) / total."""
+        a, b, c = self._w(0), self._w(1), self._w(2)
+        n = a + b + c + self._w(3)
+        r = _ratio((a + b) * (a + c), n)
+        return _ratio(a - r, a + b + c - r)
+
+    def base_rate(self):
+        """The weighted observed frequency: (hits + misses) / total."""
+        return _ratio(self._w(0) + self._w(2), self._w(0) + self._w(1) + self._w(2) + self._w(3))
+
+    def fss(self):
+        """The Fractions Skill Score 1 - num / den per radius, (.., T, planes.., N)."""
+        return 1.0 - _ratio(self.fss_sums[..., 0], self.fss_sums[..., 1])
+
+    def fss_useful(self):
+        """0.5 + base_rate / 2: the FSS from which a forecast counts as useful (Roberts & Lean 2008)."""
+        return 0.5 + 0.5 * self.base_rate()
+
+    def useful_radius(self):
+        """int64 (.., T, planes..): the smallest requested radius whose FSS reaches fss_useful, or -1 (none does, or NaN)."""
+        ok = self.fss() >= self.fss_useful().unsqueeze(-1)
+        r = torch.tensor(self.radii, dtype=torch.int64, device=ok.device)
+        big = EVENT_MAX_RADIUS + 1
+        first = torch.where(ok, r, torch.full_like(r, big)).amin(-1)
+        return torch.where(first == big, torch.full_like(first, -1), first)
+
+
+def _events(pred, target, target_levels, thr, T, radii, bits, bit, what):
+    """pangu_event_scores_f32 over pred / target (cases.., *plane_shape, H, W), thr (T, *plane_shape).  Returns counts, wsums
+    (cases.., T, *plane_shape, 4) and fss sums (cases.., T, *plane_shape, N, 2)."""
+    import ctypes
+    H, W = pred.shape[-2], pred.shape[-1]
+    if target.shape != pred.shape:
+        raise ValueError(f"{what}: the target is {tuple(target.shape)}, the forecast {tuple(pred.shape)}")
+    nplane = len(thr.shape) - 1
+    case_shape, plane_shape = tuple(pred.shape[:-2 - nplane]), tuple(pred.shape[-2 - nplane:-2])
+    planes = pred.numel() // (H * W)
+    per_case = thr[0].numel()
+    stream = _stream(pred)
+    p_ptr, t_ptr = _chk(pred, what), _chk(target, what + " target")
+    dev = pred.device
+    N = len(radii)
+    thr = thr.to(device=dev, dtype=torch.float32).reshape(T, 1, per_case).expand(T, planes // per_case, per_case).contiguous()
+    counts = torch.empty((T, planes, 4), dtype=torch.int64, device=dev)
+    wsums = torch.empty((T, planes, 4), dtype=torch.float64, device=dev)
+    fss = torch.empty((T, planes, N, 2), dtype=torch.float64, device=dev)
+    ws = torch.empty(event_scores_workspace_bytes(planes, H, T, N), dtype=torch.uint8, device=dev)
+    if (H, str(dev)) not in _SCORECARD_WEIGHTS:
+        _SCORECARD_WEIGHTS[(H, str(dev))] = latitude_weights(H, dev)
+    w = _SCORECARD_WEIGHTS[(H, str(dev))]
+    host_radii = (ctypes.c_int * N)(*radii)
+    _lib.check(_lib.load().pangu_event_scores_f32(
+        stream, p_ptr, t_ptr, target_levels, thr.data_ptr(), T, host_radii, N, w.data_ptr(), None if bits is None else bits.data_ptr(),
+        bit, counts.data_ptr(), wsums.data_ptr(), fss.data_ptr(), ws.data_ptr(), ws.numel(), planes, H, W), "event_scores_f32")
+    nc = len(case_shape)
+    shape = (T,) + case_shape + plane_shape
+    return (counts.reshape(shape + (4,)).movedim(0, nc), wsums.reshape(shape + (4,)).movedim(0, nc),
+            fss.reshape(shape + (N, 2)).movedim(0, nc))
+
+
+def _event_domain(H, W, regions, region, device, who):
+    """(bits, bit) of the one region to score: (None, 0) for the whole grid."""
+    if regions is None:
+        if region is not None:
+            raise ValueError(f"{who}: region {region!r} named without regions")
+        return None, 0
+    plan = regions if isinstance(regions, RegionPlan) else region_bits(H, W, regions, device)
+    if region is None or region not in plan.names:
+        raise ValueError(f"{who}: region names the one region to score, one of {plan.names}; got {region!r}")
+    if (plan.H, plan.W) != (H, W) or plan.bits.device != torch.device(device):
+        raise ValueError(f"{who}: the region plan is for a {(plan.H, plan.W)} grid on {plan.bits.device}, the fields are "
+                         f"{(H, W)} on {device}")
+    if plan.everywhere:
+        return None, 0
+    return plan.bits, plan.names.index(region)
+
+
+def event_scores(upper, surface, target_upper, target_surface, thresholds, radii=(0,), regions=None, region=None,
+                 target_levels_reversed=False):
+    """Event verification of forecasts upper (.., 5, 13, H, W) / surface (.., 4, H, W) against targets of the same shapes, all fp32
+    in physical units; leading dimensions are separate cases.  The events are x > threshold for the pair `thresholds` (T, 5, 13) /
+    (T, 4), T <= 4 (+inf: no event on that plane).  One HIP pass per tensor (pangu_event_scores_f32, definitions pinned in
+    csrc/events.hip), no host sync, bit-identical from run to run.
+
+    radii: up to 4 strictly increasing box radii in grid points, 0 <= r <= 32: the neighbourhoods of the Fractions Skill Score
+    (radius 0 is the point-wise score).  regions / region: None scores the whole grid; else a mapping as for region_bits or a
+    RegionPlan, and the name of the ONE region whose points are scored (every grid point still feeds the neighbourhoods).
+    target_levels_reversed: the upper-air target is stored with its level axis reversed.
+    Returns (upper_scores, surface_scores), two EventScores."""
+    who = "event_scores"
+    if upper.dim() < 4 or surface.dim() < 3 or tuple(upper.shape[-4:-2]) != (5, 13) or surface.shape[-3] != 4:
+        raise ValueError(f"{who}: expected upper (.., 5, 13, H, W) and surface (.., 4, H, W)")
+    if tuple(upper.shape[:-4]) != tuple(surface.shape[:-3]) or tuple(upper.shape[-2:]) != tuple(surface.shape[-2:]):
+        raise ValueError(f"{who}: upper and surface disagree in their cases or grids")
+    H, W = upper.shape[-2], upper.shape[-1]
+    if W % 4 or W > EVENT_MAX_W:
+        raise ValueError(f"{who}: W % 4 != 0 or W > {EVENT_MAX_W}")
+    if target_upper is None or target_surface is None:
+        raise ValueError(f"{who}: both targets are required")
+    if target_upper.numel() != upper.numel() or target_surface.numel() != surface.numel():
+        raise ValueError(f"{who}: the targets must hold one value per forecast value, got {tuple(target_upper.shape)} and "
+                         f"{tuple(target_surface.shape)} for {tuple(upper.shape)} and {tuple(surface.shape)}")
+    thr_u, thr_s, T = _check_thresholds(thresholds, who)
+    if T == 0:
+        raise ValueError(f"{who}: thresholds are required: a pair of tensors (T, 5, 13) and (T, 4)")
+    radii = _check_radii(radii, W, who)
+    bits, bit = _event_domain(H, W, regions, region, upper.device, who)
+    cu, wu, fu = _events(upper, target_upper.reshape(upper.shape), 13 if target_levels_reversed else 0, thr_u, T, radii, bits, bit,
+                         "events upper")
+    cs, wsf, fs = _events(surface, target_surface.reshape(surface.shape), 0, thr_s, T, radii, bits, bit, "events surface")
+    return EventScores(cu, wu, fu, radii), EventScores(cs, wsf, fs, radii)
+
+
+EVENT_METRICS = ("pod", "far", "csi", "frequency_bias", "ets", "base_rate")
+
+
+class EventAccumulator:
+    """Pools EventScores over cases, per lead: counts add in int64 and the weighted sums in float64 on their device (no host
+    sync), so pooled scores are the scores over all cases' points and the pooled FSS is 1 - sum num / sum den.  leads: the number
+    of leads (0 .. leads-1); thresholds, radii, regions, region and target_levels_reversed as for event_scores, which score()
+    calls.  The twin of ScoreAccumulator, and what rollout(events=) feeds."""
+
+    def __init__(self, leads, thresholds, radii, regions=None, region=None, target_levels_reversed=False):
+        self.leads = int(leads)
+        if self.leads < 1:
+            raise ValueError("EventAccumulator: leads must be >= 1")
+        _, _, T = _check_thresholds(thresholds, "EventAccumulator")
+        if T == 0:
+            raise ValueError("EventAccumulator: thresholds are required: a pair of tensors (T, 5, 13) and (T, 4)")
+        self.thresholds, self.T = thresholds, T
+        self.radii = _check_radii(radii, None, "EventAccumulator")
+        if regions is None and region is not None:
+            raise ValueError(f"EventAccumulator: region {region!r} named without regions")
+        self.regions, self.region, self.target_levels_reversed = regions, region, bool(target_levels_reversed)
+        self._plans = {}
+        self._pool = [None] * self.leads
+
+    def _check_lead(self, lead):
+        if not 0 <= lead < self.leads:
+            raise IndexError(f"lead {lead} outside 0..{self.leads - 1}")
+
+    def score(self, lead, upper, surface, target_upper, target_surface):
+        """event_scores of these fields, pooled at `lead`; returns the two EventScores of this call."""
+        self._check_lead(lead)
+        plan = self.regions
+        if plan is not None and not isinstance(plan, RegionPlan):
+            key = (upper.shape[-2], upper.shape[-1], str(upper.device))
+            if key not in self._plans:
+                self._plans[key] = region_bits(key[0], key[1], self.regions, upper.device)
+            plan = self._plans[key]
+        eu, es = event_scores(upper, surface, target_upper, target_surface, self.thresholds, self.radii, plan, self.region,
+                              self.target_levels_reversed)
+        self.add(lead, eu, es)
+        return eu, es
+
+    def add(self, lead, upper_scores, surface_scores):
+        """Pools sums computed elsewhere; leading case dimensions are summed, each counting `cases` per entry."""
+        self._check_lead(lead)
+        N = len(self.radii)
+        flat = []
+        for e, pshape in ((upper_scores, (5, 13)), (surface_scores, (4,))):
+            if e.radii != self.radii:
+                raise ValueError(f"EventAccumulator: scores of the radii {e.radii} added to a pool of {self.radii}")
+            tail = (self.T,) + pshape
+            if tuple(e.counts.shape[-len(tail) - 1:-1]) != tail:
+                raise ValueError(f"EventAccumulator: expected counts (.., {', '.join(map(str, tail))}, 4), got {tuple(e.counts.shape)}")
+            flat.append((e.counts.to(torch.int64).reshape((-1,) + tail + (4,)), e.wsums.double().reshape((-1,) + tail + (4,)),
+                         e.fss_sums.double().reshape((-1,) + tail + (N, 2))))
+        if flat[0][0].shape[0] != flat[1][0].shape[0]:
+            raise ValueError("EventAccumulator: upper and surface scores of different numbers of cases")
+        n = flat[0][0].shape[0] * upper_scores.cases
+        if self._pool[lead] is None:
+            self._pool[lead] = tuple(EventScores(c.sum(0), w.sum(0), f.sum(0), self.radii, n) for c, w, f in flat)
+            return
+        for pooled, (c, w, f) in zip(self._pool[lead], flat):
+            pooled.counts.add_(c.sum(0))
+            pooled.wsums.add_(w.sum(0))
+            pooled.fss_sums.add_(f.sum(0))
+            pooled.cases += n
+
+    def cases(self, lead):
+        self._check_lead(lead)
+        return 0 if self._pool[lead] is None else self._pool[lead][0].cases
+
+    def sums(self, lead):
+        """(upper, surface) pooled EventScores of a lead, counts (T, 5, 13, 4) and (T, 4, 4)."""
+        self._check_lead(lead)
+        if self._pool[lead] is None:
+            raise ValueError(f"EventAccumulator: nothing scored at lead {lead}")
+        return self._pool[lead]
+
+    def table(self, lead, metrics=EVENT_METRICS):
+        """The event scores of a lead on the host: {"cases": n, "radii": radii, metric: float64 numpy (T, 69), ..., "fss": (T, 69, N),
+        "fss_useful": (T, 69), "useful_radius": int64 (T, 69)}, the 65 upper-air planes (variable-major) followed by the 4 surface
+        planes.  One device-to-host copy: the only sync."""
+        up, sf = self.sums(lead)
+        T, N = self.T, len(self.radii)
+        both = lambda f: torch.cat((f(up).reshape(T, 65, -1), f(sf).reshape(T, 4, -1)), 1).double()
+        names = tuple(metrics) + ("fss_useful", "useful_radius")
+        cols = [both(lambda e, m=m: getattr(e, m)()) for m in names] + [both(lambda e: e.fss())]
+        host = torch.cat(cols, -1).cpu().numpy()
+        out = {"cases": up.cases, "radii": self.radii}
+        out.update({m: host[..., i] for i, m in enumerate(names)})
+        out["useful_radius"] = out["useful_radius"].astype("int64")
+        out["fss"] = host[..., len(names):]
+        return out
