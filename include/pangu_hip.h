@@ -697,6 +697,32 @@ int pangu_event_scores_f32(pangu_stream_t stream, const float* pred, const float
                            const unsigned char* domain_bits, int domain_bit, unsigned long long* counts, double* wsums, double* fss,
                            void* workspace, long long workspace_bytes, int planes, int H, int W);
 
+/* Lead-window statistics: fold ONE lead's field src [planes][plane_elems] fp32 into the accumulators of ONE window of leads, one
+ * launch on `stream`, no workspace, no atomics (csrc/leadstats.hip pins the definitions).  v = src * mul[q] + add[q] in two
+ * roundings, mul / add fp32 [planes] indexed by SOURCE plane q, both or neither (NULL: v = src), and q = p (levels = 0) or the
+ * level-reversed plane (levels = L), exactly as for pangu_regrid_planes_f32.  Every output is [planes][plane_elems], indexed by
+ * output plane p, and may be NULL (not kept); per element, with `lead` in 0..254:
+ *   first != 0 (the window's first lead): outputs are assigned and never read, so nothing needs zeroing:
+ *       sum = v; vmin = vmax = v; when_min = when_max = lead; per threshold t: e = (v > thr[t][p]), count = run = longest = e;
+ *   first == 0:
+ *       sum = sum + v (one fp32 add: the left-to-right fp32 sum in lead order);
+ *       if (v < vmin || v != v) { vmin = v; when_min = lead; }, the same with > for vmax / when_max: a NaN takes the extreme and no
+ *       number takes it back, a tie (signed zeros included) keeps the earlier lead, +-inf are numbers;
+ *       e = (v > thr[t][p]) (false for NaN); count += e; run = e ? run + 1 : 0; longest = max(longest, run).
+ *   thr fp32 [T][planes], 0 <= T <= 4, +inf: no event; count, run, longest bytes [T][planes][plane_elems]; when_min, when_max bytes.
+ *   A window holds at most 255 leads, so no byte counter wraps.
+ * Planes whose arrays all have one phase (the same number of elements, 0..3, up to a 16-B boundary of the fp32 fields and a 4-B
+ * boundary of the byte fields) are accessed 16 B / 4 B per lane after a scalar head; other planes 4 B / 1 B per lane.  Outputs are
+ * bit-identical from run to run and independent of the other planes of the launch.
+ * Checked before the launch -- PANGU_E_NULL: src; mul without add or the reverse; thr with T > 0.  PANGU_E_SHAPE: a non-positive
+ * size, plane_elems >= 2^31, levels < 0 or planes % levels != 0, T outside 0..4, lead outside 0..254, planes * ceil(plane_elems /
+ * 2048) >= 2^31.  PANGU_E_ARG: no output requested; when_min without vmin or when_max without vmax; longest without run; T > 0 with
+ * neither count nor longest; T == 0 with count, run or longest; an fp32 pointer that is not 4-B aligned. */
+int pangu_lead_stats_update_f32(pangu_stream_t stream, const float* src, const float* mul, const float* add, float* sum, float* vmin,
+                                float* vmax, unsigned char* when_min, unsigned char* when_max, const float* thr, int T,
+                                unsigned char* count, unsigned char* run, unsigned char* longest, int planes, long long plane_elems,
+                                int levels, int lead, int first);
+
 /* Adam over a whole list of tensors in ONE launch (reference finetune_fully.py:121 torch.optim.Adam, stepped at
  * models/pangu_sample.py:75): p, grad, exp_avg, exp_avg_sq fp32, updated in place with the arithmetic of torch's fused Adam
  * (L2 weight decay added to the gradient, bias corrections, eps outside the root; doubles where that code uses doubles) -- bit

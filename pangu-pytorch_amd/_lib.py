@@ -89,6 +89,7 @@ SIGNATURES = {
     "pangu_scorecard_sums_f32": [_P, _P, _P, _I, _P, _I, _P, _P, _I, _P, _P, _c.c_longlong, _I, _I, _I],
     "pangu_event_scores_ws_bytes": [_I, _I, _I, _I],
     "pangu_event_scores_f32": [_P, _P, _P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _c.c_longlong, _I, _I, _I],
+    "pangu_lead_stats_update_f32": [_P] * 10 + [_I, _P, _P, _P, _I, _c.c_longlong, _I, _I, _I],
     "pangu_window_attn_bwd_bf16": [_P] * 10 + [_I] * 6,
     "pangu_ln_residual_bwd_bf16": [_P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _F],
     "pangu_downsample_ln_bwd_bf16": [_P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P],

@@ -234,6 +234,12 @@ class EnsembleRollout:
             out["error"] = score.zonal_spectrum(mu, ms, target, target_surface, **kw)
         return out
 
+    def update_lead_stats(self, agg, lead):
+        """Fold the current member state into the lead windows of agg (a score.LeadWindowStats built without stats_last) at `lead`:
+        per-member window means, extremes and spell lengths, leading dimension E.  score.ensemble_scores, ensemble_quantiles and
+        ensemble_reliability(want_fields=True) of agg.result(w)'s fields give their probabilities."""
+        agg.update(lead, self.upper, self.surface)
+
     @staticmethod
     def product_names(mean_std=True, quantiles=None, thresholds=None):
         """The names of the tensors products() returns for the same arguments, in its order."""
@@ -266,7 +272,7 @@ class EnsembleRollout:
 
 def ensemble_rollout(model, inp, inp_surface, statistics, maps, const_h, stats_last, members, amplitude, steps=7, seed=0,
                      chunk=None, targets=None, reliability=None, thresholds=None, drain=None, products=None, quantile_levels=None,
-                     **perturb_kw):
+                     *, lead_stats=None, **perturb_kw):
     """`steps` steps of an EnsembleRollout.  Returns the final member state (upper, surface); with targets (a list of
     (target, target_surface) per step) also the list of per-step score dicts.  With reliability (a score.ReliabilityAccumulator
     of at least `steps` leads; needs targets) step k's reliability tables against targets[k], for the events x > thresholds,
@@ -277,7 +283,12 @@ def ensemble_rollout(model, inp, inp_surface, statistics, maps, const_h, stats_l
     the step index; the pack launches follow the replays on the same stream, with no host synchronisation here.  A drain built
     with regrid=(H_out, W_out) delivers the products on that coarser grid (remapped on the device), with no change here.
     quantile_levels (needs targets): step k's history entry becomes (upper_scores, surface_scores, upper_quantiles,
-    surface_quantiles), the last two the score.QuantileResult of quantile_scores against targets[k]."""
+    surface_quantiles), the last two the score.QuantileResult of quantile_scores against targets[k].
+    lead_stats: a score.LeadWindowStats (built WITHOUT stats_last) whose windows all end within `steps`: after step k the member
+    state is folded into every window that holds lead k (EnsembleRollout.update_lead_stats); the statistics are per member, their
+    leading dimension is E.  The return value is unchanged."""
+    from .rollout import check_lead_stats
+    check_lead_stats(lead_stats, steps, "ensemble_rollout")
     if reliability is not None and targets is None:
         raise ValueError("ensemble_rollout: reliability needs targets")
     if reliability is None and thresholds is not None:
@@ -310,5 +321,7 @@ def ensemble_rollout(model, inp, inp_surface, statistics, maps, const_h, stats_l
                 reliability.add(k, *ens.reliability(*targets[k], thresholds=thresholds, seed=seed))
             if drain is not None:
                 drain.submit(ens.products(**product_kw), tag=k)
+            if lead_stats is not None:
+                ens.update_lead_stats(lead_stats, k)
         up, sf = ens.state()
     return (up, sf, history) if targets is not None else (up, sf)

@@ -70,8 +70,19 @@ class GraphedStep:
         return self.out, self.out_surface
 
 
+def check_lead_stats(lead_stats, steps, who):
+    """What rollout(lead_stats=) and ensemble.ensemble_rollout(lead_stats=) ask of a score.LeadWindowStats, before the first step."""
+    if lead_stats is None:
+        return
+    if getattr(lead_stats, "stats_last", None) is not None:
+        raise ValueError(f"{who}: lead_stats must be built without stats_last (it is handed physical fields)")
+    end = max(b for _, b in lead_stats.windows)
+    if steps < end:
+        raise ValueError(f"{who}: {steps} steps do not reach the end of every lead window (the last ends at lead {end})")
+
+
 def rollout(model, inp, inp_surface, statistics, maps, const_h, stats_last, steps=7, graph=True, keep=False, drain=None,
-            scorecard=None, targets=None, events=None):
+            scorecard=None, targets=None, events=None, *, lead_stats=None):
     """`steps` chained forwards. Returns the last step's physical-unit fields (and, with keep=True, a list of the
     normalised outputs of every step, cloned).
 
@@ -89,7 +100,14 @@ def rollout(model, inp, inp_surface, statistics, maps, const_h, stats_last, step
     host sync, and the returned values are unchanged.
 
     events: a score.EventAccumulator with at least `steps` leads, scored against the same `targets` at the same place
-    (events.score: contingency tables and Fractions Skill Score sums, two more launches per tensor), with or without a scorecard."""
+    (events.score: contingency tables and Fractions Skill Score sums, two more launches per tensor), with or without a scorecard.
+
+    lead_stats: a score.LeadWindowStats (built WITHOUT stats_last: it is handed physical fields) whose windows all end within
+    `steps`.  After step k the step's physical-unit fields are folded into every window that holds lead k (lead_stats.update: one
+    launch per tensor and window, behind the graph replay on the same stream, outside the captured graph, no host sync); the
+    window means, extremes and spell lengths are then read from lead_stats.result(w) (lead_stats.reset() before the next rollout).
+    The returned values are unchanged."""
+    check_lead_stats(lead_stats, steps, "rollout")
     if (scorecard is not None and targets is None) or (targets is not None and scorecard is None and events is None):
         raise ValueError("rollout: scorecard and targets go together (a score.ScoreAccumulator and one target pair or None per step)")
     if events is not None and targets is None:
@@ -119,6 +137,8 @@ def rollout(model, inp, inp_surface, statistics, maps, const_h, stats_last, step
                     scorecard.score(k, g.inp, g.inp_surface, *targets[k])
                 if events is not None and targets[k] is not None:
                     events.score(k, g.inp, g.inp_surface, *targets[k])
+                if lead_stats is not None:
+                    lead_stats.update(k, g.inp, g.inp_surface)
             up, sf = g.inp.clone(), g.inp_surface.clone()
         else:
             up, sf = inp, inp_surface
@@ -133,4 +153,6 @@ def rollout(model, inp, inp_surface, statistics, maps, const_h, stats_last, step
                     scorecard.score(k, up, sf, *targets[k])
                 if events is not None and targets[k] is not None:
                     events.score(k, up, sf, *targets[k])
+                if lead_stats is not None:
+                    lead_stats.update(k, up, sf)
     return (up, sf, history) if keep else (up, sf)

@@ -1454,3 +1454,244 @@ class EventAccumulator:
         out["useful_radius"] = out["useful_radius"].astype("int64")
         out["fss"] = host[..., len(names):]
         return out
+
+
+# ---- statistics across the leads of a rollout: window means, extremes and their leads, exceedance counts, spell lengths ----------
+
+LEAD_MAX_WINDOWS = 4
+LEAD_MAX_LEADS = 255                  # csrc/leadstats.hip: the byte counters and when_* hold 0..255
+LEAD_STATS = ("mean", "min", "max", "when_min", "when_max", "count", "longest_spell")
+
+
+class LeadWindowResult:
+    """The statistics of one complete lead window [a, b), every entry an (upper, surface) pair shaped like the submitted fields, or
+    None where that statistic was not kept:
+      window          (a, b), and n = b - a, the number of leads;
+      sum, mean       fp32: the left-to-right fp32 sum in lead order, and sum / n;
+      min, max        fp32 (a NaN at any lead gives NaN);
+      when_min/_max   uint8: the absolute lead of the extreme (the earliest on a tie);
+      count           uint8 (.., T, 5, 13, H, W) / (.., T, 4, H, W): the leads with x > threshold, T placed as in EventScores;
+      longest_spell   uint8, the same shape: the longest run of consecutive such leads."""
+
+    def __init__(self, window, **pairs):
+        self.window = tuple(window)
+        self.n = self.window[1] - self.window[0]
+        for name in ("sum", "mean", "min", "max", "when_min", "when_max", "count", "longest_spell"):
+            setattr(self, name, pairs.get(name))
+
+
+def _lead_stats_launch(stream, src_ptr, mul, add, fields, thr, T, planes, plane_elems, levels, lead, first):
+    """pangu_lead_stats_update_f32; fields: a dict of the kept device tensors among sum, min, max, when_min, when_max, count, run,
+    longest; mul / add / thr device tensors or None."""
+    ptr = lambda t: None if t is None else t.data_ptr()
+    f = lambda k: ptr(fields.get(k))
+    _lib.check(_lib.load().pangu_lead_stats_update_f32(
+        stream, src_ptr, ptr(mul), ptr(add), f("sum"), f("min"), f("max"), f("when_min"), f("when_max"), ptr(thr) if T else None, T,
+        f("count"), f("run"), f("longest"), planes, plane_elems, levels, lead, 1 if first else 0), "lead_stats_update_f32")
+
+
+class LeadWindowStats:
+    """Statistics across the leads of a rollout, kept on the device: per window of leads the mean field, the minimum and maximum
+    with the leads at which they occur, the number of leads above a threshold and the longest run of consecutive such leads.
+
+        agg = LeadWindowStats(windows=[(0, 7), (0, 3), (3, 7)], stats=("mean", "max", "when_max", "count", "longest_spell"),
+                              thresholds=(thr_upper (T,5,13), thr_surface (T,4)))
+        for k in range(7): ...; agg.update(k, upper, surface)          # or rollout(..., lead_stats=agg)
+        week = agg.result(0); week.mean, week.max, week.when_max, week.count, week.longest_spell
+
+    windows          up to 4 half-open lead ranges [a, b), 0 <= a < b <= 255; they may overlap and need not start at 0.
+    stats            a subset of mean, min, max, when_min, when_max, count, longest_spell; when_* keeps its extreme too.
+    thresholds       for count / longest_spell (and only with one of them): the events x > threshold, a pair (T, 5, 13) / (T, 4) in
+                     physical units in the model's level order, T <= 4, +inf: no event on that plane.
+    stats_last       the 4-tuple of rollout.norm_back: the submitted fields are NORMALISED model outputs and are de-normalised by the
+                     kernel (per stored plane, as data.HostDrain(stats_last=) does).  None: they are physical already.
+    levels_reversed  the upper-air tensor is stored with ascending levels (an analysis read from disk); reversed by addressing.
+
+    update(lead, upper, surface) takes upper (.., 5, 13, H, W) and surface (.., 4, H, W), contiguous fp32 device tensors; leading
+    dimensions (ensemble members, cases) are simply more planes, with statistics of their own.  It issues one launch per tensor per
+    window that holds `lead` (pangu_lead_stats_update_f32, definitions pinned in csrc/leadstats.hip) on the current stream, with no
+    host sync; a lead in no window issues none.  Leads arrive in strictly increasing order and every lead of a window must arrive.
+
+    Storage is allocated at the first update, per window and element: 4 B each for mean (its sum), min and max, 1 B each for
+    when_min and when_max, and per threshold 1 B for count and 2 B for longest_spell (the current run and the longest).  bytes()
+    gives the total.  It is what an ensemble pays: E = 50 members x (mean, min, max) x one window is 50 x 69 x 721 x 1440 x 12 B,
+    about 43 GB -- keep per-member statistics of few windows, or reduce the members first.
+
+    The results compose with what exists: deterministic_scores of two window means is the weekly-mean scorecard, ensemble_scores /
+    ensemble_quantiles / ensemble_reliability(want_fields=True) of per-member results give the probabilistic products, and
+    data.HostDrain ships products(w)."""
+
+    def __init__(self, windows, stats=("mean",), thresholds=None, stats_last=None, levels_reversed=False):
+        who = "LeadWindowStats"
+        try:
+            self.windows = tuple((int(a), int(b)) for a, b in windows)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: windows is a sequence of (first lead, end lead) pairs") from None
+        if not 1 <= len(self.windows) <= LEAD_MAX_WINDOWS:
+            raise ValueError(f"{who}: 1..{LEAD_MAX_WINDOWS} windows, got {len(self.windows)}")
+        for a, b in self.windows:
+            if not 0 <= a < b <= LEAD_MAX_LEADS:
+                raise ValueError(f"{who}: a window [a, b) needs 0 <= a < b <= {LEAD_MAX_LEADS}, got ({a}, {b})")
+        stats = (stats,) if isinstance(stats, str) else tuple(stats)
+        for s in stats:
+            if s not in LEAD_STATS:
+                raise ValueError(f"{who}: unknown statistic {s!r}; the statistics are {LEAD_STATS}")
+        if not stats:
+            raise ValueError(f"{who}: no statistic requested")
+        self.stats = tuple(s for s in LEAD_STATS if s in stats)
+        thr_u, thr_s, T = _check_thresholds(thresholds, who)
+        events = "count" in self.stats or "longest_spell" in self.stats
+        if events and T == 0:
+            raise ValueError(f"{who}: count and longest_spell need thresholds, a pair of tensors (T, 5, 13) and (T, 4)")
+        if T and not events:
+            raise ValueError(f"{who}: thresholds are used only by count and longest_spell")
+        self.thresholds, self.T = ((thr_u, thr_s) if T else None), T
+        self.stats_last, self.levels_reversed = stats_last, bool(levels_reversed)
+        kept = []                                       # the kernel's fields, in its argument order
+        if "mean" in self.stats:
+            kept.append("sum")
+        for ext in ("min", "max"):
+            if ext in self.stats or "when_" + ext in self.stats:
+                kept.append(ext)
+        kept += [w for w in ("when_min", "when_max") if w in self.stats]
+        if "count" in self.stats:
+            kept.append("count")
+        if "longest_spell" in self.stats:
+            kept += ["run", "longest"]
+        self._kept = tuple(kept)
+        self._shapes = None                             # (upper shape, surface shape, device) of the first update
+        self._acc = None                                # per window: (upper fields, surface fields), dicts of device tensors
+        self._aux = None                                # per tensor: (mul, add, thr) device tensors or None
+        self.reset()
+
+    def reset(self):
+        """Forget every lead (a new rollout); the accumulators stay allocated and need no clearing."""
+        self._last = -1
+        self._seen = [0] * len(self.windows)
+
+    def _check_window(self, w):
+        if not 0 <= w < len(self.windows):
+            raise IndexError(f"window {w} outside 0..{len(self.windows) - 1}")
+
+    def complete(self, w):
+        """True once every lead of window w has arrived."""
+        self._check_window(w)
+        a, b = self.windows[w]
+        return self._seen[w] == b - a
+
+    def bytes(self):
+        """The accumulators' footprint on the device (0 before the first update)."""
+        if self._acc is None:
+            return 0
+        return sum(t.numel() * t.element_size() for pair in self._acc for fields in pair for t in fields.values())
+
+    def _field_shape(self, key, shape):
+        return ((self.T,) if key in ("count", "run", "longest") else ()) + tuple(shape)
+
+    def _allocate(self, upper, surface):
+        dev = upper.device
+        self._aux = []
+        for t, pshape, thr in ((upper, (5, 13), self.thresholds[0] if self.T else None),
+                               (surface, (4,), self.thresholds[1] if self.T else None)):
+            mul = add = None
+            if self.stats_last is not None:
+                s_mean, s_std, u_mean, u_std = self.stats_last
+                mean, std = (u_mean, u_std) if len(pshape) == 2 else (s_mean, s_std)
+                lead = tuple(t.shape[:-2]) + (1, 1)
+                expand = lambda v: v.to(device=dev, dtype=torch.float32).reshape(pshape + (1, 1)).expand(lead).contiguous().view(-1)
+                mul, add = expand(std), expand(mean)
+            if thr is not None:
+                per = thr[0].numel()
+                planes = t.numel() // (t.shape[-1] * t.shape[-2])
+                thr = thr.to(device=dev, dtype=torch.float32).reshape(self.T, 1, per).expand(self.T, planes // per, per).contiguous()
+            self._aux.append((mul, add, thr))
+        dtype = lambda k: torch.float32 if k in ("sum", "min", "max") else torch.uint8
+        self._acc = [tuple({k: torch.empty(self._field_shape(k, t.shape), dtype=dtype(k), device=dev) for k in self._kept}
+                           for t in (upper, surface)) for _ in self.windows]
+
+    def update(self, lead, upper, surface):
+        """Fold the fields of `lead` into every window that holds it."""
+        lead = int(lead)
+        shapes = self._check_update(lead, upper, surface)
+        self._fold(lead, upper, surface)
+        self._shapes = shapes
+        for w, (a, b) in enumerate(self.windows):
+            if a <= lead < b:
+                self._seen[w] += 1
+        self._last = lead
+
+    def _check_update(self, lead, upper, surface):
+        """Everything update() refuses before a device call; returns (upper shape, surface shape, device)."""
+        who = "LeadWindowStats.update"
+        if not 0 <= lead < LEAD_MAX_LEADS:
+            raise IndexError(f"{who}: lead {lead} outside 0..{LEAD_MAX_LEADS - 1}")
+        if lead <= self._last:
+            raise ValueError(f"{who}: leads must arrive in strictly increasing order, got {lead} after {self._last}")
+        for (a, b), seen in zip(self.windows, self._seen):
+            if seen < b - a and lead >= a and lead != a + seen:
+                raise ValueError(f"{who}: window ({a}, {b}) expects lead {a + seen} next, got {lead}: every lead of a window must arrive")
+        for t, name in ((upper, "upper"), (surface, "surface")):
+            if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.is_contiguous()):
+                raise ValueError(f"{who}: {name} must be a contiguous float32 tensor")
+        if upper.dim() < 4 or surface.dim() < 3 or tuple(upper.shape[-4:-2]) != (5, 13) or surface.shape[-3] != 4:
+            raise ValueError(f"{who}: expected upper (.., 5, 13, H, W) and surface (.., 4, H, W)")
+        if tuple(upper.shape[:-4]) != tuple(surface.shape[:-3]) or tuple(upper.shape[-2:]) != tuple(surface.shape[-2:]):
+            raise ValueError(f"{who}: upper and surface disagree in their leading dimensions or grids")
+        if upper.numel() == 0 or upper.device != surface.device:
+            raise ValueError(f"{who}: empty tensors, or upper and surface on different devices")
+        shapes = (tuple(upper.shape), tuple(surface.shape), upper.device)
+        if self._shapes is not None and shapes != self._shapes:
+            raise ValueError(f"{who}: shapes and device must stay those of the first update, {self._shapes}; got {shapes}")
+        return shapes
+
+    def _fold(self, lead, upper, surface):
+        """The device side of update(): the accumulators (at the first call) and one launch per tensor and window that holds lead."""
+        if not upper.is_cuda:
+            raise RuntimeError(f"LeadWindowStats.update: the Pangu HIP path needs tensors on an MI355X device (got {upper.device}); "
+                               "there is no CPU fallback")
+        stream = _stream(upper)
+        if self._acc is None:
+            self._allocate(upper, surface)
+        elems = upper.shape[-1] * upper.shape[-2]
+        for w, (a, b) in enumerate(self.windows):
+            if not a <= lead < b:
+                continue
+            for t, fields, (mul, add, thr), levels in zip((upper, surface), self._acc[w], self._aux,
+                                                          (13 if self.levels_reversed else 0, 0)):
+                _lead_stats_launch(stream, t.data_ptr(), mul, add, fields, thr, self.T, t.numel() // elems, elems, levels, lead,
+                                   lead == a)
+
+    def _stat_pair(self, w, stat):
+        key = {"mean": "sum", "longest_spell": "longest"}.get(stat, stat)
+        pair = tuple(fields[key] for fields in self._acc[w])
+        if stat == "mean":
+            n = self.windows[w][1] - self.windows[w][0]
+            return tuple(t / float(n) for t in pair)
+        if stat in ("count", "longest_spell"):          # (T, cases.., planes.., H, W) -> T behind the cases, as in EventScores
+            return tuple(t.movedim(0, t.dim() - 1 - nplane - 2) for t, nplane in zip(pair, (2, 1)))
+        return pair
+
+    def result(self, w):
+        """The LeadWindowResult of window w, once it is complete.  The tensors are the live accumulators (or views of them): clone
+        what must outlive the next reset() and update()."""
+        if not self.complete(w):
+            a, b = self.windows[w]
+            raise ValueError(f"LeadWindowStats: window ({a}, {b}) is incomplete: {self._seen[w]} of {b - a} leads have arrived")
+        pairs = {s: self._stat_pair(w, s) for s in self.stats}
+        for ext in ("min", "max"):
+            if ext in self._kept:
+                pairs[ext] = self._stat_pair(w, ext)
+        if "sum" in self._kept:
+            pairs["sum"] = self._stat_pair(w, "sum")
+        return LeadWindowResult(self.windows[w], **pairs)
+
+    def product_names(self, w):
+        """The names of the tensors products(w) returns, in its order: <statistic>_upper, <statistic>_surface per statistic."""
+        self._check_window(w)
+        return [f"{s}_{part}" for s in self.stats for part in ("upper", "surface")]
+
+    def products(self, w):
+        """The statistics of the complete window w as an ordered list of contiguous fp32 tensors (the byte fields converted), in the
+        order of `stats`: what a data.HostDrain built without stats_last accepts; product_names(w) names the entries."""
+        r = self.result(w)
+        return [t.to(torch.float32).contiguous() for s in self.stats for t in getattr(r, s)]
