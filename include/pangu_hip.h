@@ -182,6 +182,15 @@ int pangu_window_attn_fwd(pangu_stream_t stream, const float* qkv, const float* 
 int pangu_window_attn_fwd_compact(pangu_stream_t stream, const float* qkv, const float* qkv_bias,
                                   const float* esb_compact, float* out, float* lse, int Z, int H, int W, int C,
                                   int heads, int shifted);
+/* The same two forwards for frozen INFERENCE with both contractions computed as exact-split bf16 MFMA products (each fp32 operand
+ * the exact sum of three bf16 values, six products per term into one fp32 accumulator: csrc/attn_f32_split.hip); error at the
+ * level of the fp32-MFMA kernel's own.  No lse is produced: training keeps pangu_window_attn_fwd.  The two bias modes are
+ * bit-identical to each other. */
+int pangu_window_attn_fwd_split(pangu_stream_t stream, const float* qkv, const float* qkv_bias, const float* esb,
+                                float* out, int Z, int H, int W, int C, int heads, int shifted);
+int pangu_window_attn_fwd_split_compact(pangu_stream_t stream, const float* qkv, const float* qkv_bias,
+                                        const float* esb_compact, float* out, int Z, int H, int W, int C, int heads,
+                                        int shifted);
 
 /* EarthAttention3D.forward's own calling convention (reference layers.py:360-421, the part between linear1 and linear2) for
  * callers that use the module OUTSIDE EarthSpecificBlock: the tensor is already partitioned and the mask is explicit.

@@ -91,12 +91,13 @@ def _plain_proj(blk, lin, x2, act=ops.ACT_NONE):
     return ops.linear(x2, w, lin.bias, act=act)
 
 
-# (N, K) of the fused projections that stay on the fp32-MFMA kernel although the split kernel serves them and is faster (1.5 x): the
-# stage-1/2 attention out-projection.  With all four shapes on the split kernel the 7-step rollout's step-7 fingerprint error against
-# the reference reads 1.04e-3, over the 1e-3 that tests/test_gpu_rollout.py allows (8.74e-4 before); that figure moves between
-# 8.5e-4 and 1.5e-3 over the 16 subsets of the four shapes, each of them more accurate per launch than the fp32 kernel
-# (profiles/f32_split_ln_per_shape.md), and the subset without this shape reads 8.54e-4.
-_LN_SPLIT_NOT_DISPATCHED = {(384, 384)}
+# (N, K) of the fused projections that stay on the fp32-MFMA kernel although the split kernel serves them.  Empty since the attention
+# core runs as exact-split products too: the 7-step rollout's step-7 fingerprint error against the reference, which
+# tests/test_gpu_rollout.py bounds by 1e-3, moves between 7.5e-4 and 1.5e-3 with rounding detail alone (each arm more accurate per
+# launch than the fp32 kernel: profiles/f32_split_ln_per_shape.md).  It kept the stage-1/2 attention out-projection (384, 384) here
+# while the attention core was fp32 MFMA (8.54e-4 without it, 1.04e-3 with it); over the eight subsets of that shape and the two
+# attention stages (profiles/attn_f32_split_rollout.md) the one with everything dispatched reads 7.46e-4 and is the fastest.
+_LN_SPLIT_NOT_DISPATCHED = set()
 
 
 def _ln_proj(blk, lin, x2, shortcut, norm, out=None, branch_scale=1.0):
@@ -112,9 +113,17 @@ def _ln_proj(blk, lin, x2, shortcut, norm, out=None, branch_scale=1.0):
     return ops.linear_ln_residual(x2, w, lin.bias, shortcut, norm.weight, norm.bias, out=out, branch_scale=branch_scale)
 
 
+# C of the blocks whose attention core stays on the fp32-MFMA kernel (csrc/attn_f32.hip) although the exact-split kernel
+# (csrc/attn_f32_split.hip) serves them: same form and same reason as _LN_SPLIT_NOT_DISPATCHED; empty for the same measurement
+# (profiles/attn_f32_split_rollout.md: with attention split at C = 384 only, step 7 reads 1.11e-3).
+_ATTN_SPLIT_NOT_DISPATCHED = set()
+
+
 def _block_rows(blk, x2, B, Z, H, W, roll, out=None):
     """The inference composition of a block on the 2-D rows x2 (B*N, C) of B samples -> (B*N, C), written into the 2-D `out` if
-    given: 5 kernel launches per sample (qkv, attention core, proj+LN+residual, MLP-up+GELU, MLP-down+LN+residual)."""
+    given: 5 kernel launches per sample (qkv, attention core, proj+LN+residual, MLP-up+GELU, MLP-down+LN+residual).  With the
+    block's split_projections flag set (PanguModel.use_split_projections) the attention core is the exact-split bf16-MFMA kernel
+    for every C not in _ATTN_SPLIT_NOT_DISPATCHED, like the projections around it; otherwise the fp32-MFMA kernel."""
     N, C = x2.shape[0] // B, x2.shape[1]
     att = blk.attention
     s1, s2 = drop_path_scales(blk)
@@ -128,9 +137,10 @@ def _block_rows(blk, x2, B, Z, H, W, roll, out=None):
                 att._esb_compact = esb_c = None
         cp = esb_c is not None
         esb = esb_c if cp else att.earth_specific_bias[0]
+        sp = bool(getattr(blk, "split_projections", True)) and C not in _ATTN_SPLIT_NOT_DISPATCHED
         o = torch.cat([ops.window_attention(qkv[b * N:(b + 1) * N], att.linear1.bias, esb, Z, H, W,
-                                            att.head_number, roll, compact=cp) for b in range(B)], 0) if B > 1 else \
-            ops.window_attention(qkv, att.linear1.bias, esb, Z, H, W, att.head_number, roll, compact=cp)
+                                            att.head_number, roll, compact=cp, split=sp) for b in range(B)], 0) if B > 1 else \
+            ops.window_attention(qkv, att.linear1.bias, esb, Z, H, W, att.head_number, roll, compact=cp, split=sp)
         if C in (192, 384):     # projection + post-norm residual in one launch (the GEMM tile spans the row)
             x1 = _ln_proj(blk, att.linear2, o, x2, blk.norm1, branch_scale=s1)
         else:

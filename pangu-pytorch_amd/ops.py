@@ -634,10 +634,14 @@ def lora_merge(W, A, B, scaling, out=None):
     return out
 
 
-def window_attention(qkv, qkv_bias, esb, Z, H, W, heads, shifted, want_lse=False, compact=False):
+def window_attention(qkv, qkv_bias, esb, Z, H, W, heads, shifted, want_lse=False, compact=False, split=False):
     """esb: the expanded (types, heads, 144, 144) table, or with compact=True the paper's compact table laid out
-    (types, heads, 3312) (weights.compact_bias_table): same result bit for bit, 6.3x fewer bias bytes."""
+    (types, heads, 3312) (weights.compact_bias_table): same result bit for bit, 6.3x fewer bias bytes.
+    split=True: the inference-only kernel that runs both contractions as exact-split bf16 MFMA products
+    (csrc/attn_f32_split.hip); it produces no lse."""
     lib = _lib.load()
+    if split and want_lse:
+        raise RuntimeError("window_attention: the exact-split kernel is inference only and produces no lse")
     N, C3 = qkv.shape
     C = C3 // 3
     if N != Z * H * W:
@@ -650,6 +654,11 @@ def window_attention(qkv, qkv_bias, esb, Z, H, W, heads, shifted, want_lse=False
     lse = torch.empty((N, heads), dtype=torch.float32, device=qkv.device) if want_lse else None
     Np = (Z // 2) * ((H + 5) // 6) * (W // 12) * 144          # padded token count: the core's FLOPs (4*Np*144*C)
     with _timed("attn", 4.0 * Np * 144 * C):
+        if split:
+            fn = lib.pangu_window_attn_fwd_split_compact if compact else lib.pangu_window_attn_fwd_split
+            _lib.check(fn(_stream(qkv), _chk(qkv, "qkv"), _chk(qkv_bias, "qkv_bias"), _chk(esb, "esb"), out.data_ptr(),
+                          Z, H, W, C, heads, int(shifted)), "window_attn_fwd_split")
+            return out
         fn = lib.pangu_window_attn_fwd_compact if compact else lib.pangu_window_attn_fwd
         _lib.check(fn(_stream(qkv), _chk(qkv, "qkv"), _chk(qkv_bias, "qkv_bias"), _chk(esb, "esb"), out.data_ptr(),
                       lse.data_ptr() if want_lse else None, Z, H, W, C, heads, int(shifted)), "window_attn_fwd")

@@ -127,14 +127,16 @@ class PanguModel(nn.Module):
         return self
 
     def use_split_projections(self, enable=True):
-        """Frozen fp32 INFERENCE runs the four projections of every block on the bf16 matrix pipe as exact-split products: the
-        plain ones (qkv, MLP-up + GELU: csrc/gemm_f32_split.hip) and the ones fused with LayerNorm + residual (attention
-        out-projection, MLP-down: csrc/gemm_ln_f32_split.hip); both run the main loop of csrc/split_f32.h.  Each fp32 operand is the exact sum of three bf16 values; the error
-        is at the level of the fp32-MFMA kernels' own.  The per-weight images are made once and cached under
-        the weight's stamp: 6 bytes per weight element, about 130 MB for the whole model (80 MB of it the plain projections'; the
-        C = 384 out-projection stays on the fp32-MFMA kernel and has no image: fused._LN_SPLIT_NOT_DISPATCHED).  This is the default; `use_split_projections(False)` selects the fp32-MFMA kernels for all four and
-        drops the images.  LoRA layers compute on the image of their merged weight; training and the bf16 path never take the
-        split kernels."""
+        """Frozen fp32 INFERENCE runs every contraction of a block on the bf16 matrix pipe as exact-split products: the plain
+        projections (qkv, MLP-up + GELU: csrc/gemm_f32_split.hip), the ones fused with LayerNorm + residual (attention
+        out-projection, MLP-down: csrc/gemm_ln_f32_split.hip; both run the main loop of csrc/split_f32.h) and the window-attention
+        core (QK^T and PV: csrc/attn_f32_split.hip).  Each fp32 operand is the exact sum of three bf16 values; the error is at the
+        level of the fp32-MFMA kernels' own.  The per-weight images are made once and cached under the
+        weight's stamp: 6 bytes per weight element, about 140 MB for the whole model (80 MB of it the plain projections'); the
+        attention core needs no image (q, k, v and the probabilities are split inside the kernel).  Shapes listed in
+        fused._LN_SPLIT_NOT_DISPATCHED / fused._ATTN_SPLIT_NOT_DISPATCHED (both empty) would stay on the fp32-MFMA kernels.  This is
+        the default; `use_split_projections(False)` selects the fp32-MFMA kernels throughout and drops the images.  LoRA layers
+        compute on the image of their merged weight; training and the bf16 path never take the split kernels."""
         for m in self.modules():
             if isinstance(m, EarthSpecificBlock):
                 m.split_projections = bool(enable)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-shape kernel micro-benchmarks on one MI355X (development tool, not the headline bench).
 
-  python tools/bench_kernels.py gemm|attn|rows|mlp_fused|... [--lib-compare]
+  python tools/bench_kernels.py gemm|attn|attn_f32|rows|mlp_fused|... [--lib-compare]
 `--lib-compare` also times torch.matmul (hipBLASLt/rocBLAS) on the same shapes as an external yardstick."""
 import os
 import sys
@@ -240,6 +240,25 @@ def attn():
                   f"   | compact bias table {msc:7.3f} ms  {fl / msc / 1e9:6.1f} TF/s")
 
 
+def attn_f32():
+    """The fp32 forward's two attention kernels side by side: fp32 MFMA (csrc/attn_f32.hip) and exact-split bf16 MFMA
+    (csrc/attn_f32_split.hip), both stages, unshifted / shifted, expanded / compact bias table."""
+    for C, Z, H, W, heads, types in ((192, 8, 181, 360, 6, 124), (384, 8, 91, 180, 12, 64)):
+        N = Z * H * W
+        qkv = torch.randn(N, 3 * C, device="cuda")
+        b1 = torch.randn(3 * C, device="cuda")
+        tables = {"expanded": torch.randn(types, heads, 144, 144, device="cuda") * 0.1,
+                  "compact": torch.randn(types, heads, 3312, device="cuda") * 0.1}
+        fl = 4.0 * (Z // 2) * ((H + 5) // 6) * (W // 12) * 144 * 144 * C
+        for sh in (False, True):
+            for mode, esb in tables.items():
+                cp = mode == "compact"
+                ms = timeit(lambda: ops.window_attention(qkv, b1, esb, Z, H, W, heads, sh, compact=cp))
+                mss = timeit(lambda: ops.window_attention(qkv, b1, esb, Z, H, W, heads, sh, compact=cp, split=True))
+                print(f"attn_f32 C={C} shifted={int(sh)} {mode:8s}: fp32 MFMA {ms:7.3f} ms {fl / ms / 1e9:6.1f} TF/s   | split "
+                      f"{mss:7.3f} ms {fl / mss / 1e9:6.1f} TF/s   | {ms / mss:5.2f}x")
+
+
 def rows():
     for N, C in ((521280, 192), (131040, 384)):
         y, s = torch.randn(N, C, device="cuda"), torch.randn(N, C, device="cuda")
@@ -260,6 +279,6 @@ def rows():
 
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "gemm"
-    {"gemm": lambda: gemm("--lib-compare" in sys.argv), "attn": attn, "attn_bwd": attn_bwd, "rows": rows,
+    {"gemm": lambda: gemm("--lib-compare" in sys.argv), "attn": attn, "attn_f32": attn_f32, "attn_bwd": attn_bwd, "rows": rows,
      "gemm_bf16": lambda: gemm_bf16("--lib-compare" in sys.argv), "attn_bf16": attn_bf16, "gemm_ln_bf16": gemm_ln_bf16, "mlp_fused": mlp_fused, "mlp_train": mlp_train, "attn_qkv_bf16": attn_qkv_bf16, "gemm_ln": gemm_ln,
      "wgrad_bf16": lambda: wgrad(True), "wgrad": lambda: wgrad(False)}[what]()

@@ -25,7 +25,8 @@ FAMILIES = {
                      ("gemm_f32_dma.hip", "gemm_f32.hip", "gemm_f32_split.hip", "split_f32.h", "gemm_f32_dma_loop.h")),
             "gemm_ln": (("gemm_ln_residual_f32",), ("gemm_ln_f32_dma.hip", "gemm_ln_f32_split.hip", "split_f32.h", "gemm_f32_dma_loop.h",
                         "ln_epilogue_f32.h")),
-            "attn": (("window_attn_f32_kernel",), ("attn_f32.hip",))},
+            "attn": (("window_attn_f32_kernel", "window_attn_f32_split_kernel"),
+                     ("attn_f32.hip", "attn_f32_split.hip", "attn_bf16_tile.h", "split_f32.h", "gemm_f32_dma_loop.h"))},
     "bf16": {"mlp_fused": (("mlp_ln_residual_bf16_kernel",), ("mlp_fused_bf16.hip",)),
              "attn_qkv": (("window_attn_qkv_bf16_kernel",), ("attn_bf16.hip", "attn_bf16_tile.h")),
              "gemm": (("gemm_tn_bf16", "gemm_ws_bf16"), ("gemm_bf16.hip", "gemm_ws_bf16.hip")),

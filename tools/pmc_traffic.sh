@@ -5,6 +5,8 @@
 # 2. separate --pmc passes (FETCH_SIZE | WRITE_SIZE | SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE | SQ_INSTS_VALU SQ_WAVES), as MI355X_MICROARCH.md prescribes
 # 3. tools/pmc_to_json.py: per-launch HBM bytes (FETCH_SIZE x2), MFMA busy, the git commit, sha256 of the kernel sources, and a
 #    check that every kernel family priced from the counters was launched by the traced command (fails otherwise)
+#    (families and their sources: FAMILIES in tools/pmc_to_json.py; the f32 `attn` family counts window_attn_f32_kernel and
+#    window_attn_f32_split_kernel and hashes attn_f32.hip, attn_f32_split.hip and the headers the latter includes)
 # The first failing step (non-zero exit or time limit) ends the script with its status: no later pass starts on the GPU.
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"

@@ -8,7 +8,11 @@ rel-L2 and max-abs / max error of both against an fp64 product of the same fp32 
 Shapes: the cases of tests/test_gpu_parity.py::test_linear, the generator of ::test_linear_random_shapes, and the four plain
 projections of the model at M = 4096.  A shape the split kernel does not serve is listed as such.  --ln: the cases of
 tests/test_gpu_linear_ln_split.py::test_parity_against_fp64 and ::test_wide_dynamic_range, and the four fused projections of the
-model at M = 4096, against the fp64 value of shortcut + s * LN(a W^T + b)."""
+model at M = 4096, against the fp64 value of shortcut + s * LN(a W^T + b).
+
+  python tools/split_error.py --attn > profiles/attn_f32_split_error.md       (the window-attention core)
+--attn: the cases of tests/test_gpu_attn_split.py (six geometries, unshifted / shifted, and the peaked shifted inputs) at five seeds
+each, fp32-MFMA kernel and exact-split kernel against the oracle evaluated in fp64."""
 import os
 import random
 import sys
@@ -137,9 +141,45 @@ def main_ln():
             print(f"| {name} | {M}x{N}x{K} | {t0:.3f} | {t1:.3f} | {t0 / t1:.2f}x | {2.0 * M * N * K / t1 / 1e9:.0f} |")
 
 
+ATTN_GEOMS = [(2, 1, 12, 1), (4, 7, 24, 2), (2, 13, 36, 5), (6, 19, 12, 3), (8, 181, 24, 6), (8, 91, 24, 12)]
+
+
+def main_attn():
+    import pangu_oracle as O
+    print("# Exact-split window attention: error against the oracle in fp64\n")
+    print("rel-L2 / max-abs of `pangu_window_attn_fwd` (fp32 MFMA) and `pangu_window_attn_fwd_split` (six bf16 MFMA terms per "
+          "product, one accumulator) against `oracle/pangu_oracle.py::window_attention_core` in fp64 on the same fp32 inputs: the "
+          "cases of tests/test_gpu_attn_split.py (amp 1.5: test_error_no_worse_than_fp32_mfma_kernel; amp 9.0, shifted: "
+          "test_peaked_and_masked_rows) at five seeds.  Ratios = split / fp32 MFMA.  Made by `tools/split_error.py --attn`.\n")
+    print("| (Z, H, W, heads) | shifted | amp | seed | fp32 MFMA | split | rel-L2 ratio | max-abs ratio |")
+    print("|---|---|---|---|---|---|---|---|")
+    r_l2, r_max = [], []
+    for Z, H, W, heads in ATTN_GEOMS:
+        C, N, types = 32 * heads, Z * H * W, (Z // 2) * ((H + 5) // 6)
+        for shifted, amp in ((False, 1.5), (True, 1.5), (True, 9.0)):
+            for seed in (91, 191, 291, 391, 491):
+                qkv, b1 = synth.uniform((1, N, 3 * C), seed, amp), synth.uniform((3 * C,), seed + 1, amp / 3.0)
+                esb = synth.uniform((1, types, heads, 144, 144), seed + 2, 0.5)
+                ref = O.window_attention_core(qkv.double(), b1.double(), esb.double(), Z, H, W, heads, shifted)[0][0]
+                dev = (qkv[0].cuda(), b1.cuda(), esb[0].cuda())
+                e = []
+                for split in (False, True):
+                    d = ops.window_attention(*dev, Z, H, W, heads, shifted, split=split).double().cpu() - ref
+                    e.append(((d.norm() / ref.norm()).item(), d.abs().max().item()))
+                r_l2.append(e[1][0] / e[0][0])
+                r_max.append(e[1][1] / e[0][1])
+                print(f"| {(Z, H, W, heads)} | {int(shifted)} | {amp} | {seed} | {e[0][0]:.3e} / {e[0][1]:.3e} | {e[1][0]:.3e} / "
+                      f"{e[1][1]:.3e} | {r_l2[-1]:.3f} | {r_max[-1]:.3f} |")
+    print(f"\nrel-L2 ratio: min {min(r_l2):.3f}, median {sorted(r_l2)[len(r_l2) // 2]:.3f}, max {max(r_l2):.3f}; "
+          f"max-abs ratio: min {min(r_max):.3f}, median {sorted(r_max)[len(r_max) // 2]:.3f}, max {max(r_max):.3f} "
+          f"({len(r_l2)} cases).")
+
+
 def main():
     if "--ln" in sys.argv:
         return main_ln()
+    if "--attn" in sys.argv:
+        return main_attn()
     print("# Exact-split fp32 projection: error against an fp64 product\n")
     print("rel-L2 / (max-abs / max) of `pangu_linear_fwd` (fp32 MFMA) and `pangu_linear_fwd_split` (six bf16 MFMA terms, one "
           "accumulator) on the same fp32 inputs; ratio = split rel-L2 / fp32 rel-L2.  Made by `tools/split_error.py`.\n")
