@@ -732,6 +732,48 @@ int pangu_lead_stats_update_f32(pangu_stream_t stream, const float* src, const f
                                 unsigned char* count, unsigned char* run, unsigned char* longest, int planes, long long plane_elems,
                                 int levels, int lead, int first);
 
+/* The observation operator: bilinear interpolation of `planes` planes src [planes][H][W] fp32 to N points, and the departure
+ * statistics of the interpolated forecast against observations at those points (csrc/points.hip pins the definitions).  Any W: the
+ * gather uses 4-B loads.  v = src * mul[q] + add[q] in two roundings, mul / add fp32 [planes] indexed by SOURCE plane q, both or
+ * neither (NULL: v = src), and q = p (levels = 0) or the level-reversed plane (levels = L), exactly as for pangu_regrid_planes_f32;
+ * out, obs and departures are [planes][N], indexed by output plane p.
+ *   The plan (device memory, built by score.point_plan): row, col int32 [N], the grid node north-west of the point, and wy, wx fp32
+ *   [N], the weights of the next row r1 = min(row + 1, H - 1) and of the next column c1 = (col + 1) mod W.  Every operation rounded
+ *   once to fp32, no contraction:
+ *     line(j) = wx == 0 ? v[j][col] : fl(fl(v[j][col] * fl(1 - wx)) + fl(v[j][c1] * wx))
+ *     f       = wy == 0 ? line(row) : fl(fl(line(row) * fl(1 - wy)) + fl(line(r1) * wy))
+ *   A tap of weight zero is a select, never a product: a non-finite value at a node reaches exactly the points whose stencil holds
+ *   the node with a non-zero weight, and a point on a node returns the node's value bit for bit.
+ * The plan arrays are TRUSTED (the caller's contract, not checked): 0 <= row < H, 0 <= col < W, 0 <= wy, wx < 1 and wy == 0 where row
+ * == H - 1.  (An index outside the grid is clamped into it: a broken plan gives wrong values, not an access outside the plane.)
+ * pangu_sample_points_f32 writes f to out, one launch on `stream`, no workspace.
+ * pangu_point_scores_f32: c = clim[p] (clim fp32 [planes], indexed by output plane; NULL: c = 0), d = f - o, a = f - c, b = o - c, one
+ * fp32 rounding each, and the products rounded to fp32.  A point is valid for a plane iff its observation is not NaN (the marker of a
+ * missing report; infinities are values).
+ *   departures   optional (NULL: not kept): d, NaN where the observation is missing;
+ *   region_bits  [N] bytes shared by all planes: bit r of a point's byte says that the point belongs to region r < R (higher bits are
+ *                ignored); NULL: one region that holds every point (R must be 1);
+ *   sums         [planes][R][10] doubles, the layout of pangu_scorecard_sums_f32 with weight 1, over the valid points of the region:
+ *                  [0] n    [1] sum d    [2] sum |d|    [3] sum d^2    [4] sum a    [5] sum b    [6] sum a b    [7] sum a^2
+ *                  [8] sum b^2    [9] n;  [0] and [9] are exact integers.
+ * Membership and validity are selects; a region with no valid point gives ten zeros.  Each (plane, chunk of 1024 points) writes its
+ * fp32 partials (the counts as integers) to workspace, >= pangu_point_scores_ws_bytes(planes, N, R) = planes * ceil(N / 1024) * R * 40
+ * bytes (host-only; PANGU_E_SHAPE for sizes out of range); a second launch adds the chunks in chunk order in double.  No atomics:
+ * every output is bit-identical from run to run, and a plane's outputs do not depend on which other planes are in the launch.  Two
+ * launches on `stream`, no host sync; everything is checked before the first.
+ * PANGU_E_NULL: a required pointer (src, the four plan arrays, out; obs, sums, workspace), mul without add or the reverse, region_bits
+ * == NULL with R != 1; PANGU_E_SHAPE: a non-positive size, H < 2, H*W >= 2^31, planes * N >= 2^31, R outside 1..8, levels < 0 or planes
+ * % levels != 0; PANGU_E_ARG: a workspace that is too small, or a pointer that misses its alignment: 8 B for sums, 4 B for the other
+ * fp32 / int32 arrays and the workspace. */
+int pangu_sample_points_f32(pangu_stream_t stream, const float* src, const float* mul, const float* add, const int* row,
+                            const int* col, const float* wy, const float* wx, float* out, int planes, int H, int W, int N,
+                            int levels);
+long long pangu_point_scores_ws_bytes(int planes, int N, int R);
+int pangu_point_scores_f32(pangu_stream_t stream, const float* src, const float* mul, const float* add, const int* row,
+                           const int* col, const float* wy, const float* wx, const float* obs, const float* clim,
+                           const unsigned char* region_bits, int R, float* departures, double* sums, void* workspace,
+                           long long workspace_bytes, int planes, int H, int W, int N, int levels);
+
 /* Adam over a whole list of tensors in ONE launch (reference finetune_fully.py:121 torch.optim.Adam, stepped at
  * models/pangu_sample.py:75): p, grad, exp_avg, exp_avg_sq fp32, updated in place with the arithmetic of torch's fused Adam
  * (L2 weight decay added to the gradient, bias corrections, eps outside the root; doubles where that code uses doubles) -- bit

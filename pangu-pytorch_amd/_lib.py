@@ -90,6 +90,9 @@ SIGNATURES = {
     "pangu_event_scores_ws_bytes": [_I, _I, _I, _I],
     "pangu_event_scores_f32": [_P, _P, _P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _c.c_longlong, _I, _I, _I],
     "pangu_lead_stats_update_f32": [_P] * 10 + [_I, _P, _P, _P, _I, _c.c_longlong, _I, _I, _I],
+    "pangu_sample_points_f32": [_P] * 9 + [_I] * 5,
+    "pangu_point_scores_ws_bytes": [_I, _I, _I],
+    "pangu_point_scores_f32": [_P] * 11 + [_I, _P, _P, _P, _c.c_longlong, _I, _I, _I, _I, _I],
     "pangu_window_attn_bwd_bf16": [_P] * 10 + [_I] * 6,
     "pangu_ln_residual_bwd_bf16": [_P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _F],
     "pangu_downsample_ln_bwd_bf16": [_P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P],
@@ -115,7 +118,8 @@ SIGNATURES = {
 _RESTYPES = {"pangu_error_string": _c.c_char_p, "pangu_weighted_l1_loss_blocks": _c.c_longlong,
              "pangu_fair_crps_loss_blocks": _c.c_longlong, "pangu_pack_i16_ws_bytes": _c.c_longlong,
              "pangu_ensemble_quantiles_ws_bytes": _c.c_longlong, "pangu_zonal_spectrum_ws_bytes": _c.c_longlong,
-             "pangu_scorecard_ws_bytes": _c.c_longlong, "pangu_event_scores_ws_bytes": _c.c_longlong}
+             "pangu_scorecard_ws_bytes": _c.c_longlong, "pangu_event_scores_ws_bytes": _c.c_longlong,
+             "pangu_point_scores_ws_bytes": _c.c_longlong}
 
 _lib = None
 

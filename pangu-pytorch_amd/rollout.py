@@ -81,8 +81,28 @@ def check_lead_stats(lead_stats, steps, who):
         raise ValueError(f"{who}: {steps} steps do not reach the end of every lead window (the last ends at lead {end})")
 
 
+def check_point_hooks(sites, observations, obs, steps, who):
+    """What rollout(sites=, observations=, obs=) asks before the first step; returns obs as a list (or None)."""
+    if sites is not None and sites.leads < steps:
+        raise ValueError(f"{who}: the point series holds {sites.leads} leads, the rollout makes {steps} steps")
+    if (observations is None) != (obs is None):
+        raise ValueError(f"{who}: observations and obs go together (a score.ObservationAccumulator and one pair (obs_upper, "
+                         "obs_surface) or None per step)")
+    if obs is None:
+        return None
+    obs = list(obs)
+    if len(obs) != steps:
+        raise ValueError(f"{who}: {len(obs)} obs entries for {steps} steps")
+    if observations.leads < steps:
+        raise ValueError(f"{who}: the observation accumulator holds {observations.leads} leads, the rollout makes {steps} steps")
+    for o in obs:
+        if o is not None and len(o) != 2:
+            raise ValueError(f"{who}: an obs entry is a pair (obs_upper, obs_surface) or None")
+    return obs
+
+
 def rollout(model, inp, inp_surface, statistics, maps, const_h, stats_last, steps=7, graph=True, keep=False, drain=None,
-            scorecard=None, targets=None, events=None, *, lead_stats=None):
+            scorecard=None, targets=None, events=None, *, lead_stats=None, sites=None, observations=None, obs=None):
     """`steps` chained forwards. Returns the last step's physical-unit fields (and, with keep=True, a list of the
     normalised outputs of every step, cloned).
 
@@ -106,8 +126,18 @@ def rollout(model, inp, inp_surface, statistics, maps, const_h, stats_last, step
     `steps`.  After step k the step's physical-unit fields are folded into every window that holds lead k (lead_stats.update: one
     launch per tensor and window, behind the graph replay on the same stream, outside the captured graph, no host sync); the
     window means, extremes and spell lengths are then read from lead_stats.result(w) (lead_stats.reset() before the next rollout).
-    The returned values are unchanged."""
+    The returned values are unchanged.
+
+    sites: a score.PointSeries with at least `steps` leads.  After step k the step's physical-unit fields are interpolated to the
+    series' points into its row k (sites.record: one launch per tensor), the forecast at a user's sites without draining a field.
+
+    observations: a score.ObservationAccumulator with at least `steps` leads, and obs: a sequence of `steps` entries, each a pair
+    (obs_upper (.., 5, 13, N), obs_surface (.., 4, N)) of device tensors in physical units, NaN where there is no report, or None (no
+    observations for that lead).  After step k the step's fields are scored against obs[k] at the points and pooled at lead k
+    (observations.score: two launches per tensor).  Both hooks follow the graph replay on the same stream, outside the captured
+    graph, with no host sync; the returned values are unchanged."""
     check_lead_stats(lead_stats, steps, "rollout")
+    obs = check_point_hooks(sites, observations, obs, steps, "rollout")
     if (scorecard is not None and targets is None) or (targets is not None and scorecard is None and events is None):
         raise ValueError("rollout: scorecard and targets go together (a score.ScoreAccumulator and one target pair or None per step)")
     if events is not None and targets is None:
@@ -139,6 +169,10 @@ def rollout(model, inp, inp_surface, statistics, maps, const_h, stats_last, step
                     events.score(k, g.inp, g.inp_surface, *targets[k])
                 if lead_stats is not None:
                     lead_stats.update(k, g.inp, g.inp_surface)
+                if sites is not None:
+                    sites.record(k, g.inp, g.inp_surface)
+                if observations is not None and obs[k] is not None:
+                    observations.score(k, g.inp, g.inp_surface, *obs[k])
             up, sf = g.inp.clone(), g.inp_surface.clone()
         else:
             up, sf = inp, inp_surface
@@ -155,4 +189,8 @@ def rollout(model, inp, inp_surface, statistics, maps, const_h, stats_last, step
                     events.score(k, up, sf, *targets[k])
                 if lead_stats is not None:
                     lead_stats.update(k, up, sf)
+                if sites is not None:
+                    sites.record(k, up, sf)
+                if observations is not None and obs[k] is not None:
+                    observations.score(k, up, sf, *obs[k])
     return (up, sf, history) if keep else (up, sf)

@@ -842,47 +842,48 @@ class RegionPlan:
         self.everywhere = bool(everywhere) and self.R == 1      # one region of every point: the kernel needs no mask
 
 
-def _region_box(H, W, lat, lon, who):
-    """bool numpy (H, W): rows with lat[0] <= 90 - 180 j / (H - 1) <= lat[1], columns with (360 i / W - lon[0]) mod 360 below the
-    box's width (lon[1] - lon[0] taken into (0, 360]: a box may cross the date line or the prime meridian)."""
-    import numpy as np
+def _box_limits(lat, lon, who):
+    """(south, north, west, width) of a box in degrees: the width lon[1] - lon[0] taken into (0, 360], so that a box may cross the
+    date line or the prime meridian."""
     try:
         (south, north), (west, east) = (float(v) for v in lat), (float(v) for v in lon)
     except (TypeError, ValueError):
         raise ValueError(f"{who}: lat and lon are (lo, hi) pairs in degrees") from None
     if not south <= north:      # NaN included
         raise ValueError(f"{who}: lat_lo <= lat_hi, got ({south}, {north})")
-    rows = 90.0 - 180.0 * np.arange(H, dtype=np.float64) / float(max(H - 1, 1))
-    cols = 360.0 * np.arange(W, dtype=np.float64) / float(W)
     width = east - west
     if not abs(width) <= 360.0:      # NaN included
         raise ValueError(f"{who}: a longitude range spans at most 360 degrees, got ({west}, {east})")
     if width <= 0.0:
         width += 360.0
-    in_row = (rows >= south) & (rows <= north)
-    in_col = np.mod(cols - west, 360.0) < width
-    return in_row[:, None] & in_col[None, :]
+    return south, north, west, width
 
 
-def region_bits(H, W, regions=None, device=None):
-    """The RegionPlan of up to 8 named regions on the grid (H, W): latitudes 90 - 180 j / (H - 1), longitudes 360 i / W.
-
-    regions: an ordered mapping name -> a preset name (REGION_PRESETS) or dict(lat=(lo, hi), lon=(lo, hi), mask=None); None gives
-    {"global": "global"}.  lat: both ends closed (default (-90, 90)); lon: half-open and wrapping, (lon - lo) mod 360 < hi - lo with
-    the width taken into (0, 360] (default (0, 360): every column); mask: a bool (H, W) tensor that is ANDed in, e.g. land_mask >
-    0.5.  Regions may overlap.  Plans without a mask tensor are cached per (H, W, regions, device)."""
+def _in_box(lat, lon, limits):
+    """bool numpy, the broadcast of lat and lon (float64, degrees): lat in [south, north] and (lon - west) mod 360 below the width."""
     import numpy as np
-    who = "region_bits"
-    H, W = int(H), int(W)
-    if H < 1 or W < 1:
-        raise ValueError(f"{who}: a positive grid size, got ({H}, {W})")
-    device = torch.device("cpu") if device is None else torch.device(device)
+    south, north, west, width = limits
+    return ((lat >= south) & (lat <= north)) & (np.mod(lon - west, 360.0) < width)
+
+
+def _region_box(H, W, lat, lon, who):
+    """bool numpy (H, W): rows with lat[0] <= 90 - 180 j / (H - 1) <= lat[1], columns with (360 i / W - lon[0]) mod 360 below the
+    box's width (lon[1] - lon[0] taken into (0, 360]: a box may cross the date line or the prime meridian)."""
+    import numpy as np
+    limits = _box_limits(lat, lon, who)
+    rows = 90.0 - 180.0 * np.arange(H, dtype=np.float64) / float(max(H - 1, 1))
+    cols = 360.0 * np.arange(W, dtype=np.float64) / float(W)
+    return _in_box(rows[:, None], cols[None, :], limits)
+
+
+def _region_specs(regions, H, W, who):
+    """The regions of a region_bits mapping as a list of (name, lat, lon, mask), checked; None stands for {"global": "global"}."""
     regions = {"global": "global"} if regions is None else regions
     if not hasattr(regions, "items"):
         raise ValueError(f"{who}: regions is a mapping from a name to a preset name or a dict(lat=, lon=, mask=)")
     if not 1 <= len(regions) <= SCORECARD_MAX_R:
         raise ValueError(f"{who}: 1 <= R <= {SCORECARD_MAX_R} regions, got {len(regions)}")
-    specs, key = [], []
+    specs = []
     for name, spec in regions.items():
         if isinstance(spec, str):
             if spec not in REGION_PRESETS:
@@ -899,6 +900,25 @@ def region_bits(H, W, regions=None, device=None):
         if mask is not None and not (torch.is_tensor(mask) and mask.dtype == torch.bool and tuple(mask.shape) == (H, W)):
             raise ValueError(f"{who}: the mask of region {name!r} must be a bool tensor ({H}, {W})")
         specs.append((name, lat, lon, mask))
+    return specs
+
+
+def region_bits(H, W, regions=None, device=None):
+    """The RegionPlan of up to 8 named regions on the grid (H, W): latitudes 90 - 180 j / (H - 1), longitudes 360 i / W.
+
+    regions: an ordered mapping name -> a preset name (REGION_PRESETS) or dict(lat=(lo, hi), lon=(lo, hi), mask=None); None gives
+    {"global": "global"}.  lat: both ends closed (default (-90, 90)); lon: half-open and wrapping, (lon - lo) mod 360 < hi - lo with
+    the width taken into (0, 360] (default (0, 360): every column); mask: a bool (H, W) tensor that is ANDed in, e.g. land_mask >
+    0.5.  Regions may overlap.  Plans without a mask tensor are cached per (H, W, regions, device)."""
+    import numpy as np
+    who = "region_bits"
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError(f"{who}: a positive grid size, got ({H}, {W})")
+    device = torch.device("cpu") if device is None else torch.device(device)
+    specs = _region_specs(regions, H, W, who)
+    key = []
+    for name, lat, lon, mask in specs:
         if key is not None and mask is None:
             try:
                 key.append((name, tuple(float(v) for v in lat), tuple(float(v) for v in lon)))
@@ -1695,3 +1715,284 @@ class LeadWindowStats:
         order of `stats`: what a data.HostDrain built without stats_last accepts; product_names(w) names the entries."""
         r = self.result(w)
         return [t.to(torch.float32).contiguous() for s in self.stats for t in getattr(r, s)]
+
+
+# ---- verification against point observations, and forecasts at sites: the observation operator (csrc/points.hip) ------------------
+
+POINT_CHUNK = 1024                    # csrc/points.hip PT_CHUNK: the points of one workspace partial
+
+
+class PointPlan:
+    """N points on the grid (H, W) as pangu_sample_points_f32 reads them, in the caller's order: `row`, `col` (int32 (N,)) the grid
+    node north-west of a point, `wy`, `wx` (fp32 (N,)) the weights of the next row and the next column (columns wrap), `bits` (uint8
+    (N,): bit r says that the point lies in region r); `names`, R = len(names), and `everywhere` (one region that holds every point:
+    the scores entry is then called without region bits).  0 <= wy, wx < 1 always, and wy == 0 where row == H - 1."""
+
+    def __init__(self, H, W, row, col, wy, wx, bits, names, everywhere=False):
+        self.H, self.W, self.N = int(H), int(W), int(row.shape[0])
+        self.row, self.col, self.wy, self.wx, self.bits = row, col, wy, wx, bits
+        self.names = tuple(names)
+        self.R = len(self.names)
+        self.everywhere = bool(everywhere) and self.R == 1
+
+    @property
+    def device(self):
+        return self.row.device
+
+
+def _point_cells(H, W, lat, lon):
+    """row, col (int64) and wy, wx (fp32) of point_plan for float64 coordinate arrays that passed its checks."""
+    import numpy as np
+    y = (90.0 - lat) * (H - 1) / 180.0
+    row = np.minimum(np.floor(y), H - 1)
+    wy = (y - row).astype(np.float32)
+    x = np.mod(lon, 360.0) * W / 360.0
+    col = np.floor(x)
+    wx = (x - col).astype(np.float32)
+    row, col = row.astype(np.int64), col.astype(np.int64)
+    over = col >= W                                    # (lon mod 360) rounded up to 360: the first column
+    col[over], wx[over] = 0, 0.0
+    up = wy == np.float32(1.0)                         # a weight that rounds up to 1 in fp32: the next node, weight 0
+    row[up] += 1
+    wy[up] = 0.0
+    up = wx == np.float32(1.0)
+    col[up] = (col[up] + 1) % W
+    wx[up] = 0.0
+    return row, col, wy, wx
+
+
+def point_plan(H, W, lat, lon, regions=None, device=None):
+    """The PointPlan of the points (lat[i], lon[i]) in degrees on the grid (H, W): latitudes 90 - 180 j / (H - 1), longitudes
+    360 i / W.  In float64, y = (90 - lat)(H - 1) / 180, row = min(floor(y), H - 1), wy = y - row; x = (lon mod 360) W / 360, col =
+    floor(x), wx = x - col; the weights are then rounded to fp32.  A col that reaches W becomes column 0 with wx = 0, and a weight
+    that rounds up to 1.0 moves the point to the next node with weight 0 (the column wrapping), so that the kernel never sees a
+    weight of 1.  Longitudes may be any finite value; lat outside [-90, 90], a non-finite coordinate, no point at all or lat and lon
+    of different lengths raise ValueError.
+
+    regions: a mapping as for region_bits (at most 8), evaluated at the points' own coordinates: lat in [lo, hi], (lon - lo) mod 360
+    below the width; a `mask` (bool (H, W)) is read at the grid node nearest to the point, row + (wy >= 0.5) and (col + (wx >= 0.5))
+    mod W.  None: one region that holds every point."""
+    import numpy as np
+    who = "point_plan"
+    H, W = int(H), int(W)
+    if H < 2 or W < 1:
+        raise ValueError(f"{who}: a grid of at least 2 rows and 1 column, got ({H}, {W})")
+    if H * W >= 2 ** 31:
+        raise ValueError(f"{who}: H * W must stay below 2^31")
+    as_array = lambda v: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)).astype(np.float64)
+    try:
+        lat, lon = as_array(lat), as_array(lon)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: lat and lon are sequences of numbers in degrees") from None
+    if lat.ndim != 1 or lon.ndim != 1 or lat.shape != lon.shape:
+        raise ValueError(f"{who}: lat and lon must be one-dimensional and of one length, got {lat.shape} and {lon.shape}")
+    if lat.size == 0:
+        raise ValueError(f"{who}: no points")
+    if not (np.isfinite(lat).all() and np.isfinite(lon).all()):
+        raise ValueError(f"{who}: coordinates must be finite")
+    if not ((lat >= -90.0) & (lat <= 90.0)).all():
+        raise ValueError(f"{who}: latitudes must lie in [-90, 90]")
+    device = torch.device("cpu") if device is None else torch.device(device)
+    row, col, wy, wx = _point_cells(H, W, lat, lon)
+    specs = _region_specs(regions, H, W, who)
+    bits = np.zeros(lat.size, np.uint8)
+    near_row, near_col = row + (wy >= np.float32(0.5)), (col + (wx >= np.float32(0.5))) % W
+    for r, (name, blat, blon, mask) in enumerate(specs):
+        inside = _in_box(lat, lon, _box_limits(blat, blon, f"{who}: region {name!r}"))
+        if mask is not None:
+            inside = inside & mask.detach().cpu().numpy()[near_row, near_col]
+        bits |= (inside.astype(np.uint8) << r).astype(np.uint8)
+    up = lambda a, dtype: torch.from_numpy(np.ascontiguousarray(a.astype(dtype))).to(device)
+    return PointPlan(H, W, up(row, np.int32), up(col, np.int32), up(wy, np.float32), up(wx, np.float32), up(bits, np.uint8),
+                     [s[0] for s in specs], everywhere=bool((bits == 1).all()))
+
+
+def _check_point_fields(upper, surface, plan, who):
+    if not isinstance(plan, PointPlan):
+        raise ValueError(f"{who}: plan must be a score.PointPlan")
+    for t, name in ((upper, "upper"), (surface, "surface")):
+        if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.is_contiguous()):
+            raise ValueError(f"{who}: {name} must be a contiguous float32 tensor")
+    if upper.dim() < 4 or surface.dim() < 3 or tuple(upper.shape[-4:-2]) != (5, 13) or surface.shape[-3] != 4:
+        raise ValueError(f"{who}: expected upper (.., 5, 13, H, W) and surface (.., 4, H, W)")
+    if tuple(upper.shape[:-4]) != tuple(surface.shape[:-3]) or tuple(upper.shape[-2:]) != tuple(surface.shape[-2:]):
+        raise ValueError(f"{who}: upper and surface disagree in their leading dimensions or grids")
+    if upper.numel() == 0 or upper.device != surface.device:
+        raise ValueError(f"{who}: empty tensors, or upper and surface on different devices")
+    if tuple(upper.shape[-2:]) != (plan.H, plan.W) or plan.device != upper.device:
+        raise ValueError(f"{who}: the point plan is for a {(plan.H, plan.W)} grid on {plan.device}, the fields are "
+                         f"{tuple(upper.shape[-2:])} on {upper.device}")
+    if not upper.is_cuda:
+        raise RuntimeError(f"{who}: the Pangu HIP path needs tensors on an MI355X device (got {upper.device}); there is no CPU fallback")
+
+
+def _plane_vector(values, t, nplane, device):
+    """fp32 (planes,): one value per (variable, level) of `values` ((.., 5, 13, 1, 1) or (.., 4, 1, 1) statistics) for every plane of
+    t, whose last nplane + 2 dimensions are the planes and the grid."""
+    pshape = tuple(t.shape[-2 - nplane:-2])
+    lead = tuple(t.shape[:-2]) + (1, 1)
+    return values.to(device=device, dtype=torch.float32).reshape(pshape + (1, 1)).expand(lead).contiguous().view(-1)
+
+
+def _sample_launch(t, plan, mul, add, levels, out):
+    planes = t.numel() // (plan.H * plan.W)
+    ptr = lambda v: None if v is None else v.data_ptr()
+    _lib.check(_lib.load().pangu_sample_points_f32(
+        _stream(t), t.data_ptr(), ptr(mul), ptr(add), plan.row.data_ptr(), plan.col.data_ptr(), plan.wy.data_ptr(),
+        plan.wx.data_ptr(), out.data_ptr(), planes, plan.H, plan.W, plan.N, levels), "sample_points_f32")
+    return out
+
+
+def sample_points(upper, surface, plan, stats_last=None, levels_reversed=False, out=None):
+    """upper (.., 5, 13, H, W) / surface (.., 4, H, W), contiguous fp32 device tensors, interpolated bilinearly to the plan's N points:
+    (upper (.., 5, 13, N), surface (.., 4, N)), one HIP launch per tensor on the current stream (pangu_sample_points_f32, the
+    arithmetic pinned in csrc/points.hip), no host sync.  Leading dimensions (ensemble members, cases) are simply more planes.
+    stats_last: the 4-tuple of rollout.norm_back: the fields are NORMALISED model outputs and are de-normalised by the kernel (per
+    stored plane).  levels_reversed: the upper-air tensor is stored with its level axis reversed; reversed by addressing.  out: a pair
+    of contiguous fp32 tensors of the result's shapes to write.  A NaN at a grid node reaches the points that use the node."""
+    who = "sample_points"
+    _check_point_fields(upper, surface, plan, who)
+    res = []
+    for k, (t, nplane, levels) in enumerate(((upper, 2, 13 if levels_reversed else 0), (surface, 1, 0))):
+        mul = add = None
+        if stats_last is not None:
+            s_mean, s_std, u_mean, u_std = stats_last
+            mean, std = (u_mean, u_std) if nplane == 2 else (s_mean, s_std)
+            mul, add = _plane_vector(std, t, nplane, t.device), _plane_vector(mean, t, nplane, t.device)
+        shape = tuple(t.shape[:-2]) + (plan.N,)
+        if out is None:
+            o = torch.empty(shape, dtype=torch.float32, device=t.device)
+        else:
+            o = out[k]
+            if not (torch.is_tensor(o) and o.dtype == torch.float32 and o.is_contiguous() and o.device == t.device
+                    and tuple(o.shape) == shape):
+                raise ValueError(f"{who}: out[{k}] must be a contiguous float32 tensor {shape} on {t.device}")
+        res.append(_sample_launch(t, plan, mul, add, levels, o))
+    return tuple(res)
+
+
+def point_scores_workspace_bytes(planes, N, R):
+    """Workspace of pangu_point_scores_f32 (include/pangu_hip.h): per (plane, chunk of 1024 points, region) ten 32-bit words."""
+    return planes * ((N + POINT_CHUNK - 1) // POINT_CHUNK) * R * SCORECARD_SUMS * 4
+
+
+def _point_scores(t, obs, clim, plan, want_departures, what):
+    planes = t.numel() // (plan.H * plan.W)
+    shape = tuple(t.shape[:-2]) + (plan.N,)
+    if not torch.is_tensor(obs) or tuple(obs.shape) != shape:
+        raise ValueError(f"{what}: the observations must be {shape}, one value per plane and point (NaN: no report)")
+    o_ptr = _chk(obs, what + " observations")
+    dev = t.device
+    sums = torch.empty(tuple(t.shape[:-2]) + (plan.R, SCORECARD_SUMS), dtype=torch.float64, device=dev)
+    dep = torch.empty(shape, dtype=torch.float32, device=dev) if want_departures else None
+    ws = torch.empty(point_scores_workspace_bytes(planes, plan.N, plan.R), dtype=torch.uint8, device=dev)
+    ptr = lambda v: None if v is None else v.data_ptr()
+    _lib.check(_lib.load().pangu_point_scores_f32(
+        _stream(t), t.data_ptr(), None, None, plan.row.data_ptr(), plan.col.data_ptr(), plan.wy.data_ptr(), plan.wx.data_ptr(),
+        o_ptr, ptr(clim), None if plan.everywhere else plan.bits.data_ptr(), plan.R, ptr(dep), sums.data_ptr(), ws.data_ptr(),
+        ws.numel(), planes, plan.H, plan.W, plan.N, 0), "point_scores_f32")
+    return sums, dep
+
+
+def observation_scores(upper, surface, obs_upper, obs_surface, plan, clim=None, want_departures=False):
+    """The departure statistics of forecasts upper (.., 5, 13, H, W) / surface (.., 4, H, W), fp32 in physical units, against
+    observations obs_upper (.., 5, 13, N) / obs_surface (.., 4, N) at the plan's N points, NaN where there is no report; leading
+    dimensions are separate cases.  The forecast is interpolated bilinearly to the points and compared there, two HIP launches per
+    tensor (pangu_point_scores_f32, definitions pinned in csrc/points.hip), no host sync, bit-identical from run to run.
+
+    clim: None (anomalies are the values themselves) or stats_last (s_mean, s_std, u_mean, u_std: the means serve as one
+    climatological value per plane, as in deterministic_scores).  Returns (upper_sums, surface_sums), two ScoreSums with sums
+    (.., 5, 13, R, 10) and (.., 4, R, 10) over the plan's regions, every valid point with weight 1: bias, mae, rmse, acc and the
+    others are those of the reports, `counts` their number (a plane and region without a report gives NaN scores).  wind_rmse() is
+    meaningful where u and v are reported together: it divides the two sums of squares by the number of u reports.  With
+    want_departures=True the departures forecast - observation follow, (.., 5, 13, N) and (.., 4, N), NaN where there is no report."""
+    who = "observation_scores"
+    _check_point_fields(upper, surface, plan, who)
+    cu = cs = None
+    if clim is not None:
+        clim = tuple(clim)
+        if len(clim) != 4 or clim[2].numel() != 65 or clim[0].numel() != 4:
+            raise ValueError(f"{who}: clim is None or stats_last, whose means hold 5 x 13 and 4 values")
+        cu, cs = _plane_vector(clim[2], upper, 2, upper.device), _plane_vector(clim[0], surface, 1, upper.device)
+    su, du = _point_scores(upper, obs_upper, cu, plan, want_departures, who + ": upper")
+    ss, ds = _point_scores(surface, obs_surface, cs, plan, want_departures, who + ": surface")
+    res = (ScoreSums(su, plan.names), ScoreSums(ss, plan.names))
+    return res + (du, ds) if want_departures else res
+
+
+class ObservationAccumulator:
+    """Pools observation_scores over cases, per lead: the float64 sums are added on their device (no host sync), so pooled scores
+    are the scores over all cases' reports.  leads: the number of leads (0 .. leads-1); plan and clim as for observation_scores,
+    which score() calls.  The twin of ScoreAccumulator for point observations, and what rollout(observations=) feeds."""
+
+    def __init__(self, leads, plan, clim=None):
+        if not isinstance(plan, PointPlan):
+            raise ValueError("ObservationAccumulator: plan must be a score.PointPlan")
+        try:
+            self._pool = ScoreAccumulator(leads)
+        except ValueError:
+            raise ValueError("ObservationAccumulator: leads must be >= 1") from None
+        self.leads, self.plan, self.clim = self._pool.leads, plan, clim
+
+    def score(self, lead, upper, surface, obs_upper, obs_surface):
+        """observation_scores of these fields and reports, pooled at `lead`; returns the two ScoreSums of this call."""
+        self._pool._check_lead(lead)
+        su, ss = observation_scores(upper, surface, obs_upper, obs_surface, self.plan, self.clim)
+        self._pool.add(lead, su, ss)
+        return su, ss
+
+    def cases(self, lead):
+        return self._pool.cases(lead)
+
+    def result(self, lead):
+        """(upper, surface) pooled ScoreSums of a lead, sums (5, 13, R, 10) and (4, R, 10)."""
+        self._pool._check_lead(lead)
+        if self._pool.cases(lead) == 0:
+            raise ValueError(f"ObservationAccumulator: nothing scored at lead {lead}")
+        return self._pool.sums(lead)
+
+
+class PointSeries:
+    """The forecast at the plan's N sites for every lead of a rollout (a meteogram): `upper` (leads, .., 5, 13, N) and `surface`
+    (leads, .., 4, N), fp32 on the device, allocated at the first record(); a lead that was not recorded holds NaN.
+    record(lead, upper, surface) samples physical-unit fields (sample_points: one launch per tensor, no host sync) into row `lead`;
+    rollout(sites=) calls it behind every step."""
+
+    def __init__(self, plan, leads):
+        if not isinstance(plan, PointPlan):
+            raise ValueError("PointSeries: plan must be a score.PointPlan")
+        self.plan, self.leads = plan, int(leads)
+        if self.leads < 1:
+            raise ValueError("PointSeries: leads must be >= 1")
+        self.upper = self.surface = None
+
+    def record(self, lead, upper, surface):
+        lead = int(lead)
+        if not 0 <= lead < self.leads:
+            raise IndexError(f"PointSeries.record: lead {lead} outside 0..{self.leads - 1}")
+        _check_point_fields(upper, surface, self.plan, "PointSeries.record")
+        shapes = tuple((self.leads,) + tuple(t.shape[:-2]) + (self.plan.N,) for t in (upper, surface))
+        if self.upper is None:
+            self.upper, self.surface = (torch.full(s, float("nan"), dtype=torch.float32, device=upper.device) for s in shapes)
+        elif (tuple(self.upper.shape), tuple(self.surface.shape)) != shapes:
+            raise ValueError(f"PointSeries.record: shapes must stay those of the first record, {tuple(self.upper.shape[1:])} and "
+                             f"{tuple(self.surface.shape[1:])} per lead")
+        sample_points(upper, surface, self.plan, out=(self.upper[lead], self.surface[lead]))
+
+    def _wind10(self):
+        if self.surface is None:
+            raise ValueError("PointSeries: nothing recorded")
+        return self.surface[..., 1, :], self.surface[..., 2, :]
+
+    def wind_speed10(self):
+        """sqrt(u10^2 + v10^2) of the sampled components (surface variables 1 and 2), (leads, .., N)."""
+        u, v = self._wind10()
+        return torch.sqrt(u * u + v * v)
+
+    def wind_direction10(self):
+        """The meteorological direction in degrees in [0, 360), the direction the wind blows FROM, clockwise from north: 0 for a
+        northerly (v10 < 0), 90 for an easterly (u10 < 0); 0 where the wind is calm (u10 = v10 = 0).  (leads, .., N)."""
+        u, v = self._wind10()
+        d = torch.remainder(torch.rad2deg(torch.atan2(-u, -v)), 360.0)
+        d = torch.where(d >= 360.0, torch.zeros_like(d), d)
+        return torch.where((u == 0) & (v == 0), torch.zeros_like(d), d)
