@@ -81,26 +81,6 @@ def check_lead_stats(lead_stats, steps, who):
         raise ValueError(f"{who}: {steps} steps do not reach the end of every lead window (the last ends at lead {end})")
 
 
-def check_point_hooks(sites, observations, obs, steps, who):
-    """What rollout(sites=, observations=, obs=) asks before the first step; returns obs as a list (or None)."""
-    if sites is not None and sites.leads < steps:
-        raise ValueError(f"{who}: the point series holds {sites.leads} leads, the rollout makes {steps} steps")
-    if (observations is None) != (obs is None):
-        raise ValueError(f"{who}: observations and obs go together (a score.ObservationAccumulator and one pair (obs_upper, "
-                         "obs_surface) or None per step)")
-    if obs is None:
-        return None
-    obs = list(obs)
-    if len(obs) != steps:
-        raise ValueError(f"{who}: {len(obs)} obs entries for {steps} steps")
-    if observations.leads < steps:
-        raise ValueError(f"{who}: the observation accumulator holds {observations.leads} leads, the rollout makes {steps} steps")
-    for o in obs:
-        if o is not None and len(o) != 2:
-            raise ValueError(f"{who}: an obs entry is a pair (obs_upper, obs_surface) or None")
-    return obs
-
-
 def rollout(model, inp, inp_surface, statistics, maps, const_h, stats_last, steps=7, graph=True, keep=False, drain=None,
             scorecard=None, targets=None, events=None, *, lead_stats=None, sites=None, observations=None, obs=None):
     """`steps` chained forwards. Returns the last step's physical-unit fields (and, with keep=True, a list of the
@@ -136,23 +116,58 @@ def rollout(model, inp, inp_surface, statistics, maps, const_h, stats_last, step
     observations for that lead).  After step k the step's fields are scored against obs[k] at the points and pooled at lead k
     (observations.score: two launches per tensor).  Both hooks follow the graph replay on the same stream, outside the captured
     graph, with no host sync; the returned values are unchanged."""
-    check_lead_stats(lead_stats, steps, "rollout")
-    obs = check_point_hooks(sites, observations, obs, steps, "rollout")
+    who = "rollout"
+
+    def per_step(seq, what):
+        seq = list(seq)
+        if len(seq) != steps:
+            raise ValueError(f"{who}: {len(seq)} {what} for {steps} steps")
+        return seq
+
+    def holds(hook, what):
+        if hook is not None and hook.leads < steps:
+            raise ValueError(f"{who}: the {what} holds {hook.leads} leads, the rollout makes {steps} steps")
+
+    def pairs(seq, what):
+        for p in seq:
+            if p is not None and len(p) != 2:
+                raise ValueError(f"{who}: {what} or None")
+
+    check_lead_stats(lead_stats, steps, who)
+    holds(sites, "point series")
+    if (observations is None) != (obs is None):
+        raise ValueError(f"{who}: observations and obs go together (a score.ObservationAccumulator and one pair (obs_upper, "
+                         "obs_surface) or None per step)")
+    if obs is not None:
+        obs = per_step(obs, "obs entries")
+        holds(observations, "observation accumulator")
+        pairs(obs, "an obs entry is a pair (obs_upper, obs_surface)")
     if (scorecard is not None and targets is None) or (targets is not None and scorecard is None and events is None):
-        raise ValueError("rollout: scorecard and targets go together (a score.ScoreAccumulator and one target pair or None per step)")
+        raise ValueError(f"{who}: scorecard and targets go together (a score.ScoreAccumulator and one target pair or None per step)")
     if events is not None and targets is None:
-        raise ValueError("rollout: events needs targets (a score.EventAccumulator and one target pair or None per step)")
+        raise ValueError(f"{who}: events needs targets (a score.EventAccumulator and one target pair or None per step)")
     if targets is not None:
-        targets = list(targets)
-        if len(targets) != steps:
-            raise ValueError(f"rollout: {len(targets)} targets for {steps} steps")
-        if scorecard is not None and scorecard.leads < steps:
-            raise ValueError(f"rollout: the scorecard holds {scorecard.leads} leads, the rollout makes {steps} steps")
-        if events is not None and events.leads < steps:
-            raise ValueError(f"rollout: the event accumulator holds {events.leads} leads, the rollout makes {steps} steps")
-        for t in targets:
-            if t is not None and len(t) != 2:
-                raise ValueError("rollout: a target is a pair (target_upper, target_surface) or None")
+        targets = per_step(targets, "targets")
+        holds(scorecard, "scorecard")
+        holds(events, "event accumulator")
+        pairs(targets, "a target is a pair (target_upper, target_surface)")
+
+    def hooks(k, upper, surface):
+        """Step k's physical-unit fields meet the hooks, in the documented order; all launches, no host sync."""
+        target, ob = None if targets is None else targets[k], None if obs is None else obs[k]
+        if drain is not None:
+            drain.submit([upper, surface], tag=k)
+        if scorecard is not None and target is not None:
+            scorecard.score(k, upper, surface, *target)
+        if events is not None and target is not None:
+            events.score(k, upper, surface, *target)
+        if lead_stats is not None:
+            lead_stats.update(k, upper, surface)
+        if sites is not None:
+            sites.record(k, upper, surface)
+        if observations is not None and ob is not None:
+            observations.score(k, upper, surface, *ob)
+
     history = []
     with torch.no_grad():
         if graph:
@@ -161,18 +176,7 @@ def rollout(model, inp, inp_surface, statistics, maps, const_h, stats_last, step
                 out, out_s = g.step()
                 if keep:
                     history.append((out.clone(), out_s.clone()))
-                if drain is not None:
-                    drain.submit([g.inp, g.inp_surface], tag=k)
-                if scorecard is not None and targets[k] is not None:
-                    scorecard.score(k, g.inp, g.inp_surface, *targets[k])
-                if events is not None and targets[k] is not None:
-                    events.score(k, g.inp, g.inp_surface, *targets[k])
-                if lead_stats is not None:
-                    lead_stats.update(k, g.inp, g.inp_surface)
-                if sites is not None:
-                    sites.record(k, g.inp, g.inp_surface)
-                if observations is not None and obs[k] is not None:
-                    observations.score(k, g.inp, g.inp_surface, *obs[k])
+                hooks(k, g.inp, g.inp_surface)
             up, sf = g.inp.clone(), g.inp_surface.clone()
         else:
             up, sf = inp, inp_surface
@@ -181,16 +185,5 @@ def rollout(model, inp, inp_surface, statistics, maps, const_h, stats_last, step
                 if keep:
                     history.append((out.clone(), out_s.clone()))
                 up, sf = norm_back(out, out_s, stats_last)
-                if drain is not None:
-                    drain.submit([up, sf], tag=k)
-                if scorecard is not None and targets[k] is not None:
-                    scorecard.score(k, up, sf, *targets[k])
-                if events is not None and targets[k] is not None:
-                    events.score(k, up, sf, *targets[k])
-                if lead_stats is not None:
-                    lead_stats.update(k, up, sf)
-                if sites is not None:
-                    sites.record(k, up, sf)
-                if observations is not None and obs[k] is not None:
-                    observations.score(k, up, sf, *obs[k])
+                hooks(k, up, sf)
     return (up, sf, history) if keep else (up, sf)

@@ -50,6 +50,133 @@ def weighted_acc(pred, target):
     return weighted_acc_channels(pred, target).mean(dim=0)
 
 
+# ---- what the wrappers below share: pointers, cached latitude weights, the (upper, surface) contract, per-plane vectors, lead pools
+
+_LAT_WEIGHTS = {}                     # (H, device) -> latitude_weights(H, device)
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _lat_weights(H, device):
+    """latitude_weights(H, device), built once per (H, device): half a dozen small torch launches otherwise, per tensor and call."""
+    key = (H, str(device))
+    if key not in _LAT_WEIGHTS:
+        _LAT_WEIGHTS[key] = latitude_weights(H, device)
+    return _LAT_WEIGHTS[key]
+
+
+def _no_cpu(who, device):
+    raise RuntimeError(f"{who}: the Pangu HIP path needs tensors on an MI355X device (got {device}); there is no CPU fallback")
+
+
+def _check_members(who, upper, surface, target_upper, target_surface):
+    """The member form of the pair: upper (E,5,13,H,W) and surface (E,4,H,W) on one grid, 2 <= E <= 128, W % 4 == 0, and both
+    targets or neither."""
+    us, ss = upper.shape, surface.shape
+    E = us[0]
+    if len(us) != 5 or len(ss) != 4 or ss[0] != E or us[1:3] != (5, 13) or ss[1] != 4:
+        raise ValueError(f"{who}: expected upper (E,5,13,H,W) and surface (E,4,H,W)")
+    if us[-2:] != ss[-2:]:
+        raise ValueError(f"{who}: upper and surface on different grids")
+    if not 2 <= E <= 128:
+        raise ValueError(f"{who}: 2 <= E <= 128 members, got {E}")
+    if us[-1] % 4:
+        raise ValueError(f"{who}: W % 4 != 0")
+    if (target_upper is None) != (target_surface is None):
+        raise ValueError(f"{who}: give both targets or neither")
+
+
+def _check_cases(who, upper, surface, targets=None, w4=False, max_w=None, dense=False):
+    """The case form of the pair: upper (.., 5, 13, H, W) and surface (.., 4, H, W) with the same leading dimensions and grid.
+    targets: the (target_upper, target_surface) pair of an entry that needs both, one value per forecast value; w4: W % 4 == 0,
+    and with max_w also W <= max_w; dense: contiguous fp32 tensors on one device, not empty.  Returns (H, W)."""
+    if dense:
+        for t, name in ((upper, "upper"), (surface, "surface")):
+            if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.is_contiguous()):
+                raise ValueError(f"{who}: {name} must be a contiguous float32 tensor")
+    us, ss = upper.shape, surface.shape                 # read once: every .shape builds a new torch.Size
+    if len(us) < 4 or len(ss) < 3 or us[-4:-2] != (5, 13) or ss[-3] != 4:
+        raise ValueError(f"{who}: expected upper (.., 5, 13, H, W) and surface (.., 4, H, W)")
+    if us[:-4] != ss[:-3] or us[-2:] != ss[-2:]:
+        raise ValueError(f"{who}: upper and surface disagree in their leading dimensions or grids")
+    H, W = us[-2:]
+    if w4 and (W % 4 or (max_w is not None and W > max_w)):
+        raise ValueError(f"{who}: W % 4 != 0" + ("" if max_w is None else f" or W > {max_w}"))
+    if targets is not None:
+        target_upper, target_surface = targets
+        if target_upper is None or target_surface is None:
+            raise ValueError(f"{who}: both targets are required")
+        if target_upper.numel() != upper.numel() or target_surface.numel() != surface.numel():
+            raise ValueError(f"{who}: the targets must hold one value per forecast value, got {tuple(target_upper.shape)} and "
+                             f"{tuple(target_surface.shape)} for {tuple(upper.shape)} and {tuple(surface.shape)}")
+    if dense and (upper.numel() == 0 or upper.device != surface.device):
+        raise ValueError(f"{who}: empty tensors, or upper and surface on different devices")
+    return H, W
+
+
+def _per_plane(values, t, device):
+    """fp32 (planes,) on `device`: the statistic `values` ((.., 5, 13, 1, 1), (.., 4, 1, 1) or flat, one value per plane of one
+    case) for every plane of t, whose last dimensions are one case's planes and the grid; leading cases repeat the values."""
+    v = values.to(device=device, dtype=torch.float32).reshape(-1)
+    planes = t.numel() // (t.shape[-2] * t.shape[-1])
+    return v.expand(planes // v.numel(), v.numel()).contiguous().view(planes)      # view: refuses values that do not fill the planes
+
+
+def _stats_affine(t, stats_last, upper, device):
+    """(mul, add) per plane of a NORMALISED t, so that t * mul + add is rollout.norm_back with stats_last = (s_mean, s_std, u_mean,
+    u_std); (None, None) without stats_last.  upper: t is the upper-air tensor and takes the u_ pair."""
+    if stats_last is None:
+        return None, None
+    s_mean, s_std, u_mean, u_std = stats_last
+    mean, std = (u_mean, u_std) if upper else (s_mean, s_std)
+    return _per_plane(std, t, device), _per_plane(mean, t, device)
+
+
+def _per_plane_thresholds(thr, T, planes, device):
+    """fp32 (T, cases, per_case) on `device`: the thresholds thr (T, 5, 13) or (T, 4) for `planes` planes, cases outermost."""
+    per_case = thr[0].numel()
+    return thr.to(device=device, dtype=torch.float32).reshape(T, 1, per_case).expand(T, planes // per_case, per_case).contiguous()
+
+
+class _LeadPool:
+    """What the per-lead accumulators share: `leads` slots that start empty, the lead check, cases(lead), the refusal to read an
+    empty slot, and the region plans of score() per (H, W, device)."""
+
+    _verb = "scored"
+
+    def __init__(self, leads):
+        self.leads = int(leads)
+        if self.leads < 1:
+            raise ValueError(f"{type(self).__name__}: leads must be >= 1")
+        self._pool = [None] * self.leads
+        self._plans = {}
+
+    def _check_lead(self, lead):
+        if not 0 <= lead < self.leads:
+            raise IndexError(f"lead {lead} outside 0..{self.leads - 1}")
+
+    def cases(self, lead):
+        self._check_lead(lead)
+        return 0 if self._pool[lead] is None else self._pool[lead][0].cases
+
+    def _pooled(self, lead):
+        self._check_lead(lead)
+        if self._pool[lead] is None:
+            raise ValueError(f"{type(self).__name__}: nothing {self._verb} at lead {lead}")
+        return self._pool[lead]
+
+    def _region_plan(self, regions, upper):
+        """The RegionPlan of `regions` (a mapping as for region_bits, or None for the global region) on upper's grid and device."""
+        if isinstance(regions, RegionPlan):
+            return regions
+        key = (upper.shape[-2], upper.shape[-1], str(upper.device))
+        if key not in self._plans:
+            self._plans[key] = region_bits(key[0], key[1], regions, upper.device)
+        return self._plans[key]
+
+
 ENSEMBLE_KEYS = ("rmse_mean", "acc_mean", "spread", "crps")
 
 
@@ -67,11 +194,9 @@ def _ens_stats(x, target, clim, want_fields, what):
     out = torch.empty((planes, 4), dtype=torch.float32, device=x.device)
     mean = torch.empty(x.shape[1:], dtype=torch.float32, device=x.device) if want_fields else None
     std = torch.empty(x.shape[1:], dtype=torch.float32, device=x.device) if want_fields else None
-    w = latitude_weights(H, x.device)
-    ptr = lambda t: t.data_ptr() if t is not None else None
     _lib.check(_lib.load().pangu_ensemble_stats_f32(
-        _stream(x), x.data_ptr(), x[0].numel(), E, ptr(target), ptr(clim), w.data_ptr(), out.data_ptr(), ptr(mean), ptr(std),
-        ws.data_ptr(), ws.numel() * 4, planes, H, W), "ensemble_stats_f32")
+        _stream(x), x.data_ptr(), x[0].numel(), E, _ptr(target), _ptr(clim), _lat_weights(H, x.device).data_ptr(), out.data_ptr(),
+        _ptr(mean), _ptr(std), ws.data_ptr(), ws.numel() * 4, planes, H, W), "ensemble_stats_f32")
     return {k: out[:, i].reshape(pshape) for i, k in enumerate(ENSEMBLE_KEYS)}, mean, std
 
 
@@ -86,19 +211,10 @@ def ensemble_scores(upper, surface, target_upper, target_surface, stats_last, wa
       crps       weighted mean of the fair CRPS, (1/E) sum|x_i - y| - 1/(2E(E-1)) sum_ij |x_i - x_j|.
     want_fields=True adds "mean" and "std" (the ensemble mean and the square root of the unbiased variance), shaped like one
     member.  Targets may be None: then only spread (and the fields) are computed, the other keys are NaN."""
-    E = upper.shape[0]
-    if upper.dim() != 5 or surface.dim() != 4 or surface.shape[0] != E:
-        raise ValueError("ensemble_scores: expected upper (E,5,13,H,W) and surface (E,4,H,W)")
-    if not 2 <= E <= 128:
-        raise ValueError(f"ensemble_scores: 2 <= E <= 128 members, got {E}")
-    if upper.shape[-1] % 4:
-        raise ValueError("ensemble_scores: W % 4 != 0")
-    if (target_upper is None) != (target_surface is None):
-        raise ValueError("ensemble_scores: give both targets or neither")
+    _check_members("ensemble_scores", upper, surface, target_upper, target_surface)
     s_mean, _, u_mean, _ = stats_last
-    clim = lambda t: t.to(device=upper.device, dtype=torch.float32).reshape(-1).contiguous()
-    su, mu, sdu = _ens_stats(upper, target_upper, clim(u_mean), want_fields, "ensemble upper")
-    ss, ms, sds = _ens_stats(surface, target_surface, clim(s_mean), want_fields, "ensemble surface")
+    su, mu, sdu = _ens_stats(upper, target_upper, _per_plane(u_mean, upper[0], upper.device), want_fields, "ensemble upper")
+    ss, ms, sds = _ens_stats(surface, target_surface, _per_plane(s_mean, surface[0], upper.device), want_fields, "ensemble surface")
     if want_fields:
         su.update(mean=mu, std=sdu)
         ss.update(mean=ms, std=sds)
@@ -191,17 +307,14 @@ def _reliability(x, target, thr, T, seed, first_plane, want_fields, what):
     if target is not None:
         target = target.reshape(x.shape[1:])
         _chk(target, what + " target")
-    if T:
-        thr = thr.to(device=dev, dtype=torch.float32).reshape(T, planes).contiguous()
+    thr = _per_plane_thresholds(thr, T, planes, dev) if T else None
     counts = torch.empty((planes, 1 + 2 * T, E + 1), dtype=torch.int32, device=dev)      # the entry's uint32, all < 2^31
     freq = torch.empty((planes, 1 + 2 * T, E + 1), dtype=torch.float32, device=dev)
     prob = torch.empty((T, planes, H, W), dtype=torch.float32, device=dev) if want_fields and T else None
     ws = torch.empty(reliability_workspace_bytes(planes, H, E, T), dtype=torch.uint8, device=dev)
-    w = latitude_weights(H, dev)
-    ptr = lambda t: t.data_ptr() if t is not None else None
     _lib.check(_lib.load().pangu_ensemble_reliability_f32(
-        _stream(x), x.data_ptr(), x[0].numel(), E, ptr(target), ptr(thr) if T else None, T, w.data_ptr(), int(seed) & 0xFFFFFFFF,
-        first_plane, counts.data_ptr(), freq.data_ptr(), ptr(prob), ws.data_ptr(), ws.numel(), planes, H, W),
+        _stream(x), x.data_ptr(), x[0].numel(), E, _ptr(target), _ptr(thr), T, _lat_weights(H, dev).data_ptr(),
+        int(seed) & 0xFFFFFFFF, first_plane, counts.data_ptr(), freq.data_ptr(), _ptr(prob), ws.data_ptr(), ws.numel(), planes, H, W),
         "ensemble_reliability_f32")
     return ReliabilityTables.from_raw(counts, freq, E, T, pshape, prob)
 
@@ -216,15 +329,7 @@ def ensemble_reliability(upper, surface, target_upper, target_surface, threshold
     (forecast mode, needs thresholds): the rank and observed tables are then zero.  want_fields=True adds the exceedance
     probabilities k / E as .prob.  Returns (upper_result, surface_result), two ReliabilityTables."""
     who = "ensemble_reliability"
-    E = upper.shape[0]
-    if upper.dim() != 5 or surface.dim() != 4 or surface.shape[0] != E:
-        raise ValueError(f"{who}: expected upper (E,5,13,H,W) and surface (E,4,H,W)")
-    if not 2 <= E <= 128:
-        raise ValueError(f"{who}: 2 <= E <= 128 members, got {E}")
-    if upper.shape[-1] % 4:
-        raise ValueError(f"{who}: W % 4 != 0")
-    if (target_upper is None) != (target_surface is None):
-        raise ValueError(f"{who}: give both targets or neither")
+    _check_members(who, upper, surface, target_upper, target_surface)
     thr_u, thr_s, T = _check_thresholds(thresholds, who)
     if T == 0 and target_upper is None:
         raise ValueError(f"{who}: nothing to compute without a target and without thresholds")
@@ -233,23 +338,20 @@ def ensemble_reliability(upper, surface, target_upper, target_surface, threshold
     return ru, rs
 
 
-class ReliabilityAccumulator:
+class ReliabilityAccumulator(_LeadPool):
     """Pools ReliabilityTables over cases, per lead: the tables add exactly (counts in int64, frequencies in float64, on the
     tables' device, no host sync).  leads: the number of leads (0 .. leads-1).  One rank histogram from one case says little;
     this and spread_skill_ratio are the instruments for calibrating the perturbation amplitude."""
 
     _FIELDS = ("rank_counts", "rank_freq", "event_counts", "event_freq", "observed_counts", "observed_freq")
+    _verb = "added"
 
     def __init__(self, leads):
-        self.leads = int(leads)
-        if self.leads < 1:
-            raise ValueError("ReliabilityAccumulator: leads must be >= 1")
-        self._pool = [None] * self.leads
+        super().__init__(leads)
         self.E = self.T = None
 
     def add(self, lead, upper_result, surface_result):
-        if not 0 <= lead < self.leads:
-            raise IndexError(f"lead {lead} outside 0..{self.leads - 1}")
+        self._check_lead(lead)
         for r in (upper_result, surface_result):
             if self.E is None:
                 self.E, self.T = r.E, r.T
@@ -266,14 +368,9 @@ class ReliabilityAccumulator:
                 getattr(pooled, f).add_(wide(getattr(r, f)))
             pooled.cases += r.cases
 
-    def cases(self, lead):
-        return 0 if self._pool[lead] is None else self._pool[lead][0].cases
-
     def tables(self, lead):
         """(upper, surface) pooled ReliabilityTables of a lead."""
-        if self._pool[lead] is None:
-            raise ValueError(f"ReliabilityAccumulator: nothing added at lead {lead}")
-        return self._pool[lead]
+        return self._pooled(lead)
 
     def brier(self, lead):
         return tuple(t.brier() for t in self.tables(lead))
@@ -363,13 +460,12 @@ def _quantiles(x, target, levels, want_fields, what):
         pin = torch.empty((Q, planes), dtype=torch.float32, device=dev)
         cov = torch.empty((Q, planes), dtype=torch.float32, device=dev)
         cnt = torch.empty((Q, planes), dtype=torch.int32, device=dev)
-        w = latitude_weights(H, dev)
+        w = _lat_weights(H, dev)
     ws = torch.empty(quantiles_workspace_bytes(planes, H, Q), dtype=torch.uint8, device=dev)
     lv = (ctypes.c_double * Q)(*levels)
-    ptr = lambda t: t.data_ptr() if t is not None else None
     _lib.check(_lib.load().pangu_ensemble_quantiles_f32(
-        _stream(x), x.data_ptr(), x[0].numel(), E, ctypes.addressof(lv), Q, ptr(target), ptr(w), ptr(fields), ptr(pin), ptr(cnt),
-        ptr(cov), nonfinite.data_ptr(), ws.data_ptr(), ws.numel(), planes, H, W), "ensemble_quantiles_f32")
+        _stream(x), x.data_ptr(), x[0].numel(), E, ctypes.addressof(lv), Q, _ptr(target), _ptr(w), _ptr(fields), _ptr(pin), _ptr(cnt),
+        _ptr(cov), nonfinite.data_ptr(), ws.data_ptr(), ws.numel(), planes, H, W), "ensemble_quantiles_f32")
     shaped = lambda t: None if t is None else t.reshape((Q,) + pshape)
     return QuantileResult(levels, None if fields is None else fields.reshape((Q,) + pshape + (H, W)), shaped(pin),
                           None if cnt is None else shaped(cnt.to(torch.int64)), shaped(cov),
@@ -385,15 +481,7 @@ def ensemble_quantiles(upper, surface, q, target_upper=None, target_surface=None
     want_fields=False skips the (Q, ..., H, W) fields (scores only; needs targets).  Returns (upper_result, surface_result), two
     QuantileResult."""
     who = "ensemble_quantiles"
-    E = upper.shape[0]
-    if upper.dim() != 5 or surface.dim() != 4 or surface.shape[0] != E:
-        raise ValueError(f"{who}: expected upper (E,5,13,H,W) and surface (E,4,H,W)")
-    if not 2 <= E <= 128:
-        raise ValueError(f"{who}: 2 <= E <= 128 members, got {E}")
-    if upper.shape[-1] % 4:
-        raise ValueError(f"{who}: W % 4 != 0")
-    if (target_upper is None) != (target_surface is None):
-        raise ValueError(f"{who}: give both targets or neither")
+    _check_members(who, upper, surface, target_upper, target_surface)
     levels = _check_levels(q, who)
     if not want_fields and target_upper is None:
         raise ValueError(f"{who}: nothing to compute without fields and without a target")
@@ -508,7 +596,7 @@ def _spectrum(x, minus, bw, K, bands, what):
     B = bw.shape[0]
     dev = x.device
     if not x.is_cuda:
-        raise RuntimeError(f"{what}: the Pangu HIP path needs tensors on an MI355X device (got {dev}); there is no CPU fallback")
+        _no_cpu(what, dev)
     if x.dtype != torch.float32:
         raise RuntimeError(f"{what}: expected float32, got {x.dtype}")
     stride = x.stride(0) if N > 1 else item
@@ -529,7 +617,7 @@ def _spectrum(x, minus, bw, K, bands, what):
         n = min(step, N - n0)
         out = torch.empty((n, B, planes, K + 1), dtype=torch.float32, device=dev)
         _lib.check(lib.pangu_zonal_spectrum_f32(
-            _stream(x), x[n0].data_ptr(), stride, n, None if minus is None else minus.data_ptr(), bw.data_ptr(), B,
+            _stream(x), x[n0].data_ptr(), stride, n, _ptr(minus), bw.data_ptr(), B,
             cos_t.data_ptr(), sin_t.data_ptr(), K, out.data_ptr(), ws.data_ptr(), ws.numel(), planes, H, W), "zonal_spectrum_f32")
         outs.append(out)
     power = outs[0] if len(outs) == 1 else torch.cat(outs)
@@ -719,9 +807,9 @@ def _regrid_launch(stream, src_ptr, mul, add, dst_ptr, planes, plan, levels, dev
     """pangu_regrid_planes_f32 with the plan's device tables; mul / add device tensors or None."""
     ls, lc, lw, os_, oc, ow = plan._device_tables(device)
     _lib.check(_lib.load().pangu_regrid_planes_f32(
-        stream, src_ptr, None if mul is None else mul.data_ptr(), None if add is None else add.data_ptr(), dst_ptr, planes,
-        plan.H_in, plan.W_in, plan.H_out, plan.W_out, ls.data_ptr(), lc.data_ptr(), lw.data_ptr(), plan.lat_taps, os_.data_ptr(),
-        oc.data_ptr(), ow.data_ptr(), plan.lon_taps, levels), "regrid_planes_f32")
+        stream, src_ptr, _ptr(mul), _ptr(add), dst_ptr, planes, plan.H_in, plan.W_in, plan.H_out, plan.W_out, ls.data_ptr(),
+        lc.data_ptr(), lw.data_ptr(), plan.lat_taps, os_.data_ptr(), oc.data_ptr(), ow.data_ptr(), plan.lon_taps, levels),
+        "regrid_planes_f32")
 
 
 def regrid(x, plan, mul=None, add=None, flip_levels=False, out=None):
@@ -736,7 +824,7 @@ def regrid(x, plan, mul=None, add=None, flip_levels=False, out=None):
     if not (torch.is_tensor(x) and x.dim() >= 2 and x.dtype == torch.float32 and x.is_contiguous()):
         raise ValueError(f"{who}: x must be a contiguous float32 tensor (.., H, W)")
     if not x.is_cuda:
-        raise RuntimeError(f"{who}: the Pangu HIP path needs tensors on an MI355X device (got {x.device}); there is no CPU fallback")
+        _no_cpu(who, x.device)
     if tuple(x.shape[-2:]) != plan.in_grid:
         raise ValueError(f"{who}: the plan regrids {plan.in_grid} fields, got one on {tuple(x.shape[-2:])}")
     planes = x.numel() // (plan.H_in * plan.W_in)
@@ -768,16 +856,9 @@ def regrid(x, plan, mul=None, add=None, flip_levels=False, out=None):
 def plane_affine(t, stats_last, device):
     """(mul, add) per plane of a NORMALISED model output t, flat fp32 device tensors: t * mul + add is rollout.norm_back.  stats_last
     = (s_mean (1,4,1,1), s_std, u_mean (1,5,13,1,1), u_std); 5-D tensors take the upper-air pair, 4-D ones the surface pair."""
-    s_mean, s_std, u_mean, u_std = stats_last
-    if t.dim() == 5:
-        mean, std = u_mean, u_std
-    elif t.dim() == 4:
-        mean, std = s_mean, s_std
-    else:
+    if t.dim() not in (4, 5):
         raise ValueError("stats_last serves 5-D (B,5,13,H,W) and 4-D (B,4,H,W) tensors only")
-    lead = tuple(t.shape[:-2]) + (1, 1)
-    expand = lambda v: v.to(device=device, dtype=torch.float32).expand(lead).contiguous().view(-1)
-    return expand(std), expand(mean)
+    return _stats_affine(t, stats_last, t.dim() == 5, device)
 
 
 def regrid_fields(upper, surface, plan, stats_last=None):
@@ -798,11 +879,7 @@ def regrid_fields(upper, surface, plan, stats_last=None):
     if tuple(upper.shape[-2:]) != tuple(surface.shape[-2:]):
         raise ValueError("regrid_fields: upper and surface on different grids")
     plan = _as_plan(plan, upper.shape[-2], upper.shape[-1], "regrid_fields")
-    out = []
-    for t in (upper, surface):
-        mul, add = (None, None) if stats_last is None else plane_affine(t, stats_last, t.device)
-        out.append(regrid(t, plan, mul, add))
-    return tuple(out)
+    return tuple(regrid(t, plan, *_stats_affine(t, stats_last, t is upper, t.device)) for t in (upper, surface))
 
 
 # ---- regional scorecard of a deterministic forecast: bias, MAE, RMSE, ACC, activity per (plane, region) ---------------------------
@@ -826,7 +903,6 @@ REGION_PRESETS = {
     "ausnz": ((-45.0, -12.5), (120.0, 175.0)),
 }
 
-_SCORECARD_WEIGHTS = {}               # (H, device) -> latitude_weights(H, device)
 _REGION_PLANS = {}                    # (H, W, regions, device) -> RegionPlan, for region sets without a mask tensor
 
 
@@ -1047,9 +1123,7 @@ def _scorecard(pred, target, target_levels, clim, clim_kind, plan, what):
     p_ptr, t_ptr = _chk(pred, what), _chk(target, what + " target")
     dev = pred.device
     sums = torch.empty(tuple(pred.shape[:-2]) + (R, SCORECARD_SUMS), dtype=torch.float64, device=dev)
-    if (H, str(dev)) not in _SCORECARD_WEIGHTS:      # half a dozen small torch launches otherwise, per tensor and lead
-        _SCORECARD_WEIGHTS[(H, str(dev))] = latitude_weights(H, dev)
-    w = _SCORECARD_WEIGHTS[(H, str(dev))]
+    w = _lat_weights(H, dev)
     lib = _lib.load()
 
     def launch(first, n, clim_ptr):
@@ -1062,8 +1136,7 @@ def _scorecard(pred, target, target_levels, clim, clim_kind, plan, what):
     if clim_kind == 0:
         launch(0, planes, None)
     elif clim_kind == 1:
-        per_case = clim.numel()
-        c = clim.to(device=dev, dtype=torch.float32).reshape(-1).repeat(planes // per_case).contiguous()
+        c = _per_plane(clim, pred, dev)      # named: it must outlive the launch's own allocation
         launch(0, planes, c.data_ptr())
     else:
         per_case = clim.numel() // (H * W)      # the field serves every case: one launch per case, none of them copies it
@@ -1084,18 +1157,7 @@ def deterministic_scores(upper, surface, target_upper, target_surface, regions=N
     with several cases one launch per case).  target_levels_reversed: the upper-air target is stored with its level axis reversed.
     Returns (upper_sums, surface_sums), two ScoreSums with sums (.., 5, 13, R, 10) and (.., 4, R, 10)."""
     who = "deterministic_scores"
-    if upper.dim() < 4 or surface.dim() < 3 or tuple(upper.shape[-4:-2]) != (5, 13) or surface.shape[-3] != 4:
-        raise ValueError(f"{who}: expected upper (.., 5, 13, H, W) and surface (.., 4, H, W)")
-    if tuple(upper.shape[:-4]) != tuple(surface.shape[:-3]) or tuple(upper.shape[-2:]) != tuple(surface.shape[-2:]):
-        raise ValueError(f"{who}: upper and surface disagree in their cases or grids")
-    H, W = upper.shape[-2], upper.shape[-1]
-    if W % 4:
-        raise ValueError(f"{who}: W % 4 != 0")
-    if target_upper is None or target_surface is None:
-        raise ValueError(f"{who}: both targets are required")
-    if target_upper.numel() != upper.numel() or target_surface.numel() != surface.numel():
-        raise ValueError(f"{who}: the targets must hold one value per forecast value, got {tuple(target_upper.shape)} and "
-                         f"{tuple(target_surface.shape)} for {tuple(upper.shape)} and {tuple(surface.shape)}")
+    H, W = _check_cases(who, upper, surface, targets=(target_upper, target_surface), w4=True)
     plan = regions if isinstance(regions, RegionPlan) else region_bits(H, W, regions, upper.device)
     cu = cs = None
     kind = 0
@@ -1119,34 +1181,21 @@ def deterministic_scores(upper, surface, target_upper, target_surface, regions=N
 SCORECARD_METRICS = ("bias", "mae", "rmse", "acc", "acc_centred", "activity_forecast", "activity_target")
 
 
-class ScoreAccumulator:
+class ScoreAccumulator(_LeadPool):
     """Pools ScoreSums over cases, per lead: the float64 sums are added on their device (no host sync), so pooled scores are the
     scores over all cases' points.  leads: the number of leads (0 .. leads-1); regions, clim and
     target_levels_reversed as for deterministic_scores, which score() calls.  The twin of ReliabilityAccumulator, and what
     rollout(scorecard=) feeds."""
 
     def __init__(self, leads, regions=None, clim=None, target_levels_reversed=False):
-        self.leads = int(leads)
-        if self.leads < 1:
-            raise ValueError("ScoreAccumulator: leads must be >= 1")
+        super().__init__(leads)
         self.regions, self.clim, self.target_levels_reversed = regions, clim, bool(target_levels_reversed)
-        self._plans = {}
-        self._pool = [None] * self.leads
         self.names = None
-
-    def _check_lead(self, lead):
-        if not 0 <= lead < self.leads:
-            raise IndexError(f"lead {lead} outside 0..{self.leads - 1}")
 
     def score(self, lead, upper, surface, target_upper, target_surface):
         """deterministic_scores of these fields, pooled at `lead`; returns the two ScoreSums of this call."""
         self._check_lead(lead)
-        plan = self.regions
-        if not isinstance(plan, RegionPlan):
-            key = (upper.shape[-2], upper.shape[-1], str(upper.device))
-            if key not in self._plans:
-                self._plans[key] = region_bits(key[0], key[1], self.regions, upper.device)
-            plan = self._plans[key]
+        plan = self._region_plan(self.regions, upper)
         su, ss = deterministic_scores(upper, surface, target_upper, target_surface, plan, self.clim, self.target_levels_reversed)
         self.add(lead, su, ss)
         return su, ss
@@ -1171,16 +1220,9 @@ class ScoreAccumulator:
             pooled.sums.add_(flat.sum(0))
             pooled.cases += n
 
-    def cases(self, lead):
-        self._check_lead(lead)
-        return 0 if self._pool[lead] is None else self._pool[lead][0].cases
-
     def sums(self, lead):
         """(upper, surface) pooled ScoreSums of a lead, sums (5, 13, R, 10) and (4, R, 10)."""
-        self._check_lead(lead)
-        if self._pool[lead] is None:
-            raise ValueError(f"ScoreAccumulator: nothing scored at lead {lead}")
-        return self._pool[lead]
+        return self._pooled(lead)
 
     def table(self, lead, metrics=SCORECARD_METRICS):
         """The scorecard of a lead on the host: {"regions": names, "cases": n, metric: float64 numpy (69, R), ...}, the 65
@@ -1305,23 +1347,19 @@ def _events(pred, target, target_levels, thr, T, radii, bits, bit, what):
     nplane = len(thr.shape) - 1
     case_shape, plane_shape = tuple(pred.shape[:-2 - nplane]), tuple(pred.shape[-2 - nplane:-2])
     planes = pred.numel() // (H * W)
-    per_case = thr[0].numel()
     stream = _stream(pred)
     p_ptr, t_ptr = _chk(pred, what), _chk(target, what + " target")
     dev = pred.device
     N = len(radii)
-    thr = thr.to(device=dev, dtype=torch.float32).reshape(T, 1, per_case).expand(T, planes // per_case, per_case).contiguous()
+    thr = _per_plane_thresholds(thr, T, planes, dev)
     counts = torch.empty((T, planes, 4), dtype=torch.int64, device=dev)
     wsums = torch.empty((T, planes, 4), dtype=torch.float64, device=dev)
     fss = torch.empty((T, planes, N, 2), dtype=torch.float64, device=dev)
     ws = torch.empty(event_scores_workspace_bytes(planes, H, T, N), dtype=torch.uint8, device=dev)
-    if (H, str(dev)) not in _SCORECARD_WEIGHTS:
-        _SCORECARD_WEIGHTS[(H, str(dev))] = latitude_weights(H, dev)
-    w = _SCORECARD_WEIGHTS[(H, str(dev))]
     host_radii = (ctypes.c_int * N)(*radii)
     _lib.check(_lib.load().pangu_event_scores_f32(
-        stream, p_ptr, t_ptr, target_levels, thr.data_ptr(), T, host_radii, N, w.data_ptr(), None if bits is None else bits.data_ptr(),
-        bit, counts.data_ptr(), wsums.data_ptr(), fss.data_ptr(), ws.data_ptr(), ws.numel(), planes, H, W), "event_scores_f32")
+        stream, p_ptr, t_ptr, target_levels, thr.data_ptr(), T, host_radii, N, _lat_weights(H, dev).data_ptr(), _ptr(bits), bit,
+        counts.data_ptr(), wsums.data_ptr(), fss.data_ptr(), ws.data_ptr(), ws.numel(), planes, H, W), "event_scores_f32")
     nc = len(case_shape)
     shape = (T,) + case_shape + plane_shape
     return (counts.reshape(shape + (4,)).movedim(0, nc), wsums.reshape(shape + (4,)).movedim(0, nc),
@@ -1358,18 +1396,7 @@ def event_scores(upper, surface, target_upper, target_surface, thresholds, radii
     target_levels_reversed: the upper-air target is stored with its level axis reversed.
     Returns (upper_scores, surface_scores), two EventScores."""
     who = "event_scores"
-    if upper.dim() < 4 or surface.dim() < 3 or tuple(upper.shape[-4:-2]) != (5, 13) or surface.shape[-3] != 4:
-        raise ValueError(f"{who}: expected upper (.., 5, 13, H, W) and surface (.., 4, H, W)")
-    if tuple(upper.shape[:-4]) != tuple(surface.shape[:-3]) or tuple(upper.shape[-2:]) != tuple(surface.shape[-2:]):
-        raise ValueError(f"{who}: upper and surface disagree in their cases or grids")
-    H, W = upper.shape[-2], upper.shape[-1]
-    if W % 4 or W > EVENT_MAX_W:
-        raise ValueError(f"{who}: W % 4 != 0 or W > {EVENT_MAX_W}")
-    if target_upper is None or target_surface is None:
-        raise ValueError(f"{who}: both targets are required")
-    if target_upper.numel() != upper.numel() or target_surface.numel() != surface.numel():
-        raise ValueError(f"{who}: the targets must hold one value per forecast value, got {tuple(target_upper.shape)} and "
-                         f"{tuple(target_surface.shape)} for {tuple(upper.shape)} and {tuple(surface.shape)}")
+    H, W = _check_cases(who, upper, surface, targets=(target_upper, target_surface), w4=True, max_w=EVENT_MAX_W)
     thr_u, thr_s, T = _check_thresholds(thresholds, who)
     if T == 0:
         raise ValueError(f"{who}: thresholds are required: a pair of tensors (T, 5, 13) and (T, 4)")
@@ -1384,16 +1411,14 @@ def event_scores(upper, surface, target_upper, target_surface, thresholds, radii
 EVENT_METRICS = ("pod", "far", "csi", "frequency_bias", "ets", "base_rate")
 
 
-class EventAccumulator:
+class EventAccumulator(_LeadPool):
     """Pools EventScores over cases, per lead: counts add in int64 and the weighted sums in float64 on their device (no host
     sync), so pooled scores are the scores over all cases' points and the pooled FSS is 1 - sum num / sum den.  leads: the number
     of leads (0 .. leads-1); thresholds, radii, regions, region and target_levels_reversed as for event_scores, which score()
     calls.  The twin of ScoreAccumulator, and what rollout(events=) feeds."""
 
     def __init__(self, leads, thresholds, radii, regions=None, region=None, target_levels_reversed=False):
-        self.leads = int(leads)
-        if self.leads < 1:
-            raise ValueError("EventAccumulator: leads must be >= 1")
+        super().__init__(leads)
         _, _, T = _check_thresholds(thresholds, "EventAccumulator")
         if T == 0:
             raise ValueError("EventAccumulator: thresholds are required: a pair of tensors (T, 5, 13) and (T, 4)")
@@ -1402,22 +1427,11 @@ class EventAccumulator:
         if regions is None and region is not None:
             raise ValueError(f"EventAccumulator: region {region!r} named without regions")
         self.regions, self.region, self.target_levels_reversed = regions, region, bool(target_levels_reversed)
-        self._plans = {}
-        self._pool = [None] * self.leads
-
-    def _check_lead(self, lead):
-        if not 0 <= lead < self.leads:
-            raise IndexError(f"lead {lead} outside 0..{self.leads - 1}")
 
     def score(self, lead, upper, surface, target_upper, target_surface):
         """event_scores of these fields, pooled at `lead`; returns the two EventScores of this call."""
         self._check_lead(lead)
-        plan = self.regions
-        if plan is not None and not isinstance(plan, RegionPlan):
-            key = (upper.shape[-2], upper.shape[-1], str(upper.device))
-            if key not in self._plans:
-                self._plans[key] = region_bits(key[0], key[1], self.regions, upper.device)
-            plan = self._plans[key]
+        plan = None if self.regions is None else self._region_plan(self.regions, upper)
         eu, es = event_scores(upper, surface, target_upper, target_surface, self.thresholds, self.radii, plan, self.region,
                               self.target_levels_reversed)
         self.add(lead, eu, es)
@@ -1448,16 +1462,9 @@ class EventAccumulator:
             pooled.fss_sums.add_(f.sum(0))
             pooled.cases += n
 
-    def cases(self, lead):
-        self._check_lead(lead)
-        return 0 if self._pool[lead] is None else self._pool[lead][0].cases
-
     def sums(self, lead):
         """(upper, surface) pooled EventScores of a lead, counts (T, 5, 13, 4) and (T, 4, 4)."""
-        self._check_lead(lead)
-        if self._pool[lead] is None:
-            raise ValueError(f"EventAccumulator: nothing scored at lead {lead}")
-        return self._pool[lead]
+        return self._pooled(lead)
 
     def table(self, lead, metrics=EVENT_METRICS):
         """The event scores of a lead on the host: {"cases": n, "radii": radii, metric: float64 numpy (T, 69), ..., "fss": (T, 69, N),
@@ -1503,10 +1510,9 @@ class LeadWindowResult:
 def _lead_stats_launch(stream, src_ptr, mul, add, fields, thr, T, planes, plane_elems, levels, lead, first):
     """pangu_lead_stats_update_f32; fields: a dict of the kept device tensors among sum, min, max, when_min, when_max, count, run,
     longest; mul / add / thr device tensors or None."""
-    ptr = lambda t: None if t is None else t.data_ptr()
-    f = lambda k: ptr(fields.get(k))
+    f = lambda k: _ptr(fields.get(k))
     _lib.check(_lib.load().pangu_lead_stats_update_f32(
-        stream, src_ptr, ptr(mul), ptr(add), f("sum"), f("min"), f("max"), f("when_min"), f("when_max"), ptr(thr) if T else None, T,
+        stream, src_ptr, _ptr(mul), _ptr(add), f("sum"), f("min"), f("max"), f("when_min"), f("when_max"), _ptr(thr) if T else None, T,
         f("count"), f("run"), f("longest"), planes, plane_elems, levels, lead, 1 if first else 0), "lead_stats_update_f32")
 
 
@@ -1611,20 +1617,10 @@ class LeadWindowStats:
     def _allocate(self, upper, surface):
         dev = upper.device
         self._aux = []
-        for t, pshape, thr in ((upper, (5, 13), self.thresholds[0] if self.T else None),
-                               (surface, (4,), self.thresholds[1] if self.T else None)):
-            mul = add = None
-            if self.stats_last is not None:
-                s_mean, s_std, u_mean, u_std = self.stats_last
-                mean, std = (u_mean, u_std) if len(pshape) == 2 else (s_mean, s_std)
-                lead = tuple(t.shape[:-2]) + (1, 1)
-                expand = lambda v: v.to(device=dev, dtype=torch.float32).reshape(pshape + (1, 1)).expand(lead).contiguous().view(-1)
-                mul, add = expand(std), expand(mean)
+        for t, thr in zip((upper, surface), self.thresholds if self.T else (None, None)):
             if thr is not None:
-                per = thr[0].numel()
-                planes = t.numel() // (t.shape[-1] * t.shape[-2])
-                thr = thr.to(device=dev, dtype=torch.float32).reshape(self.T, 1, per).expand(self.T, planes // per, per).contiguous()
-            self._aux.append((mul, add, thr))
+                thr = _per_plane_thresholds(thr, self.T, t.numel() // (t.shape[-1] * t.shape[-2]), dev)
+            self._aux.append(_stats_affine(t, self.stats_last, t is upper, dev) + (thr,))
         dtype = lambda k: torch.float32 if k in ("sum", "min", "max") else torch.uint8
         self._acc = [tuple({k: torch.empty(self._field_shape(k, t.shape), dtype=dtype(k), device=dev) for k in self._kept}
                            for t in (upper, surface)) for _ in self.windows]
@@ -1650,15 +1646,7 @@ class LeadWindowStats:
         for (a, b), seen in zip(self.windows, self._seen):
             if seen < b - a and lead >= a and lead != a + seen:
                 raise ValueError(f"{who}: window ({a}, {b}) expects lead {a + seen} next, got {lead}: every lead of a window must arrive")
-        for t, name in ((upper, "upper"), (surface, "surface")):
-            if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.is_contiguous()):
-                raise ValueError(f"{who}: {name} must be a contiguous float32 tensor")
-        if upper.dim() < 4 or surface.dim() < 3 or tuple(upper.shape[-4:-2]) != (5, 13) or surface.shape[-3] != 4:
-            raise ValueError(f"{who}: expected upper (.., 5, 13, H, W) and surface (.., 4, H, W)")
-        if tuple(upper.shape[:-4]) != tuple(surface.shape[:-3]) or tuple(upper.shape[-2:]) != tuple(surface.shape[-2:]):
-            raise ValueError(f"{who}: upper and surface disagree in their leading dimensions or grids")
-        if upper.numel() == 0 or upper.device != surface.device:
-            raise ValueError(f"{who}: empty tensors, or upper and surface on different devices")
+        _check_cases(who, upper, surface, dense=True)
         shapes = (tuple(upper.shape), tuple(surface.shape), upper.device)
         if self._shapes is not None and shapes != self._shapes:
             raise ValueError(f"{who}: shapes and device must stay those of the first update, {self._shapes}; got {shapes}")
@@ -1667,8 +1655,7 @@ class LeadWindowStats:
     def _fold(self, lead, upper, surface):
         """The device side of update(): the accumulators (at the first call) and one launch per tensor and window that holds lead."""
         if not upper.is_cuda:
-            raise RuntimeError(f"LeadWindowStats.update: the Pangu HIP path needs tensors on an MI355X device (got {upper.device}); "
-                               "there is no CPU fallback")
+            _no_cpu("LeadWindowStats.update", upper.device)
         stream = _stream(upper)
         if self._acc is None:
             self._allocate(upper, surface)
@@ -1810,35 +1797,18 @@ def point_plan(H, W, lat, lon, regions=None, device=None):
 def _check_point_fields(upper, surface, plan, who):
     if not isinstance(plan, PointPlan):
         raise ValueError(f"{who}: plan must be a score.PointPlan")
-    for t, name in ((upper, "upper"), (surface, "surface")):
-        if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.is_contiguous()):
-            raise ValueError(f"{who}: {name} must be a contiguous float32 tensor")
-    if upper.dim() < 4 or surface.dim() < 3 or tuple(upper.shape[-4:-2]) != (5, 13) or surface.shape[-3] != 4:
-        raise ValueError(f"{who}: expected upper (.., 5, 13, H, W) and surface (.., 4, H, W)")
-    if tuple(upper.shape[:-4]) != tuple(surface.shape[:-3]) or tuple(upper.shape[-2:]) != tuple(surface.shape[-2:]):
-        raise ValueError(f"{who}: upper and surface disagree in their leading dimensions or grids")
-    if upper.numel() == 0 or upper.device != surface.device:
-        raise ValueError(f"{who}: empty tensors, or upper and surface on different devices")
+    _check_cases(who, upper, surface, dense=True)
     if tuple(upper.shape[-2:]) != (plan.H, plan.W) or plan.device != upper.device:
         raise ValueError(f"{who}: the point plan is for a {(plan.H, plan.W)} grid on {plan.device}, the fields are "
                          f"{tuple(upper.shape[-2:])} on {upper.device}")
     if not upper.is_cuda:
-        raise RuntimeError(f"{who}: the Pangu HIP path needs tensors on an MI355X device (got {upper.device}); there is no CPU fallback")
-
-
-def _plane_vector(values, t, nplane, device):
-    """fp32 (planes,): one value per (variable, level) of `values` ((.., 5, 13, 1, 1) or (.., 4, 1, 1) statistics) for every plane of
-    t, whose last nplane + 2 dimensions are the planes and the grid."""
-    pshape = tuple(t.shape[-2 - nplane:-2])
-    lead = tuple(t.shape[:-2]) + (1, 1)
-    return values.to(device=device, dtype=torch.float32).reshape(pshape + (1, 1)).expand(lead).contiguous().view(-1)
+        _no_cpu(who, upper.device)
 
 
 def _sample_launch(t, plan, mul, add, levels, out):
     planes = t.numel() // (plan.H * plan.W)
-    ptr = lambda v: None if v is None else v.data_ptr()
     _lib.check(_lib.load().pangu_sample_points_f32(
-        _stream(t), t.data_ptr(), ptr(mul), ptr(add), plan.row.data_ptr(), plan.col.data_ptr(), plan.wy.data_ptr(),
+        _stream(t), t.data_ptr(), _ptr(mul), _ptr(add), plan.row.data_ptr(), plan.col.data_ptr(), plan.wy.data_ptr(),
         plan.wx.data_ptr(), out.data_ptr(), planes, plan.H, plan.W, plan.N, levels), "sample_points_f32")
     return out
 
@@ -1853,12 +1823,8 @@ def sample_points(upper, surface, plan, stats_last=None, levels_reversed=False, 
     who = "sample_points"
     _check_point_fields(upper, surface, plan, who)
     res = []
-    for k, (t, nplane, levels) in enumerate(((upper, 2, 13 if levels_reversed else 0), (surface, 1, 0))):
-        mul = add = None
-        if stats_last is not None:
-            s_mean, s_std, u_mean, u_std = stats_last
-            mean, std = (u_mean, u_std) if nplane == 2 else (s_mean, s_std)
-            mul, add = _plane_vector(std, t, nplane, t.device), _plane_vector(mean, t, nplane, t.device)
+    for k, (t, levels) in enumerate(((upper, 13 if levels_reversed else 0), (surface, 0))):
+        mul, add = _stats_affine(t, stats_last, k == 0, t.device)
         shape = tuple(t.shape[:-2]) + (plan.N,)
         if out is None:
             o = torch.empty(shape, dtype=torch.float32, device=t.device)
@@ -1886,10 +1852,9 @@ def _point_scores(t, obs, clim, plan, want_departures, what):
     sums = torch.empty(tuple(t.shape[:-2]) + (plan.R, SCORECARD_SUMS), dtype=torch.float64, device=dev)
     dep = torch.empty(shape, dtype=torch.float32, device=dev) if want_departures else None
     ws = torch.empty(point_scores_workspace_bytes(planes, plan.N, plan.R), dtype=torch.uint8, device=dev)
-    ptr = lambda v: None if v is None else v.data_ptr()
     _lib.check(_lib.load().pangu_point_scores_f32(
         _stream(t), t.data_ptr(), None, None, plan.row.data_ptr(), plan.col.data_ptr(), plan.wy.data_ptr(), plan.wx.data_ptr(),
-        o_ptr, ptr(clim), None if plan.everywhere else plan.bits.data_ptr(), plan.R, ptr(dep), sums.data_ptr(), ws.data_ptr(),
+        o_ptr, _ptr(clim), None if plan.everywhere else plan.bits.data_ptr(), plan.R, _ptr(dep), sums.data_ptr(), ws.data_ptr(),
         ws.numel(), planes, plan.H, plan.W, plan.N, 0), "point_scores_f32")
     return sums, dep
 
@@ -1913,7 +1878,7 @@ def observation_scores(upper, surface, obs_upper, obs_surface, plan, clim=None, 
         clim = tuple(clim)
         if len(clim) != 4 or clim[2].numel() != 65 or clim[0].numel() != 4:
             raise ValueError(f"{who}: clim is None or stats_last, whose means hold 5 x 13 and 4 values")
-        cu, cs = _plane_vector(clim[2], upper, 2, upper.device), _plane_vector(clim[0], surface, 1, upper.device)
+        cu, cs = _per_plane(clim[2], upper, upper.device), _per_plane(clim[0], surface, upper.device)
     su, du = _point_scores(upper, obs_upper, cu, plan, want_departures, who + ": upper")
     ss, ds = _point_scores(surface, obs_surface, cs, plan, want_departures, who + ": surface")
     res = (ScoreSums(su, plan.names), ScoreSums(ss, plan.names))
@@ -1936,7 +1901,7 @@ class ObservationAccumulator:
 
     def score(self, lead, upper, surface, obs_upper, obs_surface):
         """observation_scores of these fields and reports, pooled at `lead`; returns the two ScoreSums of this call."""
-        self._pool._check_lead(lead)
+        self.cases(lead)                                # refuses a lead outside the pool before any launch
         su, ss = observation_scores(upper, surface, obs_upper, obs_surface, self.plan, self.clim)
         self._pool.add(lead, su, ss)
         return su, ss
@@ -1946,8 +1911,7 @@ class ObservationAccumulator:
 
     def result(self, lead):
         """(upper, surface) pooled ScoreSums of a lead, sums (5, 13, R, 10) and (4, R, 10)."""
-        self._pool._check_lead(lead)
-        if self._pool.cases(lead) == 0:
+        if self.cases(lead) == 0:
             raise ValueError(f"ObservationAccumulator: nothing scored at lead {lead}")
         return self._pool.sums(lead)
 

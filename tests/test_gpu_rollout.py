@@ -64,6 +64,47 @@ def test_rollout_graph_equals_eager_and_bf16_drift(setup):
     assert drifts[0] < 5e-2 and drifts[-1] < 0.3
 
 
+class _Recorder:
+    """A stand-in for any of rollout()'s six hooks: what rollout() reads of a hook before the first step, and the one method it
+    calls behind a step, which logs (hook, k, data_ptr of the upper-air fields, shapes) and what else it was handed."""
+    leads, windows, stats_last = 2, ((0, 2),), None
+
+    def __init__(self, hook, log):
+        self.hook, self.log = hook, log
+
+    def _seen(self, k, upper, surface, *rest):
+        self.log.append((self.hook, k, upper.data_ptr(), (tuple(upper.shape), tuple(surface.shape)), rest))
+
+    def submit(self, tensors, tag=None):
+        self._seen(tag, *tensors)
+
+    score = update = record = _seen
+
+
+def test_rollout_hooks_meet_every_step_alike_in_both_arms(setup):
+    """steps=2 with recording stand-ins for the six hooks: the graph arm and the eager arm hand each step's fields to the hooks in
+    the documented order (drain, scorecard, events, lead_stats, sites, observations), every hook of a step sees the same tensors (in
+    the graph arm the static buffers, at every step), and a None target or obs entry skips exactly the hooks that read it."""
+    P, m, (inp, inp_s, stats, maps, const_h) = setup
+    sl = _stats_last(stats, "cuda")
+    targets, obs = [("tu", "ts"), None], [None, ("ou", "os")]
+    logs = {}
+    for graph in (True, False):
+        log = logs[graph] = []
+        hooks = {h: _Recorder(h, log) for h in ("drain", "scorecard", "events", "lead_stats", "sites", "observations")}
+        P.rollout.rollout(m, inp, inp_s, stats, maps, const_h, sl, steps=2, graph=graph, targets=targets, obs=obs, **hooks)
+    shapes = (tuple(inp.shape), tuple(inp_s.shape))
+    want = [("drain", 0, ()), ("scorecard", 0, targets[0]), ("events", 0, targets[0]), ("lead_stats", 0, ()), ("sites", 0, ()),
+            ("drain", 1, ()), ("lead_stats", 1, ()), ("sites", 1, ()), ("observations", 1, obs[1])]
+    for graph, log in logs.items():
+        assert [(h, k, rest) for h, k, _, _, rest in log] == want, graph
+        assert all(s == shapes for _, _, _, s, _ in log), graph
+        for k in (0, 1):
+            assert len({ptr for _, lead, ptr, _, _ in log if lead == k}) == 1, (graph, k)      # one step, one pair of fields
+    assert len({ptr for _, _, ptr, _, _ in logs[True]}) == 1                                    # the graph's static input buffer
+    assert [(h, k, s) for h, k, _, s, _ in logs[True]] == [(h, k, s) for h, k, _, s, _ in logs[False]]
+
+
 def test_rollout_two_steps_vs_reference_golden(setup, golden_dir):
     """Two chained 24 h steps (the loop of reference inference/inference_singleOutput.py:97-105 with normBackData,
     era5_data/utils_data.py:324-330, between them) through the fp32 hipGraph rollout == the REFERENCE run the same way
