@@ -78,6 +78,13 @@ int pangu_linear_fwd(pangu_stream_t stream, const float* A, int lda, const float
 int pangu_split_weight_bf16x3(pangu_stream_t stream, const float* W, int N, int K, void* image);
 int pangu_linear_fwd_split(pangu_stream_t stream, const float* A, int lda, const void* image, const float* bias,
                            float* C, int ldc, int M, int N, int K, int act);
+/* The column-padded form of the two, for any N % 4 == 0 (K % 16 == 0): the image is that of W extended by zero rows to
+ * Npad = 192 * ceil(N / 192) rows (6 * Npad * K bytes, a zero row +0 in all three planes), and the GEMM runs whole 192-column
+ * tiles over it but neither reads bias[N..] nor writes a column >= N of C (ldc may exceed N) or a row >= M: per element the
+ * product of pangu_linear_fwd_split on the zero-extended weight, bit for bit.  PANGU_E_SHAPE for N % 4 != 0 or K % 16 != 0. */
+int pangu_split_weight_bf16x3_padded(pangu_stream_t stream, const float* W, int N, int K, void* image);
+int pangu_linear_fwd_split_padded(pangu_stream_t stream, const float* A, int lda, const void* image, const float* bias,
+                                  float* C, int ldc, int M, int N, int K, int act);
 
 /* Weight/bias gradient of a projection (autograd of the calls above; the training step of reference
  * models/pangu_sample.py:71 `loss.backward()`):

@@ -457,15 +457,20 @@ class PatchRecoverHalvesFn(torch.autograd.Function):
     layer of the whole-model driver in training and inference: without a graph its forward is the inference recovery."""
 
     @staticmethod
-    def forward(ctx, skip, x, cw, cb, sw, sb, geom, skip_grad=None, sh=None):
+    def forward(ctx, skip, x, cw, cb, sw, sb, geom, skip_grad=None, sh=None, split=None):
+        # split: frozen fp32 inference only (the caller decides: a forward cannot read grad mode) -- the padded split images
+        # (surface, upper air) of the two conv weights, either None where that launch stays on the fp32-MFMA kernel
         ctx.skip_grad = skip_grad
         ctx.pr = pr = _precision(sh)
         n_s, LAT, LON = geom
         N, C = skip.shape
         assert skip.stride() == (2 * C, 1) and x.stride() == (2 * C, 1) and x.data_ptr() == skip.data_ptr() + skip.element_size() * C
         cat = torch.as_strided(skip, (N, 2 * C), (2 * C, 1), skip.storage_offset())
-        y_s = pr.k.linear(cat[:n_s], pr.w(sw), sb, **pr.f32_out)
-        y_u = pr.k.linear(cat[n_s:], pr.w(cw), cb, **pr.f32_out)
+        img_s, img_u = split if split is not None and sh is None else (None, None)
+        y_s = ops.linear_split(cat[:n_s], img_s, sw.shape[0], sb, padded=True) if img_s is not None else \
+            pr.k.linear(cat[:n_s], pr.w(sw), sb, **pr.f32_out)
+        y_u = ops.linear_split(cat[n_s:], img_u, cw.shape[0], cb, padded=True) if img_u is not None else \
+            pr.k.linear(cat[n_s:], pr.w(cw), cb, **pr.f32_out)
         ctx.save_for_backward(cat, cw, sw)
         ctx.geom = geom
         return ops.patch_recover_scatter(y_u, y_s, LAT, LON)

@@ -31,15 +31,21 @@ using Tile = SplitTile<4, 1, 2, true>;           // 4 x 1 row-owning waves, ring
 constexpr int BM = Tile::BM;                     // 128
 constexpr int BN = Tile::BN;                     // 192 = W_ROWS: one n-tile block of the image per tile
 
-// One thread per (row n, 8 consecutive k): W[N][K] fp32 -> the three planes of the image (layout above; N % 192 == 0, K % 16 == 0)
+// One thread per (row n, 8 consecutive k): W[N][K] fp32 -> the three planes of the image (layout above; N % 192 == 0, K % 16 == 0).
+// PAD: the image has `rows` >= N rows (a multiple of 192); rows >= N are zero rows, never read from W, +0 in all three planes.
+template <bool PAD>
 __global__ __launch_bounds__(256) void split_weight_kernel(const float* __restrict__ W, unsigned char* __restrict__ image, int N,
-                                                           int K) {
+                                                           int K, int rows) {
   const int kc = K >> 3;
   const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (t >= (long long)N * kc) return;
+  if (t >= (long long)(PAD ? rows : N) * kc) return;
   const int n = (int)(t / kc), c = (int)(t - (long long)n * kc);
   const float* src = W + (size_t)n * K + c * 8;
-  const f32x4 c0 = *reinterpret_cast<const f32x4*>(src), c1 = *reinterpret_cast<const f32x4*>(src + 4);
+  f32x4 c0 = {0.f, 0.f, 0.f, 0.f}, c1 = {0.f, 0.f, 0.f, 0.f};
+  if (!PAD || n < N) {
+    c0 = *reinterpret_cast<const f32x4*>(src);
+    c1 = *reinterpret_cast<const f32x4*>(src + 4);
+  }
   bf16x8 p[3];
   split8(c0, c1, p[0], p[1], p[2]);
   const int nt = n / BN, nl = n - nt * BN, kt = c >> 1, lh = c & 1;
@@ -48,7 +54,10 @@ __global__ __launch_bounds__(256) void split_weight_kernel(const float* __restri
   for (int q = 0; q < 3; ++q) *reinterpret_cast<bf16x8*>(dst + q * PLANE) = p[q];
 }
 
-template <int ACT, bool HAS_BIAS>
+// PADN: the image has 192 n_tiles rows, of which the first N (N % 4 == 0) are W's and the rest zero rows; the epilogue skips the
+// bias load and the store of every 16-byte column segment that starts at a column >= N (segments are whole: N % 4 == 0), so
+// neither bias[N..] is read nor C's columns >= N are written (ldc may exceed N).  The product is the unpadded kernel's.
+template <int ACT, bool HAS_BIAS, bool PADN = false>
 __global__ __launch_bounds__(256, 3) void gemm_f32_split_kernel(const float* __restrict__ A, int lda,
                                                                 const unsigned char* __restrict__ image,
                                                                 const float* __restrict__ bias, float* __restrict__ C, int ldc,
@@ -68,7 +77,7 @@ __global__ __launch_bounds__(256, 3) void gemm_f32_split_kernel(const float* __r
   const int lr = lane & 31, lh = lane >> 5;
 
   f32x16 acc[1][6];                                // the wave's rows 32 wave .. +31 x the tile's 192 columns
-  split_main_loop<4, 1, 2, true, true>(smem, A, lda, image, M, N, K, m0, n_tile, acc);
+  split_main_loop<4, 1, 2, true, true>(smem, A, lda, image, M, PADN ? n_tiles * BN : N, K, m0, n_tile, acc);
 
   // epilogue (as gemm_f32_dma.hip): each 32x32 tile is transposed through a wave-private LDS patch -> 16-B row segments
   constexpr int EP_LD = 36;
@@ -80,8 +89,9 @@ __global__ __launch_bounds__(256, 3) void gemm_f32_split_kernel(const float* __r
 #pragma unroll
   for (int j = 0; j < 6; ++j) {
     const int col = n0 + j * 32 + ec;
+    const bool live = !PADN || col < N;            // PADN: this lane's column segment of the tile exists
     f32x4 bv = {0.f, 0.f, 0.f, 0.f};
-    if (HAS_BIAS) bv = *reinterpret_cast<const f32x4*>(bias + col);
+    if (HAS_BIAS && live) bv = *reinterpret_cast<const f32x4*>(bias + col);
 #pragma unroll
     for (int r = 0; r < 16; ++r) ep[((r & 3) + 8 * (r >> 2) + 4 * lh) * EP_LD + lr] = acc[0][j][r];
 #pragma unroll
@@ -94,7 +104,7 @@ __global__ __launch_bounds__(256, 3) void gemm_f32_split_kernel(const float* __r
       }
       // rows >= M fall outside the descriptor's range and are dropped; non-temporal as in gemm_f32_dma.hip
       const unsigned off = ((unsigned)(row0 + 8 * it) * (unsigned)ldc + (unsigned)col) * 4u;
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), c_rsrc, (int)off, 0, 2);
+      if (live) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), c_rsrc, (int)off, 0, 2);
     }
   }
 }
@@ -106,8 +116,19 @@ extern "C" int pangu_split_weight_bf16x3(pangu_stream_t stream, const float* W, 
   if (N <= 0 || K <= 0 || (N % BN) != 0 || (K % BK) != 0) return PANGU_E_SHAPE;
   if ((long long)N * K * 6 >= 0xFFFFFFFFll) return PANGU_E_RANGE;
   const long long threads = (long long)N * (K / 8);
-  hipLaunchKernelGGL(split_weight_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, W,
-                     reinterpret_cast<unsigned char*>(image), N, K);
+  hipLaunchKernelGGL(split_weight_kernel<false>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, W,
+                     reinterpret_cast<unsigned char*>(image), N, K, N);
+  return pangu_launch_status();
+}
+
+extern "C" int pangu_split_weight_bf16x3_padded(pangu_stream_t stream, const float* W, int N, int K, void* image) {
+  if (!W || !image) return PANGU_E_NULL;
+  if (N <= 0 || K <= 0 || (N % 4) != 0 || (K % BK) != 0) return PANGU_E_SHAPE;
+  const long long rows = ((long long)N + BN - 1) / BN * BN;
+  if (rows * K * 6 >= 0xFFFFFFFFll) return PANGU_E_RANGE;
+  const long long threads = rows * (K / 8);
+  hipLaunchKernelGGL(split_weight_kernel<true>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, W,
+                     reinterpret_cast<unsigned char*>(image), N, K, (int)rows);
   return pangu_launch_status();
 }
 
@@ -124,6 +145,29 @@ extern "C" int pangu_linear_fwd_split(pangu_stream_t stream, const float* A, int
   const unsigned char* img = reinterpret_cast<const unsigned char*>(image);
 #define PANGU_SPLIT_LAUNCH(ACT, HB) \
   hipLaunchKernelGGL((gemm_f32_split_kernel<ACT, HB>), g, blk, 0, s, A, lda, img, bias, C, ldc, M, N, K, m_tiles, n_tiles)
+  if (act == PANGU_ACT_GELU) {
+    if (bias) PANGU_SPLIT_LAUNCH(PANGU_ACT_GELU, true); else PANGU_SPLIT_LAUNCH(PANGU_ACT_GELU, false);
+  } else {
+    if (bias) PANGU_SPLIT_LAUNCH(PANGU_ACT_NONE, true); else PANGU_SPLIT_LAUNCH(PANGU_ACT_NONE, false);
+  }
+#undef PANGU_SPLIT_LAUNCH
+  return pangu_launch_status();
+}
+
+extern "C" int pangu_linear_fwd_split_padded(pangu_stream_t stream, const float* A, int lda, const void* image,
+                                             const float* bias, float* C, int ldc, int M, int N, int K, int act) {
+  if (!A || !image || !C) return PANGU_E_NULL;
+  if (M <= 0 || N <= 0 || K <= 0 || lda < K || ldc < N || (lda & 3) || (ldc & 3)) return PANGU_E_SHAPE;
+  if (act != PANGU_ACT_NONE && act != PANGU_ACT_GELU) return PANGU_E_ARG;
+  if ((N % 4) != 0 || (K % BK) != 0) return PANGU_E_SHAPE;       // not served: the caller takes pangu_linear_fwd
+  const long long rows = ((long long)N + BN - 1) / BN * BN;       // rows of the padded image
+  if (!pangu_fits_u32(M, lda, 4) || !pangu_fits_u32(M, ldc, 4) || rows * K * 6 >= 0xFFFFFFFFll) return PANGU_E_RANGE;
+  const int m_tiles = (M + BM - 1) / BM, n_tiles = (int)(rows / BN);
+  const dim3 g(((m_tiles + 7) / 8) * 8 * n_tiles), blk(256);
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned char* img = reinterpret_cast<const unsigned char*>(image);
+#define PANGU_SPLIT_LAUNCH(ACT, HB) \
+  hipLaunchKernelGGL((gemm_f32_split_kernel<ACT, HB, true>), g, blk, 0, s, A, lda, img, bias, C, ldc, M, N, K, m_tiles, n_tiles)
   if (act == PANGU_ACT_GELU) {
     if (bias) PANGU_SPLIT_LAUNCH(PANGU_ACT_GELU, true); else PANGU_SPLIT_LAUNCH(PANGU_ACT_GELU, false);
   } else {

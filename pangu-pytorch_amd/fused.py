@@ -231,11 +231,41 @@ def sample_block(blk, x, Z, H, W, roll, out=None, sh=None, infer=False):
         *_layers.lora_args(blk.linear.linear1, blk.linear.linear2, att.linear1, att.linear2))
 
 
+# (N, K) of the projections outside the blocks (down/up-sampling, patch embedding, patch recovery) that stay on the fp32-MFMA
+# kernel although the column-padded split kernel serves them: same form as _LN_SPLIT_NOT_DISPATCHED.  The two surface launches
+# (M = 65160), under 0.1 ms of the step together: patch recovery (64, 384) measured 0.94 - 0.99 x per launch (N = 64 padded to a
+# 192-column tile triples its matrix work); patch embedding (192, 112) measured 38 -> 25 us per launch, but the headline and the
+# 7-step rollout's step-7 error (6.76e-4 of the 1e-3 that tests/test_gpu_rollout.py allows, and it moves with any rounding detail)
+# were taken without it, so it stays here until both are re-taken with it (profiles/f32_split_resampling.md).
+_RESAMPLE_SPLIT_NOT_DISPATCHED = {(192, 112), (64, 384)}
+
+
+def _resample_image(m, lin):
+    """The padded split image of the projection `lin` of the resampling / embedding / recovery module `m` in frozen fp32
+    inference, or None where the launch stays on the fp32-MFMA kernel: the module's split_projections flag is off
+    (PanguModel.use_split_projections), the shape is listed in _RESAMPLE_SPLIT_NOT_DISPATCHED, or the kernel does not serve it
+    (N % 4, K % 16).  Cached and keyed like _plain_proj's: a LoRA layer's image is that of its W_eff."""
+    w = _layers.eff_weight(lin)
+    w2 = w.reshape(w.shape[0], -1)              # Conv1d(k=1) weights are (out, in, 1)
+    if not getattr(m, "split_projections", True) or tuple(w2.shape) in _RESAMPLE_SPLIT_NOT_DISPATCHED:
+        return None
+    return ops.split_image(lin, w, None if w is lin.weight else ("lora",) + tuple(lin._stamp()), padded=True)
+
+
+def _resample_proj(m, lin, x2, out=None):
+    """A projection outside the blocks in frozen fp32 inference: the exact-split kernel from the cached padded image
+    (_resample_image), the fp32-MFMA kernel otherwise.  x2 / out may be row-strided."""
+    image = _resample_image(m, lin)
+    if image is not None:
+        return ops.linear_split(x2, image, lin.weight.shape[0], lin.bias, out=out, padded=True)
+    return ops.linear(x2, _layers.eff_weight(lin), lin.bias, out=out)
+
+
 def _embed_rows(m, inp, inp_surface, consts, levels_reversed, out):
     a_s, a_u = ops.patch_embed_gather(inp, inp_surface, *consts, levels_reversed)
     n_s = a_s.shape[0]
-    ops.linear(a_s, m.conv_surface.weight, m.conv_surface.bias, out=out[:n_s])
-    ops.linear(a_u, m.conv.weight, m.conv.bias, out=out[n_s:])
+    _resample_proj(m, m.conv_surface, a_s, out=out[:n_s])
+    _resample_proj(m, m.conv, a_u, out=out[n_s:])
     return out
 
 
@@ -256,18 +286,18 @@ def sample_down(m, x, Z, H, W, skip_grad=None, sh=None, infer=False):
     if _infer_arm(m, sh, infer, x):
         if sh is not None:        # (get_lin: the bf16 image of W_eff where the projection carries adapters)
             return ob.linear(ob.downsample_ln(x, m.norm.weight, m.norm.bias, Z, H, W), sh.get_lin(m.linear))
-        return ops.linear(ops.downsample_ln(x, m.norm.weight, m.norm.bias, Z, H, W), _layers.eff_weight(m.linear))
+        return _resample_proj(m, m.linear, ops.downsample_ln(x, m.norm.weight, m.norm.bias, Z, H, W))
     return DownSampleFn.apply(x, _layers.eff_weight(m.linear), m.norm.weight, m.norm.bias, (Z, H, W), skip_grad, sh,
                               *_layers.lora_args(m.linear))
 
 
 def _up_rows(m, x2, B, Z, H2, W2, H):
-    y = ops.linear(x2, _layers.eff_weight(m.linear1))          # (B*N, 4Co)
+    y = _resample_proj(m, m.linear1, x2)                       # (B*N, 4Co)
     N, Co, Nf = x2.shape[0] // B, y.shape[1] // 4, Z * H * 2 * W2
     out = torch.empty((B * Nf, Co), dtype=torch.float32, device=x2.device)
     for b in range(B):
         g = ops.upsample_ln(y[b * N:(b + 1) * N], m.norm.weight, m.norm.bias, Z, H2, W2, H)
-        ops.linear(g, _layers.eff_weight(m.linear2), out=out[b * Nf:(b + 1) * Nf])
+        _resample_proj(m, m.linear2, g, out=out[b * Nf:(b + 1) * Nf])
     return out
 
 
@@ -309,8 +339,10 @@ def forward_model(model, inp, inp_surface, statistics, maps, const_h, levels_rev
         x = run_layer(model.layers[2], x, H2, W2)
         x = sample_up(model.upsample, x, 8, H2, W2, H4, sh, infer)
         x = run_layer(model.layers[3], x, H4, W4, halves[1])
+        # frozen fp32 inference: the recovery's two products from their padded split images (the Function cannot read grad mode)
+        split = (_resample_image(rec, rec.conv_surface), _resample_image(rec, rec.conv)) if infer and sh is None else None
         res.append(PatchRecoverHalvesFn.apply(skip, x, rec.conv.weight, rec.conv.bias, rec.conv_surface.weight,
-                                              rec.conv_surface.bias, (H4 * W4, LAT, LON), skip_grad, sh))
+                                              rec.conv_surface.bias, (H4 * W4, LAT, LON), skip_grad, sh, split))
     return tuple(_stack(t, B) for t in zip(*res))       # (B = 1: a view, no 286 MB stack copy)
 
 
@@ -361,8 +393,8 @@ def patch_recover(m, x, Z, H, W, LAT=721, LON=1440):
     outs, outs_s = [], []
     for b in range(B):
         xb = _tok2d(x[b:b + 1])
-        y_s = ops.linear(xb[:n_s], m.conv_surface.weight, m.conv_surface.bias)
-        y_u = ops.linear(xb[n_s:], m.conv.weight, m.conv.bias)
+        y_s = _resample_proj(m, m.conv_surface, xb[:n_s])     # (the launches of forward_model's recovery: B = 2 == two B = 1, bit for bit)
+        y_u = _resample_proj(m, m.conv, xb[n_s:])
         o, os_ = ops.patch_recover_scatter(y_u, y_s, LAT, LON)
         outs.append(o)
         outs_s.append(os_)

@@ -265,6 +265,9 @@ def assert_plain_tree(root, what):
 class PatchEmbedding_pretrain(nn.Module):
     """reference layers.py:12-93."""
 
+    # frozen fp32 inference: its projections on the exact-split bf16-MFMA kernel (PanguModel.use_split_projections sets it)
+    split_projections = True
+
     def __init__(self, patch_size, dim):
         super().__init__()
         self.conv = nn.Conv1d(in_channels=192, out_channels=dim, kernel_size=1, stride=1)
@@ -414,6 +417,9 @@ class EarthSpecificLayer(nn.Module):
 class DownSample(nn.Module):
     """reference layers.py:423-459."""
 
+    # frozen fp32 inference: its projections on the exact-split bf16-MFMA kernel (PanguModel.use_split_projections sets it)
+    split_projections = True
+
     def __init__(self, dim):
         super().__init__()
         self.linear = nn.Linear(in_features=4 * dim, out_features=2 * dim, bias=False)
@@ -425,6 +431,9 @@ class DownSample(nn.Module):
 
 class UpSample(nn.Module):
     """reference layers.py:461-499."""
+
+    # frozen fp32 inference: its projections on the exact-split bf16-MFMA kernel (PanguModel.use_split_projections sets it)
+    split_projections = True
 
     def __init__(self, input_dim, output_dim):
         super().__init__()
@@ -443,6 +452,9 @@ class UpSample(nn.Module):
 
 class PatchRecovery_pretrain(nn.Module):
     """reference layers.py:501-545."""
+
+    # frozen fp32 inference: its projections on the exact-split bf16-MFMA kernel (PanguModel.use_split_projections sets it)
+    split_projections = True
 
     def __init__(self, dim):
         super().__init__()

@@ -25,6 +25,22 @@ def image_index(N, K, plane, n, k):
     return (((((nt * (K // BK) + kt) * 3 + plane) * 2 + lh) * BN + nl) * 8) + j
 
 
+def padded_rows(N):
+    """Rows of the column-padded image of an N-row weight (pangu_split_weight_bf16x3_padded): the next multiple of 192."""
+    return -(-N // BN) * BN
+
+
+def served_padded(N, K):
+    return N > 0 and N % 4 == 0 and K % BK == 0
+
+
+def image_index_padded(N, K, plane, n, k):
+    """Index (in bf16 elements) of plane `plane` of row n, column k of the padded image of an (N, K) weight, n in
+    0 .. padded_rows(N) - 1: W[n][k] for n < N, a zero (+0 in every plane) for the rows behind.  It is the image of W extended
+    by zero rows, so the index is image_index at padded_rows(N) rows, and the image has 3 padded_rows(N) K bf16 slots."""
+    return image_index(padded_rows(N), K, plane, n, k)
+
+
 def unpermute(image_u16, N, K):
     """image_u16: the image as a flat sequence of 3 N K bf16 bit patterns -> three row-major lists-of-lists [plane][n][k]."""
     return [[[image_u16[image_index(N, K, p, n, k)] for k in range(K)] for n in range(N)] for p in range(3)]

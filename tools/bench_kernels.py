@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-shape kernel micro-benchmarks on one MI355X (development tool, not the headline bench).
 
-  python tools/bench_kernels.py gemm|attn|attn_f32|rows|mlp_fused|... [--lib-compare]
+  python tools/bench_kernels.py gemm|attn|attn_f32|resample|rows|mlp_fused|... [--lib-compare]
 `--lib-compare` also times torch.matmul (hipBLASLt/rocBLAS) on the same shapes as an external yardstick."""
 import os
 import sys
@@ -259,6 +259,29 @@ def attn_f32():
                       f"{mss:7.3f} ms {fl / mss / 1e9:6.1f} TF/s   | {ms / mss:5.2f}x")
 
 
+RESAMPLE_SHAPES = [  # (M, N, K, bias, name): the projections outside the blocks, once per step each
+    (131040, 384, 768, False, "down"), (131040, 768, 384, False, "up1"), (456120, 160, 384, True, "recover"),
+    (521280, 192, 192, False, "up2"), (456120, 192, 192, True, "embed"), (65160, 192, 112, True, "embed surf"),
+    (65160, 64, 384, True, "recover surf"),
+]
+
+
+def resample():
+    """The fp32 forward's projections outside the blocks under both kernels: fp32 MFMA (ops.linear) and the column-padded
+    exact-split kernel (ops.linear_split(padded=True)); a process prints one sample per shape and kernel."""
+    for M, N, K, bias, name in RESAMPLE_SHAPES:
+        a = torch.randn(M, K, device="cuda")
+        w = torch.randn(N, K, device="cuda") / K ** 0.5
+        b = torch.randn(N, device="cuda") if bias else None
+        out = torch.empty(M, N, device="cuda")
+        image = ops.split_weight_image(w, padded=True)
+        ms = timeit(lambda: ops.linear(a, w, b, out=out))
+        mss = timeit(lambda: ops.linear_split(a, image, N, b, out=out, padded=True))
+        fl = 2.0 * M * N * K
+        print(f"resample {name:12s} M={M:6d} N={N:4d} K={K:4d}: fp32 MFMA {ms * 1e3:7.1f} us {fl / ms / 1e9:6.1f} TF/s   | split "
+              f"{mss * 1e3:7.1f} us {fl / mss / 1e9:6.1f} TF/s   | {ms / mss:5.2f}x")
+
+
 def rows():
     for N, C in ((521280, 192), (131040, 384)):
         y, s = torch.randn(N, C, device="cuda"), torch.randn(N, C, device="cuda")
@@ -279,6 +302,6 @@ def rows():
 
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "gemm"
-    {"gemm": lambda: gemm("--lib-compare" in sys.argv), "attn": attn, "attn_f32": attn_f32, "attn_bwd": attn_bwd, "rows": rows,
+    {"gemm": lambda: gemm("--lib-compare" in sys.argv), "attn": attn, "attn_f32": attn_f32, "attn_bwd": attn_bwd, "rows": rows, "resample": resample,
      "gemm_bf16": lambda: gemm_bf16("--lib-compare" in sys.argv), "attn_bf16": attn_bf16, "gemm_ln_bf16": gemm_ln_bf16, "mlp_fused": mlp_fused, "mlp_train": mlp_train, "attn_qkv_bf16": attn_qkv_bf16, "gemm_ln": gemm_ln,
      "wgrad_bf16": lambda: wgrad(True), "wgrad": lambda: wgrad(False)}[what]()

@@ -12,7 +12,11 @@ model at M = 4096, against the fp64 value of shortcut + s * LN(a W^T + b).
 
   python tools/split_error.py --attn > profiles/attn_f32_split_error.md       (the window-attention core)
 --attn: the cases of tests/test_gpu_attn_split.py (six geometries, unshifted / shifted, and the peaked shifted inputs) at five seeds
-each, fp32-MFMA kernel and exact-split kernel against the oracle evaluated in fp64."""
+each, fp32-MFMA kernel and exact-split kernel against the oracle evaluated in fp64.
+
+  python tools/split_error.py --resample                                      (the projections outside the blocks)
+--resample: down-sampling, the two of up-sampling, patch embedding and patch recovery (upper air and surface) at M = 4096 on the
+column-padded kernel, five seeds each."""
 import os
 import random
 import sys
@@ -175,7 +179,38 @@ def main_attn():
           f"({len(r_l2)} cases).")
 
 
+RESAMPLE = [(4096, 384, 768, False, "down"), (4096, 768, 384, False, "up1"), (4096, 160, 384, True, "recover"),
+            (4096, 192, 192, False, "up2"), (4096, 192, 192, True, "embed"), (4096, 192, 112, True, "embed surf"),
+            (4096, 64, 384, True, "recover surf")]
+
+
+def main_resample():
+    print("# Column-padded exact-split projection at the shapes outside the blocks: error against an fp64 product\n")
+    print("rel-L2 / (max-abs / max) of `pangu_linear_fwd` (fp32 MFMA) and `pangu_linear_fwd_split_padded` on the same fp32 inputs, "
+          "five seeds per shape; ratio = split rel-L2 / fp32 rel-L2.  Made by `tools/split_error.py --resample`.\n")
+    print("| projection | MxNxK | bias | seed | fp32 MFMA | split (padded) | ratio |")
+    print("|---|---|---|---|---|---|---|")
+    worst, worst_abs = 0.0, 0.0
+    for M, N, K, bias, name in RESAMPLE:
+        for seed in range(5):
+            g = torch.Generator(device="cuda").manual_seed(100 * seed + N + K)
+            a = torch.randn((M, K), generator=g, device="cuda")
+            w = torch.randn((N, K), generator=g, device="cuda") / K ** 0.5
+            b = torch.randn((N,), generator=g, device="cuda") if bias else None
+            ref = a.double() @ w.double().t()
+            if bias:
+                ref = ref + b.double()
+            f32 = errors(ops.linear(a, w, b), ref)
+            split = errors(ops.linear_split(a, ops.split_weight_image(w, padded=True), N, b, padded=True), ref)
+            print(f"| {name} | {M}x{N}x{K} | {'yes' if bias else 'no'} | {seed} | {f32[0]:.3e} / {f32[1]:.3e} | {split[0]:.3e} / "
+                  f"{split[1]:.3e} | {split[0] / f32[0]:.3f} |")
+            worst, worst_abs = max(worst, split[0] / f32[0]), max(worst_abs, split[0])
+    print(f"\nWorst ratio {worst:.3f} (required <= 1.5); worst split rel-L2 {worst_abs:.3e} (required < 2e-6).")
+
+
 def main():
+    if "--resample" in sys.argv:
+        return main_resample()
     if "--ln" in sys.argv:
         return main_ln()
     if "--attn" in sys.argv:
