@@ -71,20 +71,16 @@ int pangu_linear_fwd(pangu_stream_t stream, const float* A, int lda, const float
 /* The same product for frozen fp32 inference on the bf16 matrix pipe, bit-for-bit fp32 operands: every fp32 value is the exact
  * sum of three bf16 values (hi, mid, lo), and the six partial products of order >= 2^-16 are accumulated in fp32 (error at the
  * level of pangu_linear_fwd's own: profiles/f32_split_error.md).
- *   pangu_split_weight_bf16x3: W[N,K] fp32 -> `image`, 6 * N * K bytes: the three bf16 planes in the fragment order of the GEMM,
- *     [N/192][K/16][plane][k-half][192 rows][8 bf16].  Once per weight.  N % 192 == 0, K % 16 == 0.
- *   pangu_linear_fwd_split: C = act(A @ W^T + bias) from that image; A / C row-strided fp32, any M, act NONE or GELU.
- *     PANGU_E_SHAPE for N % 192 != 0 or K % 16 != 0 means "not served": call pangu_linear_fwd. */
+ * Both serve N > 0, N % 4 == 0, K % 16 == 0; PANGU_E_SHAPE otherwise means "not served": call pangu_linear_fwd.
+ *   pangu_split_weight_bf16x3: W[N,K] fp32 -> `image`, 6 * rows * K bytes, rows = 192 * ceil(N / 192): the three bf16 planes in
+ *     the fragment order of the GEMM, [rows/192][K/16][plane][k-half][192 rows][8 bf16]; the rows >= N are zero rows (+0 in
+ *     all three planes, never read from W).  Once per weight.
+ *   pangu_linear_fwd_split: C = act(A @ W^T + bias) from that image; A / C row-strided fp32, any M, act NONE or GELU.  It runs
+ *     whole 192-column tiles over the image; where N % 192 != 0 a column guard keeps it from reading bias[N..] and from writing
+ *     a column >= N of C (ldc may exceed N): per element the product on the zero-extended weight, bit for bit. */
 int pangu_split_weight_bf16x3(pangu_stream_t stream, const float* W, int N, int K, void* image);
 int pangu_linear_fwd_split(pangu_stream_t stream, const float* A, int lda, const void* image, const float* bias,
                            float* C, int ldc, int M, int N, int K, int act);
-/* The column-padded form of the two, for any N % 4 == 0 (K % 16 == 0): the image is that of W extended by zero rows to
- * Npad = 192 * ceil(N / 192) rows (6 * Npad * K bytes, a zero row +0 in all three planes), and the GEMM runs whole 192-column
- * tiles over it but neither reads bias[N..] nor writes a column >= N of C (ldc may exceed N) or a row >= M: per element the
- * product of pangu_linear_fwd_split on the zero-extended weight, bit for bit.  PANGU_E_SHAPE for N % 4 != 0 or K % 16 != 0. */
-int pangu_split_weight_bf16x3_padded(pangu_stream_t stream, const float* W, int N, int K, void* image);
-int pangu_linear_fwd_split_padded(pangu_stream_t stream, const float* A, int lda, const void* image, const float* bias,
-                                  float* C, int ldc, int M, int N, int K, int act);
 
 /* Weight/bias gradient of a projection (autograd of the calls above; the training step of reference
  * models/pangu_sample.py:71 `loss.backward()`):

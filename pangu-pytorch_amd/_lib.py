@@ -27,8 +27,6 @@ SIGNATURES = {
     "pangu_linear_fwd": [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "pangu_split_weight_bf16x3": [_P, _P, _I, _I, _P],
     "pangu_linear_fwd_split": [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I],
-    "pangu_split_weight_bf16x3_padded": [_P, _P, _I, _I, _P],
-    "pangu_linear_fwd_split_padded": [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I],
     "pangu_linear_wgrad": [_P, _P, _I, _P, _I, _P, _P, _I, _I, _I],
     "pangu_linear_wgrad_ws": [_P, _P, _I, _P, _I, _P, _P, _I, _I, _I, _P, _c.c_longlong],
     "pangu_lora_wgrad_f32": [_P, _P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _c.c_longlong],

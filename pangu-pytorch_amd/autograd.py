@@ -458,7 +458,7 @@ class PatchRecoverHalvesFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, skip, x, cw, cb, sw, sb, geom, skip_grad=None, sh=None, split=None):
-        # split: frozen fp32 inference only (the caller decides: a forward cannot read grad mode) -- the padded split images
+        # split: frozen fp32 inference only (the caller decides: a forward cannot read grad mode) -- the split images
         # (surface, upper air) of the two conv weights, either None where that launch stays on the fp32-MFMA kernel
         ctx.skip_grad = skip_grad
         ctx.pr = pr = _precision(sh)
@@ -467,9 +467,9 @@ class PatchRecoverHalvesFn(torch.autograd.Function):
         assert skip.stride() == (2 * C, 1) and x.stride() == (2 * C, 1) and x.data_ptr() == skip.data_ptr() + skip.element_size() * C
         cat = torch.as_strided(skip, (N, 2 * C), (2 * C, 1), skip.storage_offset())
         img_s, img_u = split if split is not None and sh is None else (None, None)
-        y_s = ops.linear_split(cat[:n_s], img_s, sw.shape[0], sb, padded=True) if img_s is not None else \
+        y_s = ops.linear_split(cat[:n_s], img_s, sw.shape[0], sb) if img_s is not None else \
             pr.k.linear(cat[:n_s], pr.w(sw), sb, **pr.f32_out)
-        y_u = ops.linear_split(cat[n_s:], img_u, cw.shape[0], cb, padded=True) if img_u is not None else \
+        y_u = ops.linear_split(cat[n_s:], img_u, cw.shape[0], cb) if img_u is not None else \
             pr.k.linear(cat[n_s:], pr.w(cw), cb, **pr.f32_out)
         ctx.save_for_backward(cat, cw, sw)
         ctx.geom = geom

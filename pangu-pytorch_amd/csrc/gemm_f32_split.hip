@@ -31,8 +31,8 @@ using Tile = SplitTile<4, 1, 2, true>;           // 4 x 1 row-owning waves, ring
 constexpr int BM = Tile::BM;                     // 128
 constexpr int BN = Tile::BN;                     // 192 = W_ROWS: one n-tile block of the image per tile
 
-// One thread per (row n, 8 consecutive k): W[N][K] fp32 -> the three planes of the image (layout above; N % 192 == 0, K % 16 == 0).
-// PAD: the image has `rows` >= N rows (a multiple of 192); rows >= N are zero rows, never read from W, +0 in all three planes.
+// One thread per (row n, 8 consecutive k): W[N][K] fp32 -> the three planes of the image (layout above; N % 4 == 0, K % 16 == 0).
+// The image has rows = ceil(N / 192) * 192 rows.  PAD (rows > N): rows >= N are zero rows, never read from W, +0 in all three planes.
 template <bool PAD>
 __global__ __launch_bounds__(256) void split_weight_kernel(const float* __restrict__ W, unsigned char* __restrict__ image, int N,
                                                            int K, int rows) {
@@ -111,23 +111,16 @@ __global__ __launch_bounds__(256, 3) void gemm_f32_split_kernel(const float* __r
 
 }  // namespace
 
+// Rows of the image of an N-row weight: W's N rows and zero rows behind them up to whole 192-row n-tile blocks.
+static long long image_rows(int N) { return ((long long)N + BN - 1) / BN * BN; }
+
 extern "C" int pangu_split_weight_bf16x3(pangu_stream_t stream, const float* W, int N, int K, void* image) {
   if (!W || !image) return PANGU_E_NULL;
-  if (N <= 0 || K <= 0 || (N % BN) != 0 || (K % BK) != 0) return PANGU_E_SHAPE;
-  if ((long long)N * K * 6 >= 0xFFFFFFFFll) return PANGU_E_RANGE;
-  const long long threads = (long long)N * (K / 8);
-  hipLaunchKernelGGL(split_weight_kernel<false>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, W,
-                     reinterpret_cast<unsigned char*>(image), N, K, N);
-  return pangu_launch_status();
-}
-
-extern "C" int pangu_split_weight_bf16x3_padded(pangu_stream_t stream, const float* W, int N, int K, void* image) {
-  if (!W || !image) return PANGU_E_NULL;
   if (N <= 0 || K <= 0 || (N % 4) != 0 || (K % BK) != 0) return PANGU_E_SHAPE;
-  const long long rows = ((long long)N + BN - 1) / BN * BN;
+  const long long rows = image_rows(N);
   if (rows * K * 6 >= 0xFFFFFFFFll) return PANGU_E_RANGE;
-  const long long threads = rows * (K / 8);
-  hipLaunchKernelGGL(split_weight_kernel<true>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, W,
+  const dim3 g((unsigned)((rows * (K / 8) + 255) / 256)), blk(256);
+  hipLaunchKernelGGL(rows == N ? split_weight_kernel<false> : split_weight_kernel<true>, g, blk, 0, (hipStream_t)stream, W,
                      reinterpret_cast<unsigned char*>(image), N, K, (int)rows);
   return pangu_launch_status();
 }
@@ -137,37 +130,17 @@ extern "C" int pangu_linear_fwd_split(pangu_stream_t stream, const float* A, int
   if (!A || !image || !C) return PANGU_E_NULL;
   if (M <= 0 || N <= 0 || K <= 0 || lda < K || ldc < N || (lda & 3) || (ldc & 3)) return PANGU_E_SHAPE;
   if (act != PANGU_ACT_NONE && act != PANGU_ACT_GELU) return PANGU_E_ARG;
-  if ((N % BN) != 0 || (K % BK) != 0) return PANGU_E_SHAPE;      // not served: the caller takes pangu_linear_fwd
-  if (!pangu_fits_u32(M, lda, 4) || !pangu_fits_u32(M, ldc, 4) || (long long)N * K * 6 >= 0xFFFFFFFFll) return PANGU_E_RANGE;
-  const int m_tiles = (M + BM - 1) / BM, n_tiles = N / BN;
-  const dim3 g(((m_tiles + 7) / 8) * 8 * n_tiles), blk(256);
-  hipStream_t s = (hipStream_t)stream;
-  const unsigned char* img = reinterpret_cast<const unsigned char*>(image);
-#define PANGU_SPLIT_LAUNCH(ACT, HB) \
-  hipLaunchKernelGGL((gemm_f32_split_kernel<ACT, HB>), g, blk, 0, s, A, lda, img, bias, C, ldc, M, N, K, m_tiles, n_tiles)
-  if (act == PANGU_ACT_GELU) {
-    if (bias) PANGU_SPLIT_LAUNCH(PANGU_ACT_GELU, true); else PANGU_SPLIT_LAUNCH(PANGU_ACT_GELU, false);
-  } else {
-    if (bias) PANGU_SPLIT_LAUNCH(PANGU_ACT_NONE, true); else PANGU_SPLIT_LAUNCH(PANGU_ACT_NONE, false);
-  }
-#undef PANGU_SPLIT_LAUNCH
-  return pangu_launch_status();
-}
-
-extern "C" int pangu_linear_fwd_split_padded(pangu_stream_t stream, const float* A, int lda, const void* image,
-                                             const float* bias, float* C, int ldc, int M, int N, int K, int act) {
-  if (!A || !image || !C) return PANGU_E_NULL;
-  if (M <= 0 || N <= 0 || K <= 0 || lda < K || ldc < N || (lda & 3) || (ldc & 3)) return PANGU_E_SHAPE;
-  if (act != PANGU_ACT_NONE && act != PANGU_ACT_GELU) return PANGU_E_ARG;
   if ((N % 4) != 0 || (K % BK) != 0) return PANGU_E_SHAPE;       // not served: the caller takes pangu_linear_fwd
-  const long long rows = ((long long)N + BN - 1) / BN * BN;       // rows of the padded image
+  const long long rows = image_rows(N);
   if (!pangu_fits_u32(M, lda, 4) || !pangu_fits_u32(M, ldc, 4) || rows * K * 6 >= 0xFFFFFFFFll) return PANGU_E_RANGE;
   const int m_tiles = (M + BM - 1) / BM, n_tiles = (int)(rows / BN);
   const dim3 g(((m_tiles + 7) / 8) * 8 * n_tiles), blk(256);
   hipStream_t s = (hipStream_t)stream;
   const unsigned char* img = reinterpret_cast<const unsigned char*>(image);
-#define PANGU_SPLIT_LAUNCH(ACT, HB) \
-  hipLaunchKernelGGL((gemm_f32_split_kernel<ACT, HB, true>), g, blk, 0, s, A, lda, img, bias, C, ldc, M, N, K, m_tiles, n_tiles)
+  const bool whole = rows == N;      // whole 192-column tiles: the instantiation without the column guard (same bits either way)
+#define PANGU_SPLIT_LAUNCH(ACT, HB)                                                                                          \
+  hipLaunchKernelGGL((whole ? gemm_f32_split_kernel<ACT, HB, false> : gemm_f32_split_kernel<ACT, HB, true>), g, blk, 0, s, A, \
+                     lda, img, bias, C, ldc, M, N, K, m_tiles, n_tiles)
   if (act == PANGU_ACT_GELU) {
     if (bias) PANGU_SPLIT_LAUNCH(PANGU_ACT_GELU, true); else PANGU_SPLIT_LAUNCH(PANGU_ACT_GELU, false);
   } else {

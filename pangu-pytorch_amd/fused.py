@@ -78,43 +78,53 @@ def mlp(m, x2d):
     return ops.linear(h, _layers.eff_weight(m.linear2), m.linear2.bias)
 
 
-def _plain_proj(blk, lin, x2, act=ops.ACT_NONE):
-    """A block's plain projection (qkv, MLP-up) in frozen fp32 inference: the exact-split bf16-MFMA kernel from the weight's cached
-    split image where the block allows it (PanguModel.use_split_projections) and the shape is served; the fp32-MFMA kernel
-    otherwise.  A LoRA layer's image is that of its W_eff, keyed by the stamps of W, A and B: a model with adapters, the same model
-    merged and (with B = 0) the base model compute the same bits, as they do on the fp32-MFMA kernels."""
+# (N, K) of the projections that stay on the fp32-MFMA kernel although the exact-split kernel serves them.  Keyed by shape alone: a
+# shape is held back in every role (block projection, projection + LayerNorm, resampling / embedding / recovery) or in none.  What
+# decides is speed and the 7-step rollout's step-7 fingerprint error against the reference, which tests/test_gpu_rollout.py bounds
+# by 1e-3 and which moves between 7.5e-4 and 1.5e-3 with rounding detail alone (each split arm is more accurate per launch than
+# the fp32 kernel: profiles/f32_split_ln_per_shape.md).  No block shape is listed: (384, 384) was while the attention core was
+# fp32 MFMA; with everything dispatched step 7 reads 7.46e-4 and the step is the fastest (profiles/attn_f32_split_rollout.md).
+# The two surface launches (M = 65160, under 0.1 ms of the step together) are: patch recovery (64, 384) measured 0.94 - 0.99 x
+# per launch (N = 64 in a 192-column tile triples its matrix work); patch embedding (192, 112) measured 38 -> 25 us, but the
+# headline and the rollout error were taken without it, so it waits until both are re-taken (profiles/f32_split_resampling.md).
+_SPLIT_NOT_DISPATCHED = {(192, 112), (64, 384)}
+
+
+def _split_image_of(owner, lin):
+    """The cached split image of the weight the projection `lin` of `owner` (a block, or the resampling / embedding / recovery
+    module) computes with in frozen fp32 inference, or None where the launch stays on the fp32-MFMA kernel: owner's
+    split_projections flag is off (PanguModel.use_split_projections), the shape is listed in _SPLIT_NOT_DISPATCHED, or the kernel
+    does not serve it (N % 4, K % 16).  A LoRA layer's image is that of its W_eff, keyed by the stamps of W, A and B: a model with
+    adapters, the same model merged and (with B = 0) the base model compute the same bits, as they do on the fp32-MFMA kernels."""
     w = _layers.eff_weight(lin)
-    if getattr(blk, "split_projections", True):
-        image = ops.split_image(lin, w, None if w is lin.weight else ("lora",) + tuple(lin._stamp()))
-        if image is not None:
-            return ops.linear_split(x2, image, w.shape[0], lin.bias, act=act)
-    return ops.linear(x2, w, lin.bias, act=act)
+    N = w.shape[0]
+    if not getattr(owner, "split_projections", True) or (N, w.numel() // N) in _SPLIT_NOT_DISPATCHED:      # Conv1d(k=1): (out, in, 1)
+        return None
+    return ops.split_image(lin, w, None if w is lin.weight else ("lora",) + tuple(lin._stamp()))
 
 
-# (N, K) of the fused projections that stay on the fp32-MFMA kernel although the split kernel serves them.  Empty since the attention
-# core runs as exact-split products too: the 7-step rollout's step-7 fingerprint error against the reference, which
-# tests/test_gpu_rollout.py bounds by 1e-3, moves between 7.5e-4 and 1.5e-3 with rounding detail alone (each arm more accurate per
-# launch than the fp32 kernel: profiles/f32_split_ln_per_shape.md).  It kept the stage-1/2 attention out-projection (384, 384) here
-# while the attention core was fp32 MFMA (8.54e-4 without it, 1.04e-3 with it); over the eight subsets of that shape and the two
-# attention stages (profiles/attn_f32_split_rollout.md) the one with everything dispatched reads 7.46e-4 and is the fastest.
-_LN_SPLIT_NOT_DISPATCHED = set()
+def _plain_proj(blk, lin, x2, act=ops.ACT_NONE):
+    """A block's plain projection (qkv, MLP-up) in frozen fp32 inference: the exact-split bf16-MFMA kernel from the weight's image
+    (_split_image_of), the fp32-MFMA kernel otherwise."""
+    image = _split_image_of(blk, lin)
+    if image is not None:
+        return ops.linear_split(x2, image, lin.weight.shape[0], lin.bias, act=act)
+    return ops.linear(x2, _layers.eff_weight(lin), lin.bias, act=act)
 
 
 def _ln_proj(blk, lin, x2, shortcut, norm, out=None, branch_scale=1.0):
     """A block's fused projection (attention out-projection, MLP-down) + LayerNorm + residual in frozen fp32 inference, C = 192 /
-    384: like _plain_proj the exact-split kernel from the cached image of the weight (of W_eff for a LoRA layer) where the block
-    allows it, the fp32-MFMA kernel otherwise."""
-    w = _layers.eff_weight(lin)
-    if getattr(blk, "split_projections", True) and tuple(w.shape) not in _LN_SPLIT_NOT_DISPATCHED:
-        image = ops.split_image(lin, w, None if w is lin.weight else ("lora",) + tuple(lin._stamp()))
-        if image is not None:
-            return ops.linear_ln_residual_split(x2, image, w.shape[0], lin.bias, shortcut, norm.weight, norm.bias, out=out,
-                                                branch_scale=branch_scale)
-    return ops.linear_ln_residual(x2, w, lin.bias, shortcut, norm.weight, norm.bias, out=out, branch_scale=branch_scale)
+    384: like _plain_proj the exact-split kernel from the weight's image, the fp32-MFMA kernel otherwise."""
+    image = _split_image_of(blk, lin)
+    if image is not None:
+        return ops.linear_ln_residual_split(x2, image, lin.weight.shape[0], lin.bias, shortcut, norm.weight, norm.bias, out=out,
+                                            branch_scale=branch_scale)
+    return ops.linear_ln_residual(x2, _layers.eff_weight(lin), lin.bias, shortcut, norm.weight, norm.bias, out=out,
+                                  branch_scale=branch_scale)
 
 
 # C of the blocks whose attention core stays on the fp32-MFMA kernel (csrc/attn_f32.hip) although the exact-split kernel
-# (csrc/attn_f32_split.hip) serves them: same form and same reason as _LN_SPLIT_NOT_DISPATCHED; empty for the same measurement
+# (csrc/attn_f32_split.hip) serves them: same form and same reason as _SPLIT_NOT_DISPATCHED; empty for the same measurement
 # (profiles/attn_f32_split_rollout.md: with attention split at C = 384 only, step 7 reads 1.11e-3).
 _ATTN_SPLIT_NOT_DISPATCHED = set()
 
@@ -231,33 +241,12 @@ def sample_block(blk, x, Z, H, W, roll, out=None, sh=None, infer=False):
         *_layers.lora_args(blk.linear.linear1, blk.linear.linear2, att.linear1, att.linear2))
 
 
-# (N, K) of the projections outside the blocks (down/up-sampling, patch embedding, patch recovery) that stay on the fp32-MFMA
-# kernel although the column-padded split kernel serves them: same form as _LN_SPLIT_NOT_DISPATCHED.  The two surface launches
-# (M = 65160), under 0.1 ms of the step together: patch recovery (64, 384) measured 0.94 - 0.99 x per launch (N = 64 padded to a
-# 192-column tile triples its matrix work); patch embedding (192, 112) measured 38 -> 25 us per launch, but the headline and the
-# 7-step rollout's step-7 error (6.76e-4 of the 1e-3 that tests/test_gpu_rollout.py allows, and it moves with any rounding detail)
-# were taken without it, so it stays here until both are re-taken with it (profiles/f32_split_resampling.md).
-_RESAMPLE_SPLIT_NOT_DISPATCHED = {(192, 112), (64, 384)}
-
-
-def _resample_image(m, lin):
-    """The padded split image of the projection `lin` of the resampling / embedding / recovery module `m` in frozen fp32
-    inference, or None where the launch stays on the fp32-MFMA kernel: the module's split_projections flag is off
-    (PanguModel.use_split_projections), the shape is listed in _RESAMPLE_SPLIT_NOT_DISPATCHED, or the kernel does not serve it
-    (N % 4, K % 16).  Cached and keyed like _plain_proj's: a LoRA layer's image is that of its W_eff."""
-    w = _layers.eff_weight(lin)
-    w2 = w.reshape(w.shape[0], -1)              # Conv1d(k=1) weights are (out, in, 1)
-    if not getattr(m, "split_projections", True) or tuple(w2.shape) in _RESAMPLE_SPLIT_NOT_DISPATCHED:
-        return None
-    return ops.split_image(lin, w, None if w is lin.weight else ("lora",) + tuple(lin._stamp()), padded=True)
-
-
 def _resample_proj(m, lin, x2, out=None):
-    """A projection outside the blocks in frozen fp32 inference: the exact-split kernel from the cached padded image
-    (_resample_image), the fp32-MFMA kernel otherwise.  x2 / out may be row-strided."""
-    image = _resample_image(m, lin)
+    """A projection outside the blocks (down/up-sampling, patch embedding, patch recovery) in frozen fp32 inference: like
+    _plain_proj the exact-split kernel from the weight's image, the fp32-MFMA kernel otherwise.  x2 / out may be row-strided."""
+    image = _split_image_of(m, lin)
     if image is not None:
-        return ops.linear_split(x2, image, lin.weight.shape[0], lin.bias, out=out, padded=True)
+        return ops.linear_split(x2, image, lin.weight.shape[0], lin.bias, out=out)
     return ops.linear(x2, _layers.eff_weight(lin), lin.bias, out=out)
 
 
@@ -339,8 +328,8 @@ def forward_model(model, inp, inp_surface, statistics, maps, const_h, levels_rev
         x = run_layer(model.layers[2], x, H2, W2)
         x = sample_up(model.upsample, x, 8, H2, W2, H4, sh, infer)
         x = run_layer(model.layers[3], x, H4, W4, halves[1])
-        # frozen fp32 inference: the recovery's two products from their padded split images (the Function cannot read grad mode)
-        split = (_resample_image(rec, rec.conv_surface), _resample_image(rec, rec.conv)) if infer and sh is None else None
+        # frozen fp32 inference: the recovery's two products from their split images (the Function cannot read grad mode)
+        split = (_split_image_of(rec, rec.conv_surface), _split_image_of(rec, rec.conv)) if infer and sh is None else None
         res.append(PatchRecoverHalvesFn.apply(skip, x, rec.conv.weight, rec.conv.bias, rec.conv_surface.weight,
                                               rec.conv_surface.bias, (H4 * W4, LAT, LON), skip_grad, sh, split))
     return tuple(_stack(t, B) for t in zip(*res))       # (B = 1: a view, no 286 MB stack copy)

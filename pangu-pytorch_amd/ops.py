@@ -365,55 +365,44 @@ def linear(a, weight, bias=None, act=ACT_NONE, out=None, aux=None):
 
 
 def split_served(N, K):
-    """The shapes pangu_linear_fwd_split serves (its 192-column tile, 16-wide k-steps)."""
-    return N % 192 == 0 and K % 16 == 0
-
-
-def split_served_padded(N, K):
-    """The shapes pangu_linear_fwd_split_padded serves: whole 16-byte column segments, 16-wide k-steps."""
+    """The shapes the exact-split kernels serve: whole 16-byte column segments, 16-wide k-steps (split_layout.served)."""
     return N > 0 and N % 4 == 0 and K % 16 == 0
 
 
-def split_padded_rows(N):
-    """Rows of the padded image of an N-row weight: the next multiple of the 192-column tile (split_layout.padded_rows)."""
+def split_image_rows(N):
+    """Rows of the image of an N-row weight: the next multiple of the 192-column tile (split_layout.image_rows)."""
     return -(-N // 192) * 192
 
 
-def split_weight_image(weight, padded=False):
-    """The exact bf16 hi/mid/lo image of an fp32 weight (N, K) in the fragment order of `linear_split` (uint8, 6 N K bytes:
-    [N/192][K/16][plane][k-half][192 rows][8 bf16]; split_layout.image_index states it), or None for a shape the kernel does not
-    serve.  padded=True: any N % 4 == 0 is served, by the image of W extended with zero rows to split_padded_rows(N) rows
-    (6 Npad K bytes, split_layout.image_index_padded; the same bytes as the plain image where N % 192 == 0), which is what
-    `linear_split(.., padded=True)` reads.  Made once per weight: callers cache it under `param_stamp(weight)` (split_image)."""
+def split_weight_image(weight):
+    """The exact bf16 hi/mid/lo image of an fp32 weight (N, K) in the fragment order of `linear_split` (uint8, 6 rows K bytes,
+    rows = split_image_rows(N): [rows/192][K/16][plane][k-half][192 rows][8 bf16], the rows behind N zero; split_layout.image_index
+    states it), or None for a shape the kernel does not serve.  Made once per weight: callers cache it under
+    `param_stamp(weight)` (split_image)."""
     w2 = weight.detach().reshape(weight.shape[0], -1)
     N, K = w2.shape
-    rows = split_padded_rows(N) if padded else N
-    if not (split_served_padded(N, K) if padded else split_served(N, K)) or 6 * rows * K >= _U32_BYTES:
+    if not split_served(N, K) or 6 * split_image_rows(N) * K >= _U32_BYTES:
         return None
-    image = torch.empty((6 * rows * K,), dtype=torch.uint8, device=w2.device)
-    fn = _lib.load().pangu_split_weight_bf16x3_padded if padded else _lib.load().pangu_split_weight_bf16x3
-    _lib.check(fn(_stream(w2), _chk(w2, "split.weight"), N, K, image.data_ptr()), "split_weight")
+    image = torch.empty((6 * split_image_rows(N) * K,), dtype=torch.uint8, device=w2.device)
+    _lib.check(_lib.load().pangu_split_weight_bf16x3(_stream(w2), _chk(w2, "split.weight"), N, K, image.data_ptr()), "split_weight")
     return image
 
 
-_split_images = weakref.WeakKeyDictionary()      # projection module -> (param_stamp of its weight, padded, image or None)
+_split_images = weakref.WeakKeyDictionary()      # projection module -> (param_stamp of its weight, image or None)
 
 
-def split_image(lin, weight, stamp=None, padded=False):
+def split_image(lin, weight, stamp=None):
     """The image of `weight`, the weight the projection module `lin` computes with, cached per module under `stamp` (a stale stamp
     rebuilds it); None when the shape is not served.  stamp: what identifies the weight's content -- by default the stamp of the
-    parameter `weight`; for a derived weight (a LoRA layer's W_eff) the stamp of what it was derived from.  padded: the
-    column-padded image (split_weight_image), asked for explicitly by the callers that launch the padded kernel; a module is
-    read in one form only, the cache entry records which.  The cache holds the modules weakly and lives here, not on the module:
-    pickling or deep-copying a model never carries the images."""
+    parameter `weight`; for a derived weight (a LoRA layer's W_eff) the stamp of what it was derived from.  The cache holds the
+    modules weakly and lives here, not on the module: pickling or deep-copying a model never carries the images."""
     if stamp is None:
         stamp = param_stamp(weight)
-    padded = bool(padded)
     hit = _split_images.get(lin)
-    if hit is None or hit[0] != stamp or hit[1] != padded:
+    if hit is None or hit[0] != stamp:
         require_epoch_hook()
-        hit = _split_images[lin] = (stamp, padded, split_weight_image(weight, padded))
-    return hit[2]
+        hit = _split_images[lin] = (stamp, split_weight_image(weight))
+    return hit[1]
 
 
 def drop_split_images(modules):
@@ -422,21 +411,20 @@ def drop_split_images(modules):
         _split_images.pop(m, None)
 
 
-def _check_split_image(what, image, N, K, padded=False):
-    rows, ok = (split_padded_rows(N), split_served_padded(N, K)) if padded else (N, split_served(N, K))
-    if image.dtype != torch.uint8 or image.numel() != 6 * rows * K or not image.is_cuda or not ok:
+def _check_split_image(what, image, N, K):
+    if image.dtype != torch.uint8 or image.numel() != 6 * split_image_rows(N) * K or not image.is_cuda or not split_served(N, K):
         raise RuntimeError(f"{what}: image of {image.numel()} bytes does not belong to a served ({N}, {K}) weight")
 
 
-def linear_split(a, image, N, bias=None, act=ACT_NONE, out=None, padded=False):
+def linear_split(a, image, N, bias=None, act=ACT_NONE, out=None):
     """out[M,N] = act(a[M,K] @ W[N,K]^T + bias) from W's split image (split_weight_image): fp32 in and out, the product on the
-    bf16 matrix pipe as six exact-split partial products.  `a`/`out` may be row-strided views; act NONE or GELU.  padded=True:
-    `image` is the padded image of an N % 4 == 0 weight; the kernel runs whole 192-column tiles over it and writes columns
-    0 .. N-1 only (`out` may be a column slice of a wider buffer)."""
+    bf16 matrix pipe as six exact-split partial products.  `a`/`out` may be row-strided views; act NONE or GELU.  The kernel
+    runs whole 192-column tiles over the image and writes columns 0 .. N-1 only (`out` may be a column slice of a wider
+    buffer)."""
     lib = _lib.load()
     ap, lda = _rows(a, "linear_split.a")
     M, K = a.shape
-    _check_split_image("linear_split", image, N, K, padded)
+    _check_split_image("linear_split", image, N, K)
     bp = _chk(bias, "linear_split.bias") if bias is not None else None
     if out is None:
         out = torch.empty((M, N), dtype=torch.float32, device=a.device)
@@ -444,62 +432,51 @@ def linear_split(a, image, N, bias=None, act=ACT_NONE, out=None, padded=False):
     chunks = _row_chunks(M, 4 * lda, 4 * ldc)
     if chunks is not None:
         for m0, m1 in chunks:
-            linear_split(a[m0:m1], image, N, bias, act, out[m0:m1], padded)
+            linear_split(a[m0:m1], image, N, bias, act, out[m0:m1])
         return out
-    fn = lib.pangu_linear_fwd_split_padded if padded else lib.pangu_linear_fwd_split
     with _timed("linear", 2.0 * M * N * K):
-        _lib.check(fn(_stream(a), ap, lda, image.data_ptr(), bp, op, ldc, M, N, K, act), "linear_fwd_split")
+        _lib.check(lib.pangu_linear_fwd_split(_stream(a), ap, lda, image.data_ptr(), bp, op, ldc, M, N, K, act), "linear_fwd_split")
+    return out
+
+
+def _linear_ln(split, a, w, N, bias, shortcut, gamma, beta, out, branch_scale):
+    """The body of linear_ln_residual (w: the fp32 weight) and of linear_ln_residual_split (split: w is the weight's image)."""
+    what, tag = ("linear_ln_residual_split", "linear_ln_split") if split else ("linear_ln_residual", "linear_ln")
+    lib = _lib.load()
+    ap, lda = _rows(a, tag + ".a")
+    M, K = a.shape
+    if split:
+        _check_split_image(what, w, N, K)
+    if (not split and w.shape[1] != K) or tuple(shortcut.shape) != (M, N):
+        raise RuntimeError(f"{what}: a {tuple(a.shape)} weight {(N, K) if split else tuple(w.shape)} shortcut {tuple(shortcut.shape)}")
+    sp, lds = _rows(shortcut, tag + ".shortcut")
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=a.device)
+    op, ldo = _rows(out, tag + ".out")
+    chunks = _row_chunks(M, 4 * lda, 4 * ldo, 4 * lds)
+    if chunks is not None:
+        for m0, m1 in chunks:
+            _linear_ln(split, a[m0:m1], w, N, bias, shortcut[m0:m1], gamma, beta, out[m0:m1], branch_scale)
+        return out
+    fn, entry = (lib.pangu_linear_ln_residual_fwd_split, "linear_ln_residual_fwd_split") if split else \
+        (lib.pangu_linear_ln_residual_fwd, "linear_ln_residual_fwd")
+    # one bucket for both, and its own: not the plain GEMM kernel of bench.py's roofline, which keeps counting the split launches
+    with _timed("linear_ln", 2.0 * M * N * K):
+        _lib.check(fn(_stream(a), ap, lda, w.data_ptr() if split else _chk(w, tag + ".weight"),
+                      _chk(bias, tag + ".bias") if bias is not None else None, sp, lds, _chk(gamma, "gamma"), _chk(beta, "beta"),
+                      op, ldo, M, N, K, float(branch_scale)), entry)
     return out
 
 
 def linear_ln_residual(a, weight, bias, shortcut, gamma, beta, out=None, branch_scale=1.0):
     """out = shortcut + branch_scale * (LayerNorm(a @ weight^T + bias) * gamma + beta) in ONE launch (N = 192; inference)."""
-    lib = _lib.load()
-    ap, lda = _rows(a, "linear_ln.a")
-    M, K = a.shape
-    N = weight.shape[0]
-    if weight.shape[1] != K or tuple(shortcut.shape) != (M, N):
-        raise RuntimeError(f"linear_ln_residual: a {tuple(a.shape)} weight {tuple(weight.shape)} shortcut {tuple(shortcut.shape)}")
-    sp, lds = _rows(shortcut, "linear_ln.shortcut")
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.float32, device=a.device)
-    op, ldo = _rows(out, "linear_ln.out")
-    chunks = _row_chunks(M, 4 * lda, 4 * ldo, 4 * lds)
-    if chunks is not None:
-        for m0, m1 in chunks:
-            linear_ln_residual(a[m0:m1], weight, bias, shortcut[m0:m1], gamma, beta, out[m0:m1], branch_scale)
-        return out
-    with _timed("linear_ln", 2.0 * M * N * K):      # its own bucket: not the plain GEMM kernel of bench.py's roofline
-        _lib.check(lib.pangu_linear_ln_residual_fwd(
-            _stream(a), ap, lda, _chk(weight, "linear_ln.weight"), _chk(bias, "linear_ln.bias") if bias is not None else None,
-            sp, lds, _chk(gamma, "gamma"), _chk(beta, "beta"), op, ldo, M, N, K, float(branch_scale)), "linear_ln_residual_fwd")
-    return out
+    return _linear_ln(False, a, weight, weight.shape[0], bias, shortcut, gamma, beta, out, branch_scale)
 
 
 def linear_ln_residual_split(a, image, N, bias, shortcut, gamma, beta, out=None, branch_scale=1.0):
     """`linear_ln_residual` from W's split image (split_weight_image): the product on the bf16 matrix pipe as six exact-split
     partial products, the LayerNorm / residual epilogue of the fp32 kernel operation for operation (N = 192 or 384; inference)."""
-    lib = _lib.load()
-    ap, lda = _rows(a, "linear_ln_split.a")
-    M, K = a.shape
-    _check_split_image("linear_ln_residual_split", image, N, K)
-    if tuple(shortcut.shape) != (M, N):
-        raise RuntimeError(f"linear_ln_residual_split: a {tuple(a.shape)} weight ({N}, {K}) shortcut {tuple(shortcut.shape)}")
-    sp, lds = _rows(shortcut, "linear_ln_split.shortcut")
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.float32, device=a.device)
-    op, ldo = _rows(out, "linear_ln_split.out")
-    chunks = _row_chunks(M, 4 * lda, 4 * ldo, 4 * lds)
-    if chunks is not None:
-        for m0, m1 in chunks:
-            linear_ln_residual_split(a[m0:m1], image, N, bias, shortcut[m0:m1], gamma, beta, out[m0:m1], branch_scale)
-        return out
-    with _timed("linear_ln", 2.0 * M * N * K):      # the bucket of linear_ln_residual: bench.py's roofline keeps counting these
-        _lib.check(lib.pangu_linear_ln_residual_fwd_split(
-            _stream(a), ap, lda, image.data_ptr(), _chk(bias, "linear_ln_split.bias") if bias is not None else None,
-            sp, lds, _chk(gamma, "gamma"), _chk(beta, "beta"), op, ldo, M, N, K, float(branch_scale)),
-            "linear_ln_residual_fwd_split")
-    return out
+    return _linear_ln(True, a, image, N, bias, shortcut, gamma, beta, out, branch_scale)
 
 
 _WGRAD_WS_BYTES = 96 << 20

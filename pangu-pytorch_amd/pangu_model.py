@@ -134,11 +134,10 @@ class PanguModel(nn.Module):
         level of the fp32-MFMA kernels' own.  The per-weight images are made once and cached under the
         weight's stamp: 6 bytes per weight element, about 140 MB for the whole model (80 MB of it the plain projections'); the
         attention core needs no image (q, k, v and the probabilities are split inside the kernel).  The projections outside the
-        blocks -- down-sampling, the two of up-sampling, patch embedding and patch recovery -- run the same kernel in its
-        column-padded form (pangu_linear_fwd_split_padded: patch recovery has N = 160, served by a 192-row image whose last
-        rows are zero and an epilogue that writes 160 columns).  Shapes listed in fused._LN_SPLIT_NOT_DISPATCHED /
-        fused._ATTN_SPLIT_NOT_DISPATCHED (both empty) and fused._RESAMPLE_SPLIT_NOT_DISPATCHED (the two small surface launches)
-        stay on the fp32-MFMA kernels.  This is the default; `use_split_projections(False)` selects the fp32-MFMA kernels
+        blocks -- down-sampling, the two of up-sampling, patch embedding and patch recovery -- run the same plain kernel
+        (patch recovery has N = 160, served by a 192-row image whose last rows are zero and an epilogue that writes 160
+        columns).  Shapes listed in fused._SPLIT_NOT_DISPATCHED (the two small surface launches) and C listed in
+        fused._ATTN_SPLIT_NOT_DISPATCHED (empty) stay on the fp32-MFMA kernels.  This is the default; `use_split_projections(False)` selects the fp32-MFMA kernels
         throughout and drops the images.  LoRA layers compute on the image of their merged weight; training and the bf16 path
         never take the split kernels."""
         for m in self.modules():

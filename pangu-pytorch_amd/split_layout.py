@@ -3,7 +3,10 @@ csrc/split_f32.h, its fp32 A part that of csrc/gemm_f32_dma_loop.h), stated in p
 pangu_split_weight_bf16x3, and the LDS stage the kernel reads its MFMA fragments from, under both wave tilings of the loop: 2 x 2
 waves of 64 x 96 (a_fragment_address, w_fragment_address: gemm_ln_f32_split.hip at N = 192) and row-owning waves of 32 x 192
 (a_row_fragment_address, w_row_fragment_address: gemm_f32_split.hip, gemm_ln_f32_split.hip at N = 384 from K = 1536).  No torch, no GPU: the
-tests un-permute an image and check the bank behaviour of the fragment reads with these."""
+tests un-permute an image and check the bank behaviour of the fragment reads with these.
+
+The image of an (N, K) weight (N % 4 == 0, K % 16 == 0) has image_rows(N) rows, whole 192-row n-tile blocks: W's N rows, and behind
+them zero rows (+0 in every plane)."""
 
 BM, BN, BK = 128, 192, 16
 A_BYTES = BM * 64                 # the fp32 A image of a stage: 128 rows of 64 B (16 floats), 16-B chunks XOR-swizzled
@@ -15,34 +18,24 @@ _F = (0, 2, 3, 1)
 
 
 def served(N, K):
-    return N % BN == 0 and K % BK == 0
+    return N > 0 and N % 4 == 0 and K % BK == 0
+
+
+def image_rows(N):
+    """Rows of the image of an N-row weight: the next multiple of 192."""
+    return -(-N // BN) * BN
 
 
 def image_index(N, K, plane, n, k):
-    """Index (in bf16 elements) of plane `plane` (0 hi, 1 mid, 2 lo) of W[n][k] in the image of an (N, K) weight:
-    [n // 192][k // 16][plane][(k // 8) & 1][n % 192][k % 8]."""
+    """Index (in bf16 elements) of plane `plane` (0 hi, 1 mid, 2 lo) of row n, column k of the image of an (N, K) weight, n in
+    0 .. image_rows(N) - 1: [n // 192][k // 16][plane][(k // 8) & 1][n % 192][k % 8]."""
     nt, nl, kt, lh, j = n // BN, n % BN, k // BK, (k // 8) & 1, k % 8
     return (((((nt * (K // BK) + kt) * 3 + plane) * 2 + lh) * BN + nl) * 8) + j
 
 
-def padded_rows(N):
-    """Rows of the column-padded image of an N-row weight (pangu_split_weight_bf16x3_padded): the next multiple of 192."""
-    return -(-N // BN) * BN
-
-
-def served_padded(N, K):
-    return N > 0 and N % 4 == 0 and K % BK == 0
-
-
-def image_index_padded(N, K, plane, n, k):
-    """Index (in bf16 elements) of plane `plane` of row n, column k of the padded image of an (N, K) weight, n in
-    0 .. padded_rows(N) - 1: W[n][k] for n < N, a zero (+0 in every plane) for the rows behind.  It is the image of W extended
-    by zero rows, so the index is image_index at padded_rows(N) rows, and the image has 3 padded_rows(N) K bf16 slots."""
-    return image_index(padded_rows(N), K, plane, n, k)
-
-
 def unpermute(image_u16, N, K):
-    """image_u16: the image as a flat sequence of 3 N K bf16 bit patterns -> three row-major lists-of-lists [plane][n][k]."""
+    """image_u16: the image as a flat sequence of 3 image_rows(N) K bf16 bit patterns -> W's rows as three row-major
+    lists-of-lists [plane][n][k]."""
     return [[[image_u16[image_index(N, K, p, n, k)] for k in range(K)] for n in range(N)] for p in range(3)]
 
 

@@ -167,7 +167,7 @@ def test_wide_dynamic_range(P, M, N, K):
     _check(P, p, True, 1.0, f"wide M{M} N{N} K{K}")
 
 
-def test_dispatch(P):
+def test_dispatch(P, monkeypatch):
     """What a block's fused projection does (fused._ln_proj): the switch off gives ops.linear_ln_residual's bits; a served layer
     takes the split op from the cached image; a weight edited in place gets a new image; a LoRA layer computes on the image of its
     merged weight; use_split_projections(False) on a model drops the images and selects the fp32 kernels."""
@@ -189,13 +189,18 @@ def test_dispatch(P):
         assert not torch.equal(y, f32(lin.weight, lin.bias, branch_scale=0.5))
         out = torch.zeros_like(sc)
         assert P.fused._ln_proj(on, lin, x, sc, norm, out=out, branch_scale=0.5) is out and torch.equal(out, y)
-        # a shape fused.py keeps on the fp32-MFMA kernel (its comment says why) gets no image
-        for N_, K_ in P.fused._LN_SPLIT_NOT_DISPATCHED:
-            lin_nd, x_nd, sc_nd = torch.nn.Linear(K_, N_, device="cuda"), torch.randn(130, K_, device="cuda"), torch.randn(130, N_, device="cuda")
-            norm_nd = torch.nn.LayerNorm(N_, device="cuda")
-            assert torch.equal(P.fused._ln_proj(on, lin_nd, x_nd, sc_nd, norm_nd),
-                               P.ops.linear_ln_residual(x_nd, lin_nd.weight, lin_nd.bias, sc_nd, norm_nd.weight, norm_nd.bias))
+        # a shape fused.py keeps on the fp32-MFMA kernel gets no image; taken off the list it takes the split op
+        lin_nd, x_nd, sc_nd = torch.nn.Linear(192, 192, device="cuda"), torch.randn(130, 192, device="cuda"), torch.randn(130, 192, device="cuda")
+        with monkeypatch.context() as mp:
+            mp.setattr(P.fused, "_SPLIT_NOT_DISPATCHED", {(192, 192)})
+            assert torch.equal(P.fused._ln_proj(on, lin_nd, x_nd, sc_nd, norm),
+                               P.ops.linear_ln_residual(x_nd, lin_nd.weight, lin_nd.bias, sc_nd, norm.weight, norm.bias))
             assert lin_nd not in P.ops._split_images
+        assert (192, 192) not in P.fused._SPLIT_NOT_DISPATCHED
+        assert torch.equal(P.fused._ln_proj(on, lin_nd, x_nd, sc_nd, norm),
+                           P.ops.linear_ln_residual_split(x_nd, P.ops.split_weight_image(lin_nd.weight), 192, lin_nd.bias, sc_nd,
+                                                          norm.weight, norm.bias))
+        assert lin_nd in P.ops._split_images
         # LoRA: B = 0 gives the base layer's bits; after an adapter update the bits of the image of W_eff
         lora = P.layers.LoraLinear.from_linear(lin, 4, 4)
         assert torch.equal(P.fused._ln_proj(on, lora, x, sc, norm), P.fused._ln_proj(on, lin, x, sc, norm))
@@ -245,7 +250,7 @@ def test_one_block_on_vs_off(P, golden_dir, C):
         assert blk.split_projections
         y_split = blk(x, st["Z"], st["H"], 24, roll)
         assert blk.linear.linear2 in P.ops._split_images
-        assert (blk.attention.linear2 in P.ops._split_images) == ((C, C) not in P.fused._LN_SPLIT_NOT_DISPATCHED)
+        assert (blk.attention.linear2 in P.ops._split_images) == ((C, C) not in P.fused._SPLIT_NOT_DISPATCHED)
         blk.split_projections = False
         y_f32 = blk(x, st["Z"], st["H"], 24, roll)
     diff = ((y_split - y_f32).abs().max() / y_f32.abs().max()).item()

@@ -146,17 +146,24 @@ def test_non_finite_rows(P):
 
 
 def test_fallback_and_image_cache(P):
-    """What a block's plain projection does (fused._plain_proj): an unserved shape (no image) and a switched-off block give
-    ops.linear's result bit for bit; a served weight takes the split kernel, a LoRA layer on the image of its merged weight; a
+    """What a block's plain projection does (fused._plain_proj): an unserved shape (N % 4, K % 16: no image) goes to ops.linear,
+    a switched-off block gives ops.linear's result bit for bit; a served weight takes the split kernel, a LoRA layer on the image of its merged weight; a
     weight edited in place (`copy_` under no_grad) gets a new image, observed through param_stamp.  K = 112 (a K padded to 16s)
     is served."""
     torch.manual_seed(4)
     on, off = types.SimpleNamespace(split_projections=True), types.SimpleNamespace(split_projections=False)
     x = torch.randn(300, 384, device="cuda")
-    lin160 = torch.nn.Linear(384, 160, device="cuda")
-    assert P.ops.split_image(lin160, lin160.weight) is None
     with torch.no_grad():
-        assert torch.equal(P.fused._plain_proj(on, lin160, x), P.ops.linear(x, lin160.weight, lin160.bias))
+        for unserved, xu in ((torch.nn.Linear(384, 162, device="cuda"), x),                     # N % 4 != 0
+                             (torch.nn.Linear(24, 192, device="cuda"), x[:, :24])):             # K % 16 != 0
+            assert P.ops.split_image(unserved, unserved.weight) is None
+            # the split kernels serve every shape the fp32-MFMA kernel serves, so what _plain_proj falls back to is ops.linear's
+            # own refusal of the shape: the same error, nothing else tried
+            with pytest.raises(RuntimeError, match="linear_fwd failed") as want:
+                P.ops.linear(xu, unserved.weight, unserved.bias)
+            with pytest.raises(RuntimeError) as got:
+                P.fused._plain_proj(on, unserved, xu)
+            assert str(got.value) == str(want.value)
         lin = torch.nn.Linear(384, 192, device="cuda")
         assert torch.equal(P.fused._plain_proj(off, lin, x), P.ops.linear(x, lin.weight, lin.bias))
         # a LoRA layer computes on the image of its merged weight W_eff: with B = 0 the base layer's bits, and after an adapter
@@ -184,6 +191,27 @@ def test_fallback_and_image_cache(P):
         lin112 = torch.nn.Linear(112, 192, device="cuda")
         assert P.ops.split_image(lin112, lin112.weight) is not None
         _check(P, torch.randn(650, 112, device="cuda"), lin112.weight.detach(), lin112.bias.detach(), 0, "K112")
+
+
+@pytest.mark.parametrize("N", [192, 384])
+def test_whole_tiles_keep_their_image_and_bits(P, N):
+    """N % 192 == 0 has no rows behind N (6 N K bytes) and the bits recorded for tests/test_gpu_split_fingerprint.py, on that
+    list's inputs: the one entry serves these shapes with the kernel that has no column guard."""
+    import json
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(root, "tools"))
+    import gemm_f32_fingerprint as F
+    with open(os.path.join(root, "profiles", "gemm_f32_shared_loops_fingerprint_new.json")) as f:
+        want = json.load(f)
+    M, K = 129, 48
+    a, w, b = F.t("a", M, K), F.t("w", N, K, scale=K ** -0.5), F.t("b", N)
+    image = P.ops.split_weight_image(w)
+    assert image.dtype == torch.uint8 and image.numel() == 6 * N * K == 6 * P.ops.split_image_rows(N) * K
+    for act in (P.ops.ACT_NONE, P.ops.ACT_GELU):
+        for bias in (b, None):
+            key = f"linear_split M={M} N={N} K={K} {F.ACT_NAMES[act]} bias={int(bias is not None)}"
+            assert F.digest(P.ops.linear_split(a, image, N, bias, act=act)) == want[key], key
 
 
 def test_one_block_split_against_fp32_kernels(P, golden_dir):

@@ -1,5 +1,5 @@
 """The projections outside the blocks in frozen fp32 inference -- down-sampling, the two of up-sampling, patch embedding, patch
-recovery -- on the column-padded exact-split kernel (fused._resample_proj, PatchRecoverHalvesFn's `split`) under the modules'
+recovery -- on the exact-split kernel (fused._resample_proj, PatchRecoverHalvesFn's `split`) under the modules'
 split_projections flag.  Needs an MI355X: run with `-m gpu`.
 
 Geometry LAT = 25, LON = 48: H4 = 7, W4 = 12 (672 stage-0 tokens: five 128-row tiles and a 32-row remainder), H2 = 4, W2 = 6 (the
@@ -120,13 +120,13 @@ def test_patch_recovery(P, net):
     n_s = H4 * W4
 
     def run():
-        split = (P.fused._resample_image(rec, rec.conv_surface), P.fused._resample_image(rec, rec.conv))
+        split = (P.fused._split_image_of(rec, rec.conv_surface), P.fused._split_image_of(rec, rec.conv))
         return PatchRecoverHalvesFn.apply(halves[0], halves[1], rec.conv.weight, rec.conv.bias, rec.conv_surface.weight,
                                           rec.conv_surface.bias, (n_s, LAT, LON), None, None, split)
 
     with torch.no_grad():
         net.use_split_projections(False)
-        assert P.fused._resample_image(rec, rec.conv) is None
+        assert P.fused._split_image_of(rec, rec.conv) is None
         off, off_s = run()
         mod, mod_s = P.fused.patch_recover(rec, cat[None], Z, H4, W4, LAT, LON)      # the module's (batched) inference arm
         assert torch.equal(mod[0], off) and torch.equal(mod_s[0], off_s)
@@ -146,7 +146,7 @@ def test_patch_recovery(P, net):
     print(f"recover surface: split-flag {e_on:.3e} fp32 {e_off:.3e}")
     assert e_off < 2e-6 and e_on <= 1.5 * e_off
     # a surface launch listed as not dispatched is the fp32 kernel under either flag
-    if tuple(rec.conv_surface.weight.shape[:2]) in P.fused._RESAMPLE_SPLIT_NOT_DISPATCHED:
+    if tuple(rec.conv_surface.weight.shape[:2]) in P.fused._SPLIT_NOT_DISPATCHED:
         assert torch.equal(on_s, off_s) and rec.conv_surface not in P.ops._split_images
 
 
@@ -169,14 +169,14 @@ def test_lora_edit_and_drop(P, net):
         assert w_eff is not ml.linear.weight
         assert torch.equal(P.fused.sample_down(ml, x, Z, H4, W4), P.ops.linear_split(g, P.ops.split_weight_image(w_eff), 384))
         # in-place edit
-        image = P.ops.split_image(m.linear, m.linear.weight, padded=True)
-        assert image is P.ops._split_images[m.linear][2]
+        image = P.ops.split_image(m.linear, m.linear.weight)
+        assert image is P.ops._split_images[m.linear][1]
         keep = m.linear.weight.clone()
         m.linear.weight.copy_(torch.randn_like(keep) / 768 ** 0.5)
         edited = P.fused.sample_down(m, x, Z, H4, W4)
-        image2 = P.ops._split_images[m.linear][2]
-        assert image2 is not image and torch.equal(image2, P.ops.split_weight_image(m.linear.weight, padded=True))
-        assert torch.equal(edited, P.ops.linear_split(g, image2, 384, padded=True)) and not torch.equal(edited, base)
+        image2 = P.ops._split_images[m.linear][1]
+        assert image2 is not image and torch.equal(image2, P.ops.split_weight_image(m.linear.weight))
+        assert torch.equal(edited, P.ops.linear_split(g, image2, 384)) and not torch.equal(edited, base)
         m.linear.weight.copy_(keep)
         # the switch
         P.fused.sample_up(net.upsample, torch.randn(N1, 384, device="cuda"), Z, H2, W2, H4)

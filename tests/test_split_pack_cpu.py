@@ -12,16 +12,27 @@ from lds_banks import conflict_free  # noqa: E402
 from pangu_pytorch_amd import split_layout as L  # noqa: E402
 
 
-@pytest.mark.parametrize("N,K", [(192, 16), (576, 192), (384, 400)])
+@pytest.mark.parametrize("N,K", [(192, 16), (576, 192), (384, 400), (160, 384), (64, 384), (4, 16), (196, 48), (192, 32), (384, 16)])
 def test_image_layout_is_a_bijection(N, K):
-    idx = [L.image_index(N, K, p, n, k) for p in range(3) for n in range(N) for k in range(K)]
-    assert sorted(idx) == list(range(3 * N * K))
+    """(plane, row 0 .. image_rows(N) - 1, k) -> every one of the 3 image_rows(N) K bf16 slots exactly once."""
+    rows = L.image_rows(N)
+    assert rows % 192 == 0 and rows - 192 < N <= rows and L.served(N, K)
+    idx = [L.image_index(N, K, p, n, k) for p in range(3) for n in range(rows) for k in range(K)]
+    assert sorted(idx) == list(range(3 * rows * K))
     # a lane's fragment (8 consecutive k of one row and plane) is one aligned 16-B chunk
     for p in range(3):
         for n in (0, 1, 191, N - 1):
             for k in range(0, K, 8):
                 base = L.image_index(N, K, p, n, k)
                 assert base % 8 == 0 and [L.image_index(N, K, p, n, k + j) - base for j in range(8)] == list(range(8))
+
+
+def test_image_rows_and_refusals():
+    assert [L.image_rows(n) for n in (4, 160, 192, 196, 384, 388)] == [192, 192, 192, 384, 384, 576]
+    assert not L.served(6, 16) and not L.served(160, 24) and not L.served(0, 16)
+    assert L.served(160, 384)
+    # the rows of W have, in the image, the index they have in the image of the zero-extended weight
+    assert L.image_index(160, 384, 2, 159, 383) == L.image_index(192, 384, 2, 159, 383)
 
 
 def test_image_block_is_the_lds_stage_image():

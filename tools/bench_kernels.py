@@ -267,16 +267,16 @@ RESAMPLE_SHAPES = [  # (M, N, K, bias, name): the projections outside the blocks
 
 
 def resample():
-    """The fp32 forward's projections outside the blocks under both kernels: fp32 MFMA (ops.linear) and the column-padded
-    exact-split kernel (ops.linear_split(padded=True)); a process prints one sample per shape and kernel."""
+    """The fp32 forward's projections outside the blocks under both kernels: fp32 MFMA (ops.linear) and the exact-split
+    kernel (ops.linear_split; the column guard at N = 160, 64); a process prints one sample per shape and kernel."""
     for M, N, K, bias, name in RESAMPLE_SHAPES:
         a = torch.randn(M, K, device="cuda")
         w = torch.randn(N, K, device="cuda") / K ** 0.5
         b = torch.randn(N, device="cuda") if bias else None
         out = torch.empty(M, N, device="cuda")
-        image = ops.split_weight_image(w, padded=True)
+        image = ops.split_weight_image(w)
         ms = timeit(lambda: ops.linear(a, w, b, out=out))
-        mss = timeit(lambda: ops.linear_split(a, image, N, b, out=out, padded=True))
+        mss = timeit(lambda: ops.linear_split(a, image, N, b, out=out))
         fl = 2.0 * M * N * K
         print(f"resample {name:12s} M={M:6d} N={N:4d} K={K:4d}: fp32 MFMA {ms * 1e3:7.1f} us {fl / ms / 1e9:6.1f} TF/s   | split "
               f"{mss * 1e3:7.1f} us {fl / mss / 1e9:6.1f} TF/s   | {ms / mss:5.2f}x")

@@ -112,6 +112,21 @@ def split_cases(out, fp32_mfma_too=False):
     return out
 
 
+GUARDED_SHAPES = ((160, 384), (64, 384), (4, 16), (196, 48))      # (N, K), N % 192 != 0: the instantiation with the column guard
+
+
+def guarded_cases(out):
+    """linear_split where the last 192-column tile is cut (profiles/split_one_form_guarded_parent.json: the digests of the
+    commit before the image got one form, taken through its column-padded entry)."""
+    for M, (N, K) in itertools.product(MS, GUARDED_SHAPES):
+        a, w, b = t("a", M, K), t("w", N, K, scale=K ** -0.5), t("b", N)
+        img = ops.split_weight_image(w)
+        for act, bias in itertools.product((ops.ACT_NONE, ops.ACT_GELU), (b, None)):
+            y = ops.linear_split(a, img, N, bias, act=act)
+            out[f"linear_split M={M} N={N} K={K} {ACT_NAMES[act]} bias={int(bias is not None)}"] = digest(y)
+    return out
+
+
 def main():
     if "--edges" in sys.argv:
         json.dump(edges(), sys.stdout, indent=0, sort_keys=True)
@@ -125,6 +140,7 @@ def main():
             y = ops.linear(a, w, bias, act=act, aux=x)
             out[f"linear M={M} N={N} K={K} {ACT_NAMES[act]} bias={int(bias is not None)}"] = digest(y, *([x] if x is not None else []))
     split_cases(out, fp32_mfma_too=True)
+    guarded_cases(out)
     json.dump(out, sys.stdout, indent=0, sort_keys=True)
     print()
 

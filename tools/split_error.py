@@ -15,8 +15,8 @@ model at M = 4096, against the fp64 value of shortcut + s * LN(a W^T + b).
 each, fp32-MFMA kernel and exact-split kernel against the oracle evaluated in fp64.
 
   python tools/split_error.py --resample                                      (the projections outside the blocks)
---resample: down-sampling, the two of up-sampling, patch embedding and patch recovery (upper air and surface) at M = 4096 on the
-column-padded kernel, five seeds each."""
+--resample: down-sampling, the two of up-sampling, patch embedding and patch recovery (upper air and surface) at M = 4096, five
+seeds each."""
 import os
 import random
 import sys
@@ -51,16 +51,12 @@ def measure(a, w, b, act):
         ref = ref + b.double()
     if act:
         ref = torch.nn.functional.gelu(ref)
-    f32 = errors(ops.linear(a, w, b, act=act), ref)
-    if not ops.split_served(N, K):
-        return f32, None
+    f32 = errors(ops.linear(a, w, b, act=act), ref)      # (the split kernel serves every shape this one serves)
     return f32, errors(ops.linear_split(a, ops.split_weight_image(w), N, b, act=act), ref)
 
 
 def row(tag, M, N, K, act, bias, f32, split):
     head = f"| {tag} | {M}x{N}x{K} | {'gelu' if act else 'none'} | {'yes' if bias else 'no'} | {f32[0]:.3e} / {f32[1]:.3e} |"
-    if split is None:
-        return head + " not served | |"
     return head + f" {split[0]:.3e} / {split[1]:.3e} | {split[0] / f32[0]:.3f} |"
 
 
@@ -185,10 +181,10 @@ RESAMPLE = [(4096, 384, 768, False, "down"), (4096, 768, 384, False, "up1"), (40
 
 
 def main_resample():
-    print("# Column-padded exact-split projection at the shapes outside the blocks: error against an fp64 product\n")
-    print("rel-L2 / (max-abs / max) of `pangu_linear_fwd` (fp32 MFMA) and `pangu_linear_fwd_split_padded` on the same fp32 inputs, "
+    print("# Exact-split projection at the shapes outside the blocks: error against an fp64 product\n")
+    print("rel-L2 / (max-abs / max) of `pangu_linear_fwd` (fp32 MFMA) and `pangu_linear_fwd_split` on the same fp32 inputs, "
           "five seeds per shape; ratio = split rel-L2 / fp32 rel-L2.  Made by `tools/split_error.py --resample`.\n")
-    print("| projection | MxNxK | bias | seed | fp32 MFMA | split (padded) | ratio |")
+    print("| projection | MxNxK | bias | seed | fp32 MFMA | split | ratio |")
     print("|---|---|---|---|---|---|---|")
     worst, worst_abs = 0.0, 0.0
     for M, N, K, bias, name in RESAMPLE:
@@ -201,7 +197,7 @@ def main_resample():
             if bias:
                 ref = ref + b.double()
             f32 = errors(ops.linear(a, w, b), ref)
-            split = errors(ops.linear_split(a, ops.split_weight_image(w, padded=True), N, b, padded=True), ref)
+            split = errors(ops.linear_split(a, ops.split_weight_image(w), N, b), ref)
             print(f"| {name} | {M}x{N}x{K} | {'yes' if bias else 'no'} | {seed} | {f32[0]:.3e} / {f32[1]:.3e} | {split[0]:.3e} / "
                   f"{split[1]:.3e} | {split[0] / f32[0]:.3f} |")
             worst, worst_abs = max(worst, split[0] / f32[0]), max(worst_abs, split[0])
